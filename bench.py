@@ -18,9 +18,15 @@ GroupNorm partials.  Computed once per sampling run, outside it: the text
 K/V projection and the time-embedding / FiLM / time-token K/V tables of the whole schedule; the DDIM
 noise (eta = 1, the reference's default) is a table drawn before the region and read inside it; CFG
 dropout is off (sampling).  ``extra.end_to_end`` times whole ``sample()`` calls including all of that.
-The timed region of --steps steps is repeated (>= 3 regions) and the median region is the headline.
+The timed region is exactly --steps steps; --repeats R times R such regions and the median region is the headline.
 
-The JSON line also carries
+A plain run prints the headline only: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+    python bench.py --dump-outputs DIR
+writes what the timed path computed in its last step (the latents a caller of the stepper receives) as DIR/latents.npy,
+float32; the inputs (synthetic latents and conditioning, the seeded per-step noise table) are the same in every run.
+
+    python bench.py --full
+repeats the timed region (>= 3 regions, >= 600 steps, unless --repeats says otherwise) and the JSON line also carries
   roofline      -- the dominant kernel of the step, ``deep_kernel`` (the persistent launch that
                    runs every level below T'=64 as one phase list): algorithmic HBM bytes of its
                    phases / its measured launch duration (HIP events on the launch stream, the
@@ -36,7 +42,8 @@ The JSON line also carries
     python bench.py --mode train --gpus N     (torchrun as above)
 measures BASELINE configs[3]'s per-GPU shape instead: one optimiser step of the multi-task trainer
 (8 clips per GPU as 3/3/2 sub-batches through the CFG pair, gradient exchange over RCCL overlapped
-with the backward pass, clip + AdamW), reported in clips/s.
+with the backward pass, clip + AdamW), reported in clips/s; with N > 1, --full adds the exchange on its own and how much of it the
+backward pass hides.
 """
 import argparse
 import json
@@ -62,7 +69,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps steps each (0: as many as make >= 600 steps, at least 3)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each, the median region is the headline "
+                                                               "(default 1; with --full 0; 0: as many as make >= 600 steps, at least 3)")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline: repeated regions, rooflines, CPU baseline, "
+                                                        "parity, other dtypes / shapes / configurations (sampling); exchange figures (train, N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="sampling: write the latents of the last timed step to DIR/latents.npy (float32)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--length", type=int, default=1500)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"])
@@ -139,6 +150,22 @@ def timed_steps(st, steps, warmup, barrier, repeats=1):
         out.append(time.perf_counter() - t0)
         k += steps
     return out if repeats > 1 else out[0]
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  An array that does not fit its share of the 64 MB budget is
+    written as a fixed sample, every k-th element of its flattened values from the first, so two builds still compare element
+    for element."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().to(torch.float32).cpu().numpy()
+        if a.nbytes > share:
+            a = np.ascontiguousarray(a.reshape(-1)[::-(-a.nbytes // share)])
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def end_to_end_bench(model, st, B, T, device):
@@ -705,7 +732,7 @@ def train_mode(args, world, rank, device, dist, barrier):
                    + ", clip 0.7 + AdamW + LinearLR", "global_batch": B * world, "seq_len": T, "parallelism": f"ddp x{world}"},
         "loss": round(float(loss), 4),
     }
-    if world > 1:
+    if world > 1 and args.full:
         # the exchange on its own (blocking form: every region, then wait), the same steps with the exchange switched off, and from the
         # two how much of it the overlapped / recorded form hides behind the backward pass
         torch.cuda.synchronize()
@@ -766,6 +793,8 @@ def aggregate(dist, dt, steps, world, device):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.mode != "sample" or args.dry_run):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the sampling step: not with --mode train or --dry-run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -818,13 +847,20 @@ def main():
             raise SystemExit(f"bench.py: --scaling strong needs --batch {B} divisible by --gpus {world}")
         B = B // world
     model = UNetCFG1d(**cfg, init_seed=1234, compute_dtype=args.dtype, device=device)
+    # the per-step noise table that reset() draws comes from torch's generator: seeded, so every run denoises the same inputs
+    torch.manual_seed(1234)
     st = build_stepper(model, B, T, device, cfg_pair=False, use_graph=not args.no_graph)
-    # the timed region is EXACTLY --steps steps; it is repeated (>= 3 regions, >= 600 steps in total) and the MEDIAN region is the
-    # headline, so one clock hiccup of a 26 ms region cannot move it; every region's ms/step is in the line ("regions")
-    reps = args.repeats if args.repeats > 0 else max(3, -(-600 // max(1, args.steps)))
+    # the timed region is EXACTLY --steps steps; with --full it is repeated (>= 3 regions, >= 600 steps in total) and the MEDIAN region
+    # is the headline, so one clock hiccup of a 26 ms region cannot move it; every region's ms/step is in the line ("regions")
+    reps = args.repeats if args.repeats is not None else (0 if args.full else 1)
+    if reps <= 0:
+        reps = max(3, -(-600 // max(1, args.steps)))
     dts = timed_steps(st, args.steps, args.warmup, barrier, repeats=reps)
+    if args.dump_outputs and rank == 0:
+        st.check()                  # a persistent launch whose wait timed out leaves garbage: never written as a result
+        dump_outputs(args.dump_outputs, {"latents": st.x})
     per_region = []
-    for d in dts:
+    for d in (dts if reps > 1 else [dts]):
         d_, _ = aggregate(dist, d, args.steps, world, device)
         per_region.append(d_)
     dt = float(np.median(per_region))
@@ -847,7 +883,7 @@ def main():
                     "min": round(min(per_region) / args.steps * 1e3, 4), "median": round(dt / args.steps * 1e3, 4),
                     "max": round(max(per_region) / args.steps * 1e3, 4), "headline": "median"},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         long_levels = conv_roofline(st)
         deep = deep_roofline(st, args.dtype)
         if deep is not None:
@@ -991,6 +1027,7 @@ def main():
             if not args.tiny:
                 out["parity"] = golden_parity(cfg, device, model if args.dtype == "bf16" else None)
             out["extra"] = extra
+    if rank == 0:
         print(json.dumps(out))
     barrier()
     if dist is not None:

@@ -871,8 +871,34 @@ def gen_host():
     save("host_pins", **out)
 
 
+def gen_ckpt_sample():
+    """values behind host_pins' checkpoint digests: the reference's training state of gen_host (two AdamW steps on seeded gradients)
+    at up to 16 evenly spaced elements of every parameter and moment.  torch's CPU kernels round differently on different processors;
+    this is written only where the rebuilt state matches the recorded digests bit for bit."""
+    import hashlib
+    cfg = tiny_model_config()
+    rmodel, _ = _build(cfg)
+    params = list(rmodel.parameters())
+    ropt = torch.optim.AdamW(params, lr=3e-5, betas=(0.9, 0.95), weight_decay=0.1)
+    for it in range(2):
+        for i, p_ in enumerate(params):
+            p_.grad = T(fill_normal(f"ckpt.grad.{it}.{i}", tuple(p_.shape), 3)) * 1e-2
+        ropt.step()
+    digest = lambda t: hashlib.sha256(np.ascontiguousarray(t.detach().numpy()).tobytes()).hexdigest()[:16]
+    g = np.load(os.path.join(HERE, "host_pins.npz"))
+    rsd, rst = rmodel.state_dict(), ropt.state_dict()["state"]
+    assert {k: digest(v) for k, v in rsd.items()} == json.loads(str(g["ckpt.param_digest"]))
+    assert [digest(rst[i]["exp_avg"]) for i in range(len(params))] == json.loads(str(g["ckpt.exp_avg_digest"]))
+    assert [digest(rst[i]["exp_avg_sq"]) for i in range(len(params))] == json.loads(str(g["ckpt.exp_avg_sq_digest"]))
+    idx = [np.unique(np.linspace(0, p_.numel() - 1, min(p_.numel(), 16)).round().astype(np.int64)) for p_ in params]
+    pick = lambda ts: np.concatenate([t.detach().reshape(-1).numpy()[j] for t, j in zip(ts, idx)]).astype(np.float32)
+    save("ckpt_sample", names=np.array(json.dumps(list(rsd))), count=np.array([len(j) for j in idx], dtype=np.int64),
+         index=np.concatenate(idx), param=pick(list(rsd.values())), exp_avg=pick([rst[i]["exp_avg"] for i in range(len(params))]),
+         exp_avg_sq=pick([rst[i]["exp_avg_sq"] for i in range(len(params))]))
+
+
 if __name__ == "__main__":
-    which = set(sys.argv[1:]) or {"schedule", "units", "tiny", "sampler", "train", "full", "fullbench", "fulltrain", "encodec", "ddpm", "host", "ddim100", "fulltrain8", "vdm"}
+    which = set(sys.argv[1:]) or {"schedule", "units", "tiny", "sampler", "train", "full", "fullbench", "fulltrain", "encodec", "ddpm", "host", "ddim100", "fulltrain8", "vdm", "ckptsample"}
     model = None
     if "schedule" in which:
         print("schedule"); gen_schedule()
@@ -902,3 +928,5 @@ if __name__ == "__main__":
         print("vdm"); gen_vdm(model)
     if "host" in which:
         print("host"); gen_host()
+    if "ckptsample" in which:
+        print("ckptsample"); gen_ckpt_sample()

@@ -78,12 +78,27 @@ def _digest(t: torch.Tensor) -> str:
     return hashlib.sha256(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()).hexdigest()[:16]
 
 
+def _assert_near_recorded(s, kind, tensors):
+    """``tensors`` at the elements ckpt_sample.npz holds of the recorded state: torch's CPU kernels round differently on different
+    processors, so agreement is to 4 units in the last place of the tensor's largest sampled value (a wrong hyper-parameter, a
+    missing weight decay or bias correction is off by far more)"""
+    o = 0
+    for name, t, n in zip(json.loads(str(s["names"])), tensors, s["count"]):
+        want = s[kind][o:o + n]
+        got = t.detach().reshape(-1).numpy()[s["index"][o:o + n]]
+        tol = 4 * np.spacing(np.abs(want).max())
+        assert np.abs(got - want).max() <= tol, (kind, name, float(np.abs(got - want).max()), float(tol))
+        o += n
+
+
 def test_checkpoint_format_matches_reference_writer(tmp_path):
     """script_util.py:79-124.  The fixture was written while the reference's save_checkpoint / load_checkpoint and the build's
     exchanged files in both directions (asserted equal there, outcome recorded); here the same training state is rebuilt
-    without the reference -- torch AdamW on the CPU, two steps on seeded gradients -- and must give the recorded tensors bit for
-    bit after a trip through FusedAdamW and the build's checkpoint file."""
+    without the reference -- torch AdamW on the CPU, two steps on seeded gradients.  On a processor that rounds as the one that
+    wrote the fixture it is the recorded state bit for bit (digests); on any other it is that state to float32 rounding at the
+    sampled elements of ckpt_sample.npz.  A trip through FusedAdamW and the build's checkpoint file must give it back bit for bit."""
     g = golden("host_pins")
+    s = golden("ckpt_sample")
     assert json.loads(str(g["ckpt.cross_load"])) == {"reference_file_into_build": True, "build_file_into_reference": True}
     cfg = tiny_model_config()
     keys = json.loads(str(g["ckpt.keys"]))
@@ -97,8 +112,16 @@ def test_checkpoint_format_matches_reference_writer(tmp_path):
         for i, p in enumerate(params):
             p.grad = torch.from_numpy(fill_normal(f"ckpt.grad.{it}.{i}", tuple(p.shape), 3)) * 1e-2
         ref_opt.step()
-    want = json.loads(str(g["ckpt.param_digest"]))
-    assert {k: _digest(v) for k, v in model.state_dict().items()} == want
+    rst = ref_opt.state_dict()["state"]
+    want = {k: _digest(v) for k, v in model.state_dict().items()}
+    ea = [_digest(rst[i]["exp_avg"]) for i in range(len(params))]
+    eq = [_digest(rst[i]["exp_avg_sq"]) for i in range(len(params))]
+    if (want, ea, eq) != (json.loads(str(g["ckpt.param_digest"])), json.loads(str(g["ckpt.exp_avg_digest"])),
+                          json.loads(str(g["ckpt.exp_avg_sq_digest"]))):
+        assert json.loads(str(s["names"])) == keys
+        _assert_near_recorded(s, "param", list(model.state_dict().values()))
+        _assert_near_recorded(s, "exp_avg", [rst[i]["exp_avg"] for i in range(len(params))])
+        _assert_near_recorded(s, "exp_avg_sq", [rst[i]["exp_avg_sq"] for i in range(len(params))])
     assert sorted(ref_opt.state_dict()["param_groups"][0]) == json.loads(str(g["ckpt.opt_group_keys"]))
     # through the build's optimiser and file format and back
     for p in params:
@@ -115,7 +138,6 @@ def test_checkpoint_format_matches_reference_writer(tmp_path):
     _, _, lr, epoch = load_checkpoint(path, m2, optimizer=o2)
     assert (lr, epoch, o2.step_count) == (3e-5, 2, 2)
     assert {k: _digest(v) for k, v in m2.state_dict().items()} == want
-    ea, eq = json.loads(str(g["ckpt.exp_avg_digest"])), json.loads(str(g["ckpt.exp_avg_sq_digest"]))
     for i, (p, o) in enumerate(zip(o2.params, o2.offsets)):
         assert _digest(o2.exp_avg[o:o + p.numel()].view_as(p)) == ea[i]
         assert _digest(o2.exp_avg_sq[o:o + p.numel()].view_as(p)) == eq[i]

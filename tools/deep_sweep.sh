@@ -7,11 +7,11 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   if [[ "$v" == ENV:* ]]; then
-    out=$(env ${v#ENV:} python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>&1 | tail -1)
+    out=$(env ${v#ENV:} python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>&1 | tail -1)
   else
     lib=gpurun_out/libsweep_$i.so
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared $v -Iinclude -I$CS $SRC -o $lib || { echo "build failed: $v"; continue; }
-    out=$(JEN1_LIB=$PWD/$lib python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>&1 | tail -1)
+    out=$(JEN1_LIB=$PWD/$lib python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>&1 | tail -1)
     rm -f $lib
   fi
   echo "$v => $(echo "$out" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], "steps/s; deep", r.get("avg_launch_us"), "us,", r.get("us_per_phase"), "us/phase; long", r.get("long_levels",{}).get("conv_ms_per_step"))' 2>&1 | tail -1)"

@@ -4,7 +4,7 @@
 # run on the GPU box:      bash tools/long_experiments.sh > gpurun_out/long_experiments.txt
 cd $GRAFT_REPO_ROOT
 run() {
-  python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 l = d['roofline']['long_levels']

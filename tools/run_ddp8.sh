@@ -6,4 +6,4 @@ cd "$(dirname "$0")/.."
 N=${1:-8}; K=${2:-20}; W=${3:-8}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "${MASTER_PORT:-29517}" \
-  bench.py --mode train --gpus "$N" --steps "$K" --warmup "$W"
+  bench.py --mode train --full --gpus "$N" --steps "$K" --warmup "$W"
