@@ -25,6 +25,19 @@ from .engine import DeepProgram
 from .model import _STEPPER_CACHES, UNetCFG1d
 
 _OBJ = {"noise": 0, "x0": 1, "v": 2}
+# jen1_step_tail's bound on the rows of its sentinel table (csrc/elementwise.hip): a plan beyond it keeps the step-pack launch
+_TAIL_MAX_ROWS = 60000
+
+
+def _tail_eligible(poison_args) -> bool:
+    """the preconditions ``jen1_step_tail`` checks on the plan's sentinel table and statistics arena, mirrored on the host: a plan that
+    fails them runs ``jen1_cfg_ddim_step_pack`` with the sentinels and the arena reset at the head of the step instead of failing every
+    step"""
+    if poison_args is None:
+        return False
+    tab_ptr, n_rows, _, zero_ptr, zero_bytes = poison_args
+    return (bool(tab_ptr) and 1 <= int(n_rows) <= _TAIL_MAX_ROWS and bool(zero_ptr) and int(zero_ptr) % 16 == 0
+            and int(zero_bytes) > 0 and int(zero_bytes) % 16 == 0)
 
 
 def get_beta_schedule(schedule_name: str, num_diffusion_timesteps: int):
@@ -356,7 +369,13 @@ class DDIMStepper:
     replays of one graph with no host-side update in between (gdm.py:202-222).
 
     ``n_streams`` > 1 splits the batch into sub-batches on parallel HIP streams (implemented and
-    parity-tested; ROCm 7.2 serialises them, so the default is 1)."""
+    parity-tested; ROCm 7.2 serialises them, so the default is 1).
+
+    The plans come from the engine and are shared by every stepper of the same shape and ``plan_slot`` (DDIM, DDPM and VDM schedules
+    of the same length included), so a plan records which stepper last filled its schedule tables and conditioning: ``reset`` and
+    ``rebind`` take the plan over (refilling what another stepper left there), and ``step`` refuses to run on a plan that another
+    stepper has taken over since.  Writes into ``x`` (one part) or the plan's ``x_in`` / ``ctx_in`` between steps are noticed through
+    the tensors' version counters and re-pack the network input; ``set_x`` writes the latents of every part."""
 
     def __init__(self, gd: GaussianDiffusion, model: UNetCFG1d, shape, conditioning, causal=False, use_graph=True,
                  n_streams: Optional[int] = None, plan_slot: int = 0, mode: str = "ddim"):
@@ -384,6 +403,8 @@ class DDIMStepper:
         self._cond = conditioning                     # keep the conditioning tensors alive
         Co = model.spec.out_channels
         lib = self.lib
+        self.plan_slot = plan_slot
+        self._token = object()                        # (a plan's ``_stepper_token``: the stepper whose tables and conditioning it holds)
         self.parts = []
         b0 = 0
         used = {}
@@ -394,13 +415,8 @@ class DDIMStepper:
             # plan_slot: independent samplers of the same shape that run concurrently (serving) own separate buffers
             plan = eng.plan(nb, T, self.nrep, bool(causal), slot=slot + 1000 * plan_slot, n_t=S)
             sl = slice(b0, b0 + nb)
-            emb = conditioning["cross_attn_cond"][sl]
-            msk = None if conditioning["cross_attn_masks"] is None else conditioning["cross_attn_masks"][sl]
-            cc = conditioning["input_concat_cond"]
-            model._prepare(plan, plan.x_in, None, emb, msk, [None if cc is None else cc[sl]], None)
-            plan._cond_refs = (emb, msk)              # the K/V cache key holds weakrefs: keep the slices alive
-            plan.set_times(self.times)
-            plan.run_time(s0)                         # FiLM / time-token K/V tables for all S timesteps
+            self._bind(plan, sl, conditioning)
+            self._fill_times(plan, s0)                # FiLM / time-token K/V tables for all S timesteps
             net = plan.net_out
             # noise table slice of this sub-batch: row stride is the full batch, so give each part its own
             # contiguous table when the batch is split
@@ -420,7 +436,7 @@ class DDIMStepper:
                      and Co == model.spec.in_channels and os.environ.get("JEN1_CFG_STEP_SCALAR") is None)
             # ... and (JEN1_STEP_TAIL, default on) the same launch sets the next step's sentinels and zeroes its statistics arena, the
             # job of the node at the head of a step: a replayed step is the three persistent launches + jen1_step_tail + the partials' sum
-            tail = fused and os.environ.get("JEN1_STEP_TAIL", "1") == "1" and plan.poison_args is not None
+            tail = fused and os.environ.get("JEN1_STEP_TAIL", "1") == "1" and _tail_eligible(plan.poison_args)
             if fused:
                 rows_ptr, parts_ptr, ld_rows = plan.pack_rows
                 pk_args = args[:5] + (sp, ticket.data_ptr(), rows_ptr, parts_ptr, ld_rows) + args[8:]
@@ -452,6 +468,7 @@ class DDIMStepper:
         self._next = 0
         self._pack_dirty = True
         self._seen_serial = -1
+        self._seen_versions = None
         self._set_step(0)                             # the cached plan may carry a previous run's counter
         self.graph = None
         self.graphs = None
@@ -507,16 +524,39 @@ class DDIMStepper:
             self._pack_dirty = True
             self._set_step(nxt)
 
+    def _bind(self, plan, sl, conditioning) -> None:
+        """this part's conditioning into the plan: text K/V cache (when the tensors changed), concat context, CFG rows"""
+        emb = conditioning["cross_attn_cond"][sl]
+        msk = None if conditioning["cross_attn_masks"] is None else conditioning["cross_attn_masks"][sl]
+        cc = conditioning["input_concat_cond"]
+        self.model._prepare(plan, plan.x_in, None, emb, msk, [None if cc is None else cc[sl]], None)
+        plan._cond_refs = (emb, msk)                  # the K/V cache key holds weakrefs: keep the slices alive
+
+    def _fill_times(self, plan, stream=None) -> None:
+        """this stepper's schedule into the plan (integer or VDM float times, then the FiLM / time-token K/V tables of all S steps);
+        the plan is this stepper's from here on"""
+        plan.set_times(self.times)
+        plan.run_time(stream)
+        plan._stepper_token = self._token
+
+    def _claim(self) -> None:
+        """take over every plan that another stepper of the same shape has filled since this one last did: its conditioning and
+        schedule tables (the plans are shared, ``Engine.plan``), then a re-pack of the network input"""
+        for sl, plan, _, _ in self.parts:
+            if getattr(plan, "_stepper_token", None) is not self._token:
+                self._bind(plan, sl, self._cond)
+                self._fill_times(plan)
+                self._pack_dirty = True
+
     def rebind(self, conditioning) -> None:
         """new conditioning for the next trajectory of the same shape: text K/V cache (when the tensors changed), concat context;
-        the schedule tables and the captured graph stay (they depend on the weights and the shape only)"""
+        the schedule tables and the captured graph stay (they depend on the weights and the shape only) unless another stepper has
+        filled the plan since"""
         self._cond = conditioning
         for sl, plan, _, _ in self.parts:
-            emb = conditioning["cross_attn_cond"][sl]
-            msk = None if conditioning["cross_attn_masks"] is None else conditioning["cross_attn_masks"][sl]
-            cc = conditioning["input_concat_cond"]
-            self.model._prepare(plan, plan.x_in, None, emb, msk, [None if cc is None else cc[sl]], None)
-            plan._cond_refs = (emb, msk)
+            self._bind(plan, sl, conditioning)
+            if getattr(plan, "_stepper_token", None) is not self._token:
+                self._fill_times(plan)
         self._pack_dirty = True                    # (the concat context is part of the packed rows)
 
     @property
@@ -530,8 +570,21 @@ class DDIMStepper:
         return n + 1 + (1 if fused else 0)
 
     def mark_dirty(self) -> None:
-        """the latents (``x``) or the concat context were written from outside: the next step re-packs the network input from them"""
+        """the latents (``x``) or the concat context were written from outside: the next step re-packs the network input from them
+        (in-place torch writes into a plan's ``x_in`` / ``ctx_in`` are noticed without it; a raw-pointer write is not)"""
         self._pack_dirty = True
+
+    def set_x(self, x: torch.Tensor) -> None:
+        """overwrite the current latents [B, C, T] of every part (a repaint-style edit between steps); the next step re-packs the
+        network input from them"""
+        x = x.to(self.gd.device, torch.float32)
+        assert tuple(x.shape) == self.shape, f"set_x: latents of shape {tuple(x.shape)}, this stepper samples {self.shape}"
+        for sl, plan, _, _ in self.parts:
+            plan.x_in.copy_(x[sl])
+        self._pack_dirty = True
+
+    def _versions(self):
+        return tuple((plan.x_in._version, plan.ctx_in._version) for _, plan, _, _ in self.parts)
 
     def _pack_if_dirty(self):
         if self._pack_dirty:
@@ -560,7 +613,9 @@ class DDIMStepper:
 
     @property
     def x(self) -> torch.Tensor:
-        """current latents [B, C, T] (the sub-batches live in their plans' input buffers)."""
+        """current latents [B, C, T] (the sub-batches live in their plans' input buffers).  With one part this IS the plan's buffer,
+        and an in-place edit of it between steps is taken up by the next step; with the batch split over several parts it is a
+        concatenated COPY, and writes into it do not reach the sampler: edit through ``set_x``."""
         if len(self.parts) == 1:
             return self.parts[0][1].x_in
         return torch.cat([p.x_in for _, p, _, _ in self.parts], dim=0)
@@ -584,6 +639,7 @@ class DDIMStepper:
         """start a trajectory at x0; unless noises are injected per step, draw the whole per-step noise
         table now (gdm.py:218 draws randn_like inside the loop: same distribution, one launch)."""
         x0 = x0.to(torch.float32)
+        self._claim()                              # (another stepper of the same shape may have filled the shared plan since)
         if self._cap_modes is not None or not self.use_graph:
             self._sync_modes(claim=True)
         for sl, plan, _, _ in self.parts:
@@ -607,6 +663,11 @@ class DDIMStepper:
                 ntab[i].copy_(self.noise_all[i, sl])
 
     def step(self, i: int, noise: Optional[torch.Tensor] = None, drop_rows=None, set_rows=False):
+        for _, plan, _, _ in self.parts:
+            if getattr(plan, "_stepper_token", None) is not self._token:
+                raise RuntimeError(f"DDIMStepper.step: another stepper of shape {self.shape} and plan_slot={self.plan_slot} has used the "
+                                   "same plan since this one's reset(): its latents, tables and conditioning are gone.  Call reset() "
+                                   "to start again, or give samplers that run interleaved different plan_slot values")
         if i != self._next:
             self._set_step(i)
         if self._cap_modes is not None and self._cap_modes != self._modes():
@@ -622,6 +683,8 @@ class DDIMStepper:
             self._push_noise(i)
         if DeepProgram.host_serial[0] != self._seen_serial and any(t for _, t in self._part_fused.values()):
             self._pack_dirty = True                # (somebody launched a persistent program from the host since this stepper's last step)
+        if self._versions() != self._seen_versions:
+            self._pack_dirty = True                # (x_in / ctx_in written in place since the last step: st.x[..., a:b] = known)
         self._pack_if_dirty()
         if self.graphs is not None:
             cur = torch.cuda.current_stream(self.gd.device)
@@ -636,4 +699,5 @@ class DDIMStepper:
         else:
             self._run_all()
         self._seen_serial = DeepProgram.host_serial[0]
+        self._seen_versions = self._versions()
         self._next = i + 1
