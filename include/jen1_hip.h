@@ -349,6 +349,20 @@ int jen1_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, flo
 int jen1_adamw_step_counted(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                             float weight_decay, int32_t* step_counter, const float* gnorm_sq, float max_norm, int skip_nonfinite,
                             void* stream);
+/* jen1_adamw_step_counted with an exponential moving average (EMA) of the parameters in the same pass.  `ema`: flat float32, same
+ * length n and 16-byte alignment as p.  With t = step_counter[0] + 1 (the step being taken, the counter of the bias corrections):
+ *   skip_nonfinite drops the step            -> ema untouched (like p, m, v; t does not advance)
+ *   t % update_every != 0                    -> ema untouched
+ *   t <= update_after_step                   -> ema = p_new (a copy)
+ *   else, k = t - update_after_step          -> decay = warmup ? clamp(1 - (1 + k / inv_gamma)^-power, min_decay, beta) : beta
+ *                                               (in double on the device), ema = fma(1 - decay, p_new - ema, ema)
+ * p, m, v come out bit-identical to jen1_adamw_step_counted.  The schedule branch is taken once per launch from the device counter: no
+ * host synchronisation, capturable, the same two launches as jen1_adamw_step_counted.  Needs 0 <= min_decay <= beta < 1,
+ * update_every >= 1, update_after_step >= 0, inv_gamma > 0, power > 0. */
+int jen1_adamw_ema_step_counted(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int32_t* step_counter, const float* gnorm_sq, float max_norm, int skip_nonfinite,
+                                float* ema, double beta, int update_after_step, int update_every, int warmup, double inv_gamma,
+                                double power, double min_decay, void* stream);
 
 /*
  * Large-M matrix-core GEMM (csrc/big_gemm.hip): the cross-attention ``to_kv`` projection over the text context, reference

@@ -8,6 +8,8 @@
 //   jen1_adamw_step  : reads that device scalar, so clip + AdamW is ONE pass with no host synchronisation:
 //                      g' = g * min(1, max_norm / (||g|| + 1e-6));  p *= 1 - lr wd;  m, v updates;  p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
 //   A non-finite gradient norm skips the step (GradScaler semantics of trainer.py:147 when fp16 is on).
+//   jen1_adamw_ema_step_counted: the same step plus an exponential moving average of the new parameters in the same pass
+//                      (40 bytes per parameter on an update step, 32 on a step the EMA schedule leaves out).
 #include "common.h"
 
 namespace {
@@ -148,6 +150,95 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(AdamArgs a) {
   }
 }
 
+// AdamW with the EMA of the parameters in the same pass (jen1_adamw_ema_step_counted).  The update of p, m, v is adamw_kernel's,
+// element for element (adam1, same operand order); MODE is uniform per launch: 0 = this step leaves the EMA alone (32 B/param),
+// 1 = ema = p_new (before update_after_step), 2 = ema += (1 - decay) (p_new - ema) as one explicit fma (40 B/param)
+struct EmaArgs {
+  float* ema;
+  double beta, inv_gamma, power, min_decay;
+  int32_t update_after_step, update_every, warmup;
+};
+
+template <int MODE>
+__device__ __forceinline__ void ema1(float& e, float p, float w) {
+  if (MODE == 1) e = p;
+  if (MODE == 2) e = __fmaf_rn(w, p - e, e);
+}
+
+template <int MODE>
+__device__ __forceinline__ void adamw_ema_body(const AdamArgs& a, float coef, float* __restrict__ ema, float w) {
+  const int64_t nv = a.n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(a.p);
+  const float4* g4 = reinterpret_cast<const float4*>(a.g);
+  float4* m4 = reinterpret_cast<float4*>(a.m);
+  float4* v4 = reinterpret_cast<float4*>(a.v);
+  float4* e4 = reinterpret_cast<float4*>(ema);
+  const int64_t stride = (int64_t)gridDim.x * OPT_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; i < nv; i += stride) {
+    float4 p = p4[i], m = m4[i], v = v4[i];
+    float4 e;
+    if (MODE == 2) e = e4[i];
+    const float4 g = nt_load4(g4 + i);
+    adam1(p.x, g.x, m.x, v.x, a, coef);
+    adam1(p.y, g.y, m.y, v.y, a, coef);
+    adam1(p.z, g.z, m.z, v.z, a, coef);
+    adam1(p.w, g.w, m.w, v.w, a, coef);
+    p4[i] = p;
+    m4[i] = m;
+    v4[i] = v;
+    if (MODE != 0) {
+      ema1<MODE>(e.x, p.x, w);
+      ema1<MODE>(e.y, p.y, w);
+      ema1<MODE>(e.z, p.z, w);
+      ema1<MODE>(e.w, p.w, w);
+      e4[i] = e;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {
+    const int64_t j = (nv << 2) + threadIdx.x;
+    float p = a.p[j], m = a.m[j], v = a.v[j];
+    adam1(p, a.g[j], m, v, a, coef);
+    a.p[j] = p; a.m[j] = m; a.v[j] = v;
+    // the copy reads p back from memory: with the register value used twice the compiler pairs and contracts this tail's m / v / p
+    // updates differently from adamw_kernel's tail and the bits differ
+    if (MODE == 1) ema[j] = *reinterpret_cast<const volatile float*>(a.p + j);
+    if (MODE == 2) ema[j] = __fmaf_rn(w, p - ema[j], ema[j]);
+  }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void adamw_ema_kernel(AdamArgs a, EmaArgs ea) {
+  // step_counter is never null here: t = steps taken + 1 drives the bias corrections AND the EMA schedule
+  const int32_t taken = a.step_counter[0];
+  const double t = (double)(taken + 1);
+  a.bc1 = (float)(1.0 - pow((double)a.beta1, t));
+  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.beta2, t)));
+  float coef = 1.0f;
+  if (a.gnorm_sq) {
+    const float nrm = sqrtf(a.gnorm_sq[0]);
+    if (a.skip_nonfinite && !(nrm <= 3.0e38f)) return;          // a dropped step leaves the EMA untouched too
+    if (a.max_norm > 0.f) {
+      const float c = a.max_norm / (nrm + 1e-6f);
+      coef = c < 1.0f ? c : 1.0f;
+    }
+  }
+  // the EMA schedule of step t, decided once per launch from the device counter (the same value in every thread)
+  const int32_t ti = taken + 1;
+  if (ti % ea.update_every != 0) {
+    adamw_ema_body<0>(a, coef, ea.ema, 0.f);
+  } else if (ti <= ea.update_after_step) {
+    adamw_ema_body<1>(a, coef, ea.ema, 0.f);
+  } else {
+    double decay = ea.beta;
+    if (ea.warmup) {
+      const double k = (double)(ti - ea.update_after_step);
+      decay = 1.0 - pow(1.0 + k / ea.inv_gamma, -ea.power);
+      decay = decay < ea.beta ? decay : ea.beta;
+      decay = decay > ea.min_decay ? decay : ea.min_decay;
+    }
+    adamw_ema_body<2>(a, coef, ea.ema, (float)(1.0 - decay));
+  }
+}
+
 // behind adamw_kernel on the same stream: count the step unless it was skipped
 __global__ void adamw_advance_kernel(int32_t* step_counter, const float* gnorm_sq, int skip_nonfinite) {
   if (skip_nonfinite && gnorm_sq && !(sqrtf(gnorm_sq[0]) <= 3.0e38f)) return;
@@ -200,9 +291,36 @@ extern "C" int jen1_adamw_step_counted(float* p, const float* g, float* m, float
   return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, step_counter, gnorm_sq, max_norm, skip_nonfinite, stream);
 }
 
+static int adamw_launch_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, int32_t* step_counter, const float* gnorm_sq, float max_norm, int skip_nonfinite,
+                            const EmaArgs* ema, void* stream);
+
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, int32_t* step_counter, const float* gnorm_sq, float max_norm, int skip_nonfinite,
                         void* stream) {
+  return adamw_launch_ema(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, step_counter, gnorm_sq, max_norm, skip_nonfinite,
+                          nullptr, stream);
+}
+
+extern "C" int jen1_adamw_ema_step_counted(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                           float eps, float weight_decay, int32_t* step_counter, const float* gnorm_sq, float max_norm,
+                                           int skip_nonfinite, float* ema, double beta, int update_after_step, int update_every,
+                                           int warmup, double inv_gamma, double power, double min_decay, void* stream) {
+  JEN1_CHECK(step_counter, "adamw_ema_step_counted: null step counter");
+  JEN1_CHECK(ema && (reinterpret_cast<uintptr_t>(ema) & 15) == 0, "adamw_ema_step_counted: null / unaligned EMA buffer");
+  JEN1_CHECK(beta >= 0.0 && beta < 1.0 && min_decay >= 0.0 && min_decay <= beta, "adamw_ema_step_counted: need 0 <= min_decay <= beta < 1");
+  JEN1_CHECK(update_every >= 1 && update_after_step >= 0 && inv_gamma > 0.0 && power > 0.0, "adamw_ema_step_counted: bad EMA schedule");
+  EmaArgs ea;
+  ea.ema = ema;
+  ea.beta = beta; ea.inv_gamma = inv_gamma; ea.power = power; ea.min_decay = min_decay;
+  ea.update_after_step = update_after_step; ea.update_every = update_every; ea.warmup = warmup ? 1 : 0;
+  return adamw_launch_ema(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, 1, step_counter, gnorm_sq, max_norm, skip_nonfinite, &ea,
+                          stream);
+}
+
+static int adamw_launch_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, int32_t* step_counter, const float* gnorm_sq, float max_norm, int skip_nonfinite,
+                            const EmaArgs* ema, void* stream) {
   JEN1_CHECK(p && g && m && v && n > 0, "adamw_step: null pointer or empty tensor");
   JEN1_CHECK(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0,
              "adamw_step: buffers must be 16-byte aligned");
@@ -218,7 +336,10 @@ static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n,
   const int64_t nv = n >> 2;
   int64_t blocks = (nv + OPT_THREADS - 1) / OPT_THREADS;
   blocks = blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks);
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, s, a);
+  if (ema)
+    hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, s, a, *ema);
+  else
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, s, a);
   if (step_counter) hipLaunchKernelGGL(adamw_advance_kernel, dim3(1), dim3(1), 0, s, step_counter, gnorm_sq, skip_nonfinite);
   JEN1_HIP(hipGetLastError());
   return 0;

@@ -5,9 +5,13 @@ Same file layout and loader tolerances as /root/reference/utils/script_util.py:7
 keep the model's current value and a ``_orig_mod.`` prefix (torch.compile) is accepted.  The model's parameters use
 the reference ``state_dict`` key schema (SURVEY.md Appendix C), so files are interchangeable in both directions;
 after loading, the HIP engine repacks its weights on next use.
+
+With an EMA of the weights (jen1_amd/ema.py) the file carries one more key, ``'ema'``: the EMA weights under the same key schema.
+The reference's loader reads only ``model`` / ``optimizer`` / ``epoch`` / ``learning_rate``, so such files still load there.
 """
 from __future__ import annotations
 
+import logging
 import os
 from typing import Optional
 
@@ -18,22 +22,34 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") else model
 
 
-def save_checkpoint(model, optimizer, lr, iteration, checkpoint_path, logger=None) -> None:
-    """script_util.py:79-90 (without the old-checkpoint cleanup, which is run management, not format)."""
+def save_checkpoint(model, optimizer, lr, iteration, checkpoint_path, logger=None, ema=None) -> None:
+    """script_util.py:79-90 (without the old-checkpoint cleanup, which is run management, not format).  ``ema``: a ``ParamEMA`` over the
+    model's parameters, saved under ``'ema'`` (its ``state_dict()``); the other keys are unchanged."""
     if logger is not None:
         logger.info(f"Saving model and optimizer state at iteration {iteration} to {checkpoint_path}")
-    torch.save({"model": _unwrap(model).state_dict(), "epoch": iteration,
-                "optimizer": optimizer.state_dict() if optimizer is not None else None, "learning_rate": lr}, checkpoint_path)
+    ck = {"model": _unwrap(model).state_dict(), "epoch": iteration,
+          "optimizer": optimizer.state_dict() if optimizer is not None else None, "learning_rate": lr}
+    if ema is not None:
+        ck["ema"] = ema.state_dict(_unwrap(model))
+    torch.save(ck, checkpoint_path)
 
 
-def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None):
-    """script_util.py:93-124: returns (model, optimizer, learning_rate, epoch)."""
+def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None, ema=None, weights: str = "model"):
+    """script_util.py:93-124: returns (model, optimizer, learning_rate, epoch).
+
+    ``ema``: a ``ParamEMA`` over the model's parameters, restored from the file's ``'ema'`` entry; a file without one (a checkpoint of the
+    reference, or of a run without EMA) seeds it from the weights loaded into the model.  ``weights="ema"`` loads the file's EMA weights into
+    the model instead of ``'model'`` (sampling from the EMA); the file must have them."""
+    if weights not in ("model", "ema"):
+        raise ValueError(f"weights must be 'model' or 'ema', not {weights!r}")
     assert os.path.isfile(checkpoint_path)
     ck = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
     epoch, learning_rate = ck["epoch"], ck["learning_rate"]
+    if weights == "ema" and ck.get("ema") is None:
+        raise KeyError(f"{checkpoint_path} holds no EMA weights ('ema'): it was saved without an EMA; load weights='model'")
     if optimizer is not None:
         optimizer.load_state_dict(ck["optimizer"])
-    saved = ck["model"]
+    saved = ck[weights]
     m = _unwrap(model)
     new_state = {}
     for k, v in m.state_dict().items():
@@ -47,6 +63,12 @@ def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None):
             new_state[k] = v
     m.load_state_dict(new_state)
     _repack(m)
+    if ema is not None:
+        if ck.get("ema") is not None:
+            ema.load_state_dict(ck["ema"], model=m)
+        else:
+            ema.load_state_dict(m.state_dict(), model=m)
+            (logger or logging.getLogger(__name__)).info(f"{checkpoint_path} has no EMA weights: the EMA starts from the loaded '{weights}' weights")
     if logger is not None:
         logger.info(f"Loaded checkpoint '{checkpoint_path}' (epoch {epoch})")
     return model, optimizer, learning_rate, epoch

@@ -132,6 +132,21 @@ class TrainConfig:
     device: str = "cuda"
     diffusion_type: str = "gdm"
     optimizer_config: OptimizerConfig = field(default_factory=OptimizerConfig)
+    # reference utils/config.py:90 (a switch with no code behind it there): an EMA of the weights, updated in the optimiser's launch
+    # (jen1_amd/ema.py); the ema_* fields are ParamEMA's arguments
+    use_ema: bool = False
+    ema_beta: float = 0.9999
+    ema_update_after_step: int = 100
+    ema_update_every: int = 10
+    ema_warmup: bool = True
+    ema_inv_gamma: float = 1.0
+    ema_power: float = 2.0 / 3.0
+    ema_min_decay: float = 0.0
+
+    def ema_kwargs(self) -> dict:
+        """``ParamEMA``'s keyword arguments from the ema_* fields"""
+        return {k[4:]: getattr(self, k) for k in ("ema_beta", "ema_update_after_step", "ema_update_every", "ema_warmup", "ema_inv_gamma",
+                                                  "ema_power", "ema_min_decay")}
 
 
 @dataclass

@@ -52,8 +52,12 @@ class Jen1:
                  cross_attn_cond_ids: Sequence[str] = ("prompt",), global_cond_ids: Sequence[str] = (),
                  input_concat_ids: Sequence[str] = ("masked_input", "mask"), *, audio_encoder, conditioner: Callable,
                  convert_audio: Optional[Callable] = None, model_config: Optional[dict] = None,
-                 diffusion_config: Optional[GDMConfig] = None, compute_dtype: str = "bf16", vdm_config: Optional[VDMConfig] = None):
-        self.ckpt_path, self.device, self.sample_rate = ckpt_path, device, sample_rate
+                 diffusion_config: Optional[GDMConfig] = None, compute_dtype: str = "bf16", vdm_config: Optional[VDMConfig] = None,
+                 weights: str = "model"):
+        """``weights="ema"`` (keyword-only, not in the reference): sample from the checkpoint's EMA weights (``checkpoint.load_checkpoint``)"""
+        if weights not in ("model", "ema"):
+            raise ValueError(f"weights must be 'model' or 'ema', not {weights!r}")
+        self.ckpt_path, self.device, self.sample_rate, self.weights = ckpt_path, device, sample_rate, weights
         self.conditioner, self.audio_encoder = conditioner, audio_encoder
         self.cross_attn_cond_ids, self.global_cond_ids, self.input_concat_ids = cross_attn_cond_ids, global_cond_ids, input_concat_ids
         self.convert_audio = convert_audio or (lambda wav, sr, target_sr, target_channels: wav)
@@ -84,7 +88,7 @@ class Jen1:
                               context_embedding_max_length=cfg.pop("context_embedding_max_length", None),
                               compute_dtype=self.compute_dtype, device=self.device, **cfg)
             if self.ckpt_path is not None:
-                model, _, _, _ = load_checkpoint(self.ckpt_path, model)
+                model, _, _, _ = load_checkpoint(self.ckpt_path, model, weights=self.weights)
             self._model = model.eval()
         return diffusion, self._model
 

@@ -150,6 +150,8 @@ SYMBOLS = {
     "jen1_grad_sqnorm_ws": (c_int, [_P, c_int64, _P, _P, _P]),
     "jen1_adamw_step": (c_int, [_P, _P, _P, _P, c_int64] + [c_float] * 5 + [c_int, _P, c_float, c_int, _P]),
     "jen1_adamw_step_counted": (c_int, [_P, _P, _P, _P, c_int64] + [c_float] * 5 + [_P, _P, c_float, c_int, _P]),
+    "jen1_adamw_ema_step_counted": (c_int, [_P, _P, _P, _P, c_int64] + [c_float] * 5 + [_P, _P, c_float, c_int] +
+                                    [_P, C.c_double, c_int, c_int, c_int, C.c_double, C.c_double, C.c_double, _P]),
     "jen1_memset_zero": (c_int, [_P, c_int64, _P]),
     "jen1_big_gemm": (c_int, [C.POINTER(BGemmArgs), _P]),
     "jen1_big_gemm_tn": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),

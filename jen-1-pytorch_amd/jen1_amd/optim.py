@@ -68,6 +68,7 @@ class FusedAdamW:
         self._gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._sq_scratch: Optional[torch.Tensor] = None       # block partials + arrival ticket of the norm, owned by this optimiser
         self.post_step_hooks = []      # callables run after every step (TrainGraph.invalidate: re-pack the compute weights)
+        self.ema = None                # ema.ParamEMA attached to this optimiser: step() then updates it in the same launch
 
     @property
     def step_count(self) -> int:
@@ -103,11 +104,14 @@ class FusedAdamW:
             L.check(lib.jen1_grad_sqnorm_ws(self.flat_grad.data_ptr(), self.numel, self._gnorm_sq.data_ptr(), self._sq_scratch.data_ptr(), s),
                     "jen1_grad_sqnorm_ws")
             gn = self._gnorm_sq.data_ptr()
-        L.check(lib.jen1_adamw_step_counted(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                            self.exp_avg_sq.data_ptr(), self.numel, float(self.lr if lr is None else lr), float(self.betas[0]),
-                                            float(self.betas[1]), float(self.eps), float(self.weight_decay), self._steps.data_ptr(), gn,
-                                            float(self.max_norm or 0.0), 1 if self.skip_nonfinite else 0, s),
-                "jen1_adamw_step_counted")
+        if self.ema is not None:
+            self.ema.launch(lib, self, float(self.lr if lr is None else lr), gn, s)      # jen1_adamw_ema_step_counted
+        else:
+            L.check(lib.jen1_adamw_step_counted(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
+                                                self.exp_avg_sq.data_ptr(), self.numel, float(self.lr if lr is None else lr),
+                                                float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                                                self._steps.data_ptr(), gn, float(self.max_norm or 0.0), 1 if self.skip_nonfinite else 0, s),
+                    "jen1_adamw_step_counted")
         for h in self.post_step_hooks:
             h()
 

@@ -54,15 +54,21 @@ class UnifiedMultiTaskTrainer:
       grad_clip     the clip norm of the fused optimiser step (nn.utils.clip_grad_norm_, trainer.py:145)
       grad_accum_every   micro-batches per optimiser step (trainer.py:139-149)
     Keyword-only extras (not in the reference): ``process_group``, ``rng``, ``compute_dtype``, ``use_graph``,
-    ``allow_uneven_tasks``, ``bucket_bytes``, ``merge_tasks``, ``merge_causal``, ``grad_dtype``.  ``UnifiedMultiTaskTrainer.build(model, diffusion, conditioner,
-    optimizer, ...)`` is the short form for code that has no config object."""
+    ``allow_uneven_tasks``, ``bucket_bytes``, ``merge_tasks``, ``merge_causal``, ``grad_dtype``, ``use_ema`` / ``ema_kwargs``.
+    ``UnifiedMultiTaskTrainer.build(model, diffusion, conditioner, optimizer, ...)`` is the short form for code that has no config object.
+
+    EMA (``config.use_ema``, the reference's switch of utils/config.py:90; ``use_ema=`` overrides it): a ``ParamEMA`` (jen1_amd/ema.py)
+    with the config's ``ema_*`` settings, updated by the optimiser's own launch, saved by ``eval_all_tasks`` under ``'ema'``.  Every rank
+    keeps its own: the parameters are identical after the gradient exchange, so the EMAs are too.  Validation stays on the trained
+    weights."""
 
     def __init__(self, config, rank: int, epoch_str: int, global_step: int, model, diffusion, conditioner: Callable, dls, optimizer,
                  lr_scheduler, scaler, logger, writers, grad_clip, grad_accum_every: int,
                  cross_attn_cond_ids: Sequence[str] = ("prompt",), global_cond_ids: Sequence[str] = (),
                  input_concat_ids: Sequence[str] = ("masked_input", "mask"), *, process_group=None, rng=_random,
                  compute_dtype: Optional[str] = None, use_graph: bool = True, allow_uneven_tasks: bool = False,
-                 bucket_bytes: int = 128 << 20, merge_tasks: bool = True, merge_causal: bool = True, grad_dtype: str = "f32"):
+                 bucket_bytes: int = 128 << 20, merge_tasks: bool = True, merge_causal: bool = True, grad_dtype: str = "f32",
+                 use_ema: Optional[bool] = None, ema_kwargs: Optional[dict] = None):
         self.config = config
         self.tasks = tuple(getattr(config, "tasks", TASKS))
         self.device = getattr(config, "device", "cuda")
@@ -80,6 +86,13 @@ class UnifiedMultiTaskTrainer:
         scaling = bool(scaler is not None and getattr(scaler, "is_enabled", lambda: False)())
         optimizer, lr_scheduler = adopt_optimizer(list(model.parameters()), optimizer, lr_scheduler, grad_clip, scaling)
         self.optimizer, self.lr_scheduler = optimizer, lr_scheduler
+        self.ema = None
+        if bool(getattr(config, "use_ema", False)) if use_ema is None else use_ema:
+            from .ema import ParamEMA
+            kw = {k: getattr(config, f"ema_{k}") for k in ("beta", "update_after_step", "update_every", "warmup", "inv_gamma", "power",
+                                                         "min_decay") if hasattr(config, f"ema_{k}")}
+            kw.update(ema_kwargs or {})
+            self.ema = ParamEMA(optimizer, model=model, **kw)
         self.graph = model.train_graph(compute_dtype)
         self.graph.attach_optimizer(optimizer)
         # forward + backward of one sub-batch replayed as a HIP graph (train.GraphedLossStep); the loss scaling of the
@@ -104,11 +117,12 @@ class UnifiedMultiTaskTrainer:
     def build(cls, model, diffusion, conditioner: Callable, optimizer: FusedAdamW, lr_scheduler: Optional[LinearLR] = None,
               grad_accum_every: int = 10, tasks: Sequence[str] = TASKS, device="cuda", cross_attn_cond_ids: Sequence[str] = ("prompt",),
               global_cond_ids: Sequence[str] = (), input_concat_ids: Sequence[str] = ("masked_input", "mask"), dls=None, save_dir: str = "",
-              eval_interval: int = 30, num_epoch: int = 100, **extras):
+              eval_interval: int = 30, num_epoch: int = 100, use_ema: bool = False, ema_kwargs: Optional[dict] = None, **extras):
         """the trainer without a config object / logger / writers (tests, bench.py): same object, short argument list"""
         from .config import TrainConfig
         cfg = TrainConfig(tasks=list(tasks), device=device, grad_accum_every=grad_accum_every, save_dir=save_dir, eval_interval=eval_interval,
-                          num_epoch=num_epoch)
+                          num_epoch=num_epoch, use_ema=bool(use_ema))
+        extras.update(use_ema=bool(use_ema), ema_kwargs=ema_kwargs)
         return cls(cfg, 0, 0, 0, model, diffusion, conditioner, dls, optimizer, lr_scheduler, None, None, None, optimizer.max_norm,
                    grad_accum_every, cross_attn_cond_ids, global_cond_ids, input_concat_ids, **extras)
 
@@ -286,7 +300,7 @@ class UnifiedMultiTaskTrainer:
                     lr = self.optimizer.lr if hasattr(self.optimizer, "lr") else None
                 self.last_checkpoint = os.path.join(save_dir, f"Jen1_step_{self.global_step}_loss_{self.best_avg_total_loss}.pth")
                 save_checkpoint(model=self.model, optimizer=self.optimizer, lr=lr, iteration=epoch, checkpoint_path=self.last_checkpoint,
-                                logger=self.logger)
+                                logger=self.logger, ema=self.ema)
         if self.rank == 0 and self.writer is not None:
             self.writer.add_scalar("loss/val_total", avg_total, self.global_step)
         self.model.train()
