@@ -318,6 +318,28 @@ int jen1_step_tail(const void* net, const float* x, const float* noise, const fl
                    uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
                    float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                    const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream);
+/* The known-region blend of an inpainting / continuation trajectory, on the result of the step's own update and before it is stored,
+ * packed and summed (so x_out, the rows of every CFG replica and the statistics partials all hold the blended latents):
+ *   kn = p known + q eps_k;   x_next' = keep kn + (1 - keep) x_next,   (p, q) = kb[2 s], kb[2 s + 1] for the step counter s
+ * every product and sum rounded to float32 by itself (no fused multiply-add): with a 0 / 1 keep it is an exact select, and it is what
+ * the torch expression keep * (p * known + q * eps_k) + (1 - keep) * x_next gives.  known, eps_k: [B][C][T] float32; keep: [B][T] float32
+ * in [0, 1]; kb: [S][2] float32, the noise level the latents are at AFTER step s ((1, 0) in the last row).  All four non-null and 4-byte
+ * aligned; everything else as in the entry point without _blend. */
+typedef struct jen1_blend_args {
+  const float* known;
+  const float* eps_k;
+  const float* keep;
+  const float* kb;
+} jen1_blend_args;
+int jen1_cfg_ddim_step_pack_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
+                                  uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                                  float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                  const jen1_blend_args* blend, void* stream);
+int jen1_step_tail_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
+                         uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                         float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                         const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
+                         const jen1_blend_args* blend, void* stream);
 
 /* CFG combine + rescale only: writes the guided denoiser output [B][C][T] float32 (model.py:362-369). */
 int jen1_cfg_combine(const void* net, float* out, int B, int C, int T, int ld, float embedding_scale, int scale_cfg,

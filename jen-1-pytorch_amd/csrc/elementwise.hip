@@ -465,7 +465,11 @@ __device__ __forceinline__ float half_wave_sum(float v) {           // over the 
 }
 
 // (bx, by) of (nbx, nby): the block's place in the step's grid -- the kernel's own grid, or the leading blocks of step_tail_kernel's
-template <typename T, bool DDIM>
+// BLEND (a compile-time variant; the plain instantiations carry none of it): the known-region blend of an inpainting / continuation
+// trajectory on the step's result, before it is stored, packed and summed:
+//   kn = p known + q eps_k;  x_next' = keep kn + (1 - keep) x_next      with (p, q) = kb[step], keep one value per (b, t)
+// every product and sum rounded to float32 by itself (the order of the torch expression keep * (p * known + q * eps_k) + (1 - keep) * xn)
+template <typename T, bool DDIM, bool BLEND = false>
 __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, const float* __restrict__ x,
                                                   const float* __restrict__ noise, const float* __restrict__ coef,
                                                   float* __restrict__ x_out, float* __restrict__ eps_out,
@@ -474,20 +478,29 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
                                                   float scale, int scale_cfg, float phi, int objective, int clip_x0,
                                                   int32_t* adv_step, unsigned* __restrict__ adv_ticket,
                                                   T* __restrict__ rows, float* __restrict__ parts, int ld_rows,
-                                                  const int bx, const int by, const int nbx, const int nby) {
+                                                  const int bx, const int by, const int nbx, const int nby,
+                                                  const jen1_blend_args bl = jen1_blend_args{nullptr, nullptr, nullptr, nullptr}) {
   // (no implicit multiply-add fusion in here: the body is inlined into two kernels and, whichever one runs a step, the trajectory must
   // come out on the same bits; the statistics sums below fuse explicitly, as pack_input_kernel's do)
 #pragma clang fp contract(off)
+  static_assert(DDIM || !BLEND, "the blend is part of the sampler step");
   extern __shared__ float tile[];   // [C][33] + one word per 8 channels
   float cf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float kp = 0.f, kq = 0.f;          // BLEND: the row of kb, read through the same counter value as coef (before the ticket below)
   if (DDIM) {
+    const float* kbr = BLEND ? bl.kb : nullptr;
     if (step_idx) {                  // (see cfg_step_kernel: the counter may be advanced by this launch's last block)
       const int st = __hip_atomic_load(step_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       coef += (size_t)st * 8;
       if (noise) noise += (size_t)st * B * C * Tn;
+      if (BLEND) kbr += (size_t)st * 2;
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) cf[i] = coef[i];
+    if (BLEND) {
+      kp = kbr[0];
+      kq = kbr[1];
+    }
   }
   const int t0 = bx * 32, b = by;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -505,6 +518,24 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
       const size_t idx = ((size_t)b * C + (c < C ? c : 0)) * Tn + tcl;
       xv[blk][k] = DDIM ? x[idx] : 0.f;
       nv[blk][k] = (DDIM && noise && cf[4] != 0.f) ? noise[idx] : 0.f;   // (a deterministic row -- sigma = 0 -- reads no noise)
+    }
+  }
+  // BLEND: the known latents and their noise are [C][T]-major like x and depend on the network output no more than x does: requested
+  // here, behind x and the step's noise and ahead of the network rows; keep is one value per thread (a thread owns one t in phase 2).
+  // What stays live across phase 1 is kn alone (32 registers at most), not the two operands.
+  float kn[BLEND ? NBLK : 1][8];
+  float kw = 0.f;
+  if (BLEND) {
+    kw = bl.keep[(size_t)b * Tn + tcl];
+#pragma unroll
+    for (int blk = 0; blk < NBLK; ++blk) {
+      if (blk * 64 >= C) continue;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int c = blk * 64 + ty + 8 * k;
+        const size_t idx = ((size_t)b * C + (c < C ? c : 0)) * Tn + tcl;
+        kn[BLEND ? blk : 0][k] = kp * bl.known[idx] + kq * bl.eps_k[idx];
+      }
     }
   }
   // phase 1: 8 rows per pass (4 waves x 2 half waves), every load of the block in flight before the first reduction
@@ -603,6 +634,7 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
       } else if (last == 1.f) xn = x0;
       else if (last == 2.f) xn = x0 * sa_n + cc * xt + sg * nv[blk][k];
       else xn = x0 * sa_n + cc * eps + sg * nv[blk][k];
+      if (BLEND) xn = kw * kn[BLEND ? blk : 0][k] + (1.0f - kw) * xn;
       x_out[idx] = xn;
       if (eps_out) eps_out[idx] = eps;
       if (x0_out) x0_out[idx] = x0;
@@ -651,6 +683,20 @@ __global__ __launch_bounds__(256) void cfg_step_vec_kernel(const T* __restrict__
                              clip_x0, adv_step, adv_ticket, rows, parts, ld_rows, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y);
 }
 
+// the step + pack launch with the known-region blend (jen1_cfg_ddim_step_pack_blend)
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_step_vec_blend_kernel(const T* __restrict__ net, const float* __restrict__ x,
+                                                                  const float* __restrict__ noise, const float* __restrict__ coef,
+                                                                  float* __restrict__ x_out, int B, int C, int Tn, int ld, int nrep,
+                                                                  float scale, int scale_cfg, float phi, int objective, int clip_x0,
+                                                                  int32_t* adv_step, unsigned* __restrict__ adv_ticket,
+                                                                  T* __restrict__ rows, float* __restrict__ parts, int ld_rows,
+                                                                  const jen1_blend_args bl) {
+  cfg_step_vec_body<T, true, true>(net, x, noise, coef, x_out, nullptr, nullptr, adv_step, B, C, Tn, ld, nrep, scale, scale_cfg, phi,
+                                   objective, clip_x0, adv_step, adv_ticket, rows, parts, ld_rows, blockIdx.x, blockIdx.y, gridDim.x,
+                                   gridDim.y, bl);
+}
+
 // ---- the tail of a replayed sampler step as ONE launch: the first nbx * nby blocks are the CFG / DDIM step + the next step's packed input
 // (above), the blocks behind them set every tensor of the next step's persistent launches to the all-ones sentinel and zero the
 // statistics arena (deep_kernel.hip's poison_kernel: same table, same 8 blocks per row).  Nothing orders the two jobs -- the step
@@ -687,6 +733,37 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const TailArgs a) {
   const uint4 ones = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
   for (size_t i = (size_t)px * 256 + threadIdx.x; i < n; i += (size_t)8 * 256) p[i] = ones;
   if (a.sync && pid == 0 && threadIdx.x == 0) a.sync[0] = 0u;
+}
+
+// jen1_step_tail_blend: the same launch with the blend variant of the step in its leading blocks.  (The fill of the blocks behind them is
+// step_tail_kernel's, restated as a function: calling it from step_tail_kernel too changes that kernel's instruction stream, and the
+// plain tail is pinned as it is.)
+__device__ __forceinline__ void tail_fill(const TailArgs& a, const int pid) {
+  const int px = pid & 7, py = pid >> 3;
+  if (py >= a.n_tab) {
+    uint4* z = reinterpret_cast<uint4*>(a.zero_ptr);
+    const size_t n = a.zero_bytes >> 4;
+    const size_t nblk = (size_t)8 * a.z_rows, blk = (size_t)(py - a.n_tab) * 8 + px;
+    for (size_t i = blk * 256 + threadIdx.x; i < n; i += nblk * 256) z[i] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const TailPoisonEntry e = a.tab[py];
+  uint4* p = reinterpret_cast<uint4*>(e.ptr);
+  const size_t n = e.bytes >> 4;
+  const uint4 ones = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+  for (size_t i = (size_t)px * 256 + threadIdx.x; i < n; i += (size_t)8 * 256) p[i] = ones;
+  if (a.sync && pid == 0 && threadIdx.x == 0) a.sync[0] = 0u;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void step_tail_blend_kernel(const TailArgs a, const jen1_blend_args bl) {
+  const int nbx = (a.Tn + 31) / 32, nstep = nbx * a.B;
+  if ((int)blockIdx.x < nstep) {
+    cfg_step_vec_body<T, true, true>((const T*)a.net, a.x, a.noise, a.coef, a.x_out, nullptr, nullptr, a.step_idx, a.B, a.C, a.Tn, a.ld,
+                                     a.nrep, a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket, (T*)a.rows, a.parts,
+                                     a.ld_rows, (int)blockIdx.x % nbx, (int)blockIdx.x / nbx, nbx, a.B, bl);
+    return;
+  }
+  tail_fill(a, (int)blockIdx.x - nstep);
 }
 
 }  // namespace
@@ -794,7 +871,7 @@ template <bool DDIM>
 static int launch_cfg(const void* net, const float* x, const float* noise, const float* coef, float* x_out, float* eps_out,
                       float* x0_out, const int32_t* step_idx, int B, int C, int T, int ld, int nrep, float scale, int scale_cfg, float phi,
                       int objective, int clip_x0, int dtype, void* stream, int32_t* adv_step = nullptr, unsigned* adv_ticket = nullptr,
-                      void* rows = nullptr, float* parts = nullptr, int ld_rows = 0) {
+                      void* rows = nullptr, float* parts = nullptr, int ld_rows = 0, const jen1_blend_args* bl = nullptr) {
   JEN1_CHECK(net && x_out, "cfg step: null pointer");
   JEN1_CHECK(nrep == 1 || nrep == 2, "cfg step: nrep must be 1 or 2");
   JEN1_CHECK(C >= 2 && C <= 256 && ld >= C, "cfg step: C must be in [2, 256]");
@@ -810,7 +887,18 @@ static int launch_cfg(const void* net, const float* x, const float* noise, const
     JEN1_CHECK(ld_rows >= C && ((size_t)ld_rows * esz) % 16 == 0 && ((uintptr_t)rows & 15) == 0 && ((uintptr_t)parts & 7) == 0,
                "cfg step + pack: rows must be 16-byte aligned with ld_rows >= C");
   }
-  if (vec && dtype == JEN1_F32) {
+  if (bl) {
+    JEN1_CHECK(rows && (dtype == JEN1_F32 || dtype == JEN1_BF16), "cfg step + blend: only with the packed rows, in f32 or bf16");
+    if (dtype == JEN1_F32) {
+      auto kern = cfg_step_vec_blend_kernel<float>;
+      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const float*)net, x, noise, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (float*)rows, parts, ld_rows, *bl);
+    } else {
+      auto kern = cfg_step_vec_blend_kernel<bf16_t>;
+      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16_t*)net, x, noise, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (bf16_t*)rows, parts, ld_rows, *bl);
+    }
+  } else if (vec && dtype == JEN1_F32) {
     auto kern = cfg_step_vec_kernel<float, DDIM>;
     JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const float*)net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (float*)rows, parts, ld_rows);
@@ -872,10 +960,55 @@ extern "C" int jen1_cfg_ddim_step_pack(const void* net, const float* x, const fl
                           scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows);
 }
 
+// the known-region blend's own operands (the *_blend entry points): all there, float32-aligned
+static int check_blend(const jen1_blend_args* bl, const char* who) {
+  JEN1_CHECK(bl, "%s: null blend arguments", who);
+  JEN1_CHECK(bl->known && bl->eps_k && bl->keep && bl->kb, "%s: null known / eps_k / keep / kb", who);
+  JEN1_CHECK((((uintptr_t)bl->known | (uintptr_t)bl->eps_k | (uintptr_t)bl->keep | (uintptr_t)bl->kb) & 3) == 0,
+             "%s: known / eps_k / keep / kb must be 4-byte aligned", who);
+  return 0;
+}
+
+extern "C" int jen1_cfg_ddim_step_pack_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
+                                             int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C,
+                                             int T, int ld, int nrep, float embedding_scale, int scale_cfg, float scale_phi,
+                                             int objective, int clip_x0, int dtype, const jen1_blend_args* blend, void* stream) {
+  JEN1_CHECK(x && coef && step_idx && ticket && rows && parts, "cfg_ddim_step_pack_blend: null x / coef / step_idx / ticket / rows / parts");
+  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_pack_blend: bad objective");
+  if (check_blend(blend, "cfg_ddim_step_pack_blend")) return 1;
+  return launch_cfg<true>(net, x, noise, coef, x_out, nullptr, nullptr, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
+                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows, blend);
+}
+
+static int step_tail_impl(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
+                          uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                          float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                          const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
+                          const jen1_blend_args* bl);
+
 extern "C" int jen1_step_tail(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
                              uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
                              float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                              const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream) {
+  return step_tail_impl(net, x, noise, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
+                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, nullptr);
+}
+
+extern "C" int jen1_step_tail_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
+                                    uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                                    float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                    const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
+                                    const jen1_blend_args* blend, void* stream) {
+  if (check_blend(blend, "step_tail_blend")) return 1;
+  return step_tail_impl(net, x, noise, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
+                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, blend);
+}
+
+static int step_tail_impl(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
+                          uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                          float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                          const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
+                          const jen1_blend_args* bl) {
   JEN1_CHECK(net && x && coef && x_out && step_idx && ticket && rows && parts, "step_tail: null net / x / coef / x_out / step_idx / ticket / rows / parts");
   JEN1_CHECK(objective >= 0 && objective <= 2 && (nrep == 1 || nrep == 2), "step_tail: bad objective / nrep");
   JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "step_tail: bad dtype");
@@ -898,7 +1031,15 @@ extern "C" int jen1_step_tail(const void* net, const float* x, const float* nois
   const dim3 grid(nstep + 8 * (n_rows + zrows));
   const size_t lds = sizeof(float) * ((size_t)C * 33 + C / 8 + 1);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == JEN1_F32) {
+  if (bl && dtype == JEN1_F32) {
+    auto kern = step_tail_blend_kernel<float>;
+    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, *bl);
+  } else if (bl) {
+    auto kern = step_tail_blend_kernel<bf16_t>;
+    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, *bl);
+  } else if (dtype == JEN1_F32) {
     auto kern = step_tail_kernel<float>;
     JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);

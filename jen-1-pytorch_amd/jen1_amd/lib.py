@@ -114,6 +114,11 @@ class RepackEntry(C.Structure):
                 ("s0", c_int64), ("s1", c_int64), ("s2", c_int64), ("tile0", c_int), ("ld2", c_int), ("dst2", c_void_p)]
 
 
+class BlendArgs(C.Structure):
+    """mirror of ``jen1_blend_args`` (include/jen1_hip.h): the known-region blend's operands, device pointers"""
+    _fields_ = [("known", c_void_p), ("eps_k", c_void_p), ("keep", c_void_p), ("kb", c_void_p)]
+
+
 class KvLayer(C.Structure):
     """mirror of ``jen1_kv_layer`` (include/jen1_train.h)"""
     _fields_ = [("w", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("gw", c_void_p), ("ggamma", c_void_p), ("gbeta", c_void_p),
@@ -144,6 +149,9 @@ SYMBOLS = {
     "jen1_cfg_ddim_step_adv": (c_int, [_P] * 9 + [c_int] * 5 + [c_float, c_int, c_float, c_int, c_int, c_int, _P]),
     "jen1_cfg_ddim_step_pack": (c_int, [_P] * 9 + [c_int] * 6 + [c_float, c_int, c_float, c_int, c_int, c_int, _P]),
     "jen1_step_tail": (c_int, [_P] * 9 + [c_int] * 6 + [c_float, c_int, c_float, c_int, c_int, c_int, _P, c_int, _P, _P, c_int64, _P]),
+    "jen1_cfg_ddim_step_pack_blend": (c_int, [_P] * 9 + [c_int] * 6 + [c_float, c_int, c_float, c_int, c_int, c_int, C.POINTER(BlendArgs), _P]),
+    "jen1_step_tail_blend": (c_int, [_P] * 9 + [c_int] * 6 + [c_float, c_int, c_float, c_int, c_int, c_int, _P, c_int, _P, _P, c_int64,
+                                     C.POINTER(BlendArgs), _P]),
     "jen1_cfg_combine": (c_int, [_P, _P] + [c_int] * 4 + [c_float, c_int, c_float, c_int, _P]),
     "jen1_grad_sqnorm": (c_int, [_P, c_int64, _P, _P]),
     "jen1_grad_sqnorm_scratch_bytes": (c_int64, []),

@@ -33,7 +33,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from .diffusion import DDIMStepper, _check_model_errors
+from .diffusion import DDIMStepper, _check_model_errors, blend_known, check_known
 from .model import _STEPPER_CACHES, UNetCFG1d
 
 
@@ -73,6 +73,15 @@ class VDM(torch.nn.Module):
         rows = [[al[i].item(), sg[i].item(), al[i + 1].item(), sg[i + 1].item(), 0.0, 3.0, 0.0, 0.0] for i in range(step)]
         return (torch.tensor(rows, dtype=torch.float32, device=self.device).reshape(step, 8), steps[:step].to(self.device, torch.float32))
 
+    def blend_table(self, step: Optional[int] = None) -> Tuple[torch.Tensor, Tuple[float, float]]:
+        """the known-region blend's table kb [step, 2] (see ``GaussianDiffusion.blend_table``): (alpha_{i+1}, sigma_{i+1}) of row i of
+        ``coeff_table``, exactly (1, 0) in the last row, and the level before step 0, (alpha_0, sigma_0)"""
+        rows, _ = self.coeff_table(step)
+        kb = rows[:, 2:4].clone()
+        kb[-1, 0], kb[-1, 1] = 1.0, 0.0
+        p0, q0 = rows[0, 0:2].tolist()
+        return kb.contiguous(), (p0, q0)
+
     @torch.no_grad()
     def p_sample(self, x, i: int, model, conditioning, causal, dropout_rows=None):
         """one step of the repaired loop: ``i`` is the step index (see the module docstring)"""
@@ -84,8 +93,13 @@ class VDM(torch.nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, model, shape, conditioning, step=1000, return_all_timesteps=False, init_data=None, causal=False, *,
-                      init_noise=None, dropout_rows: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True, fused: bool = True):
+                      init_noise=None, dropout_rows: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True, fused: bool = True,
+                      known=None, keep_mask=None, known_noise=None):
+        """``known`` / ``keep_mask`` / ``known_noise`` (not in the reference): the known-region blend, as in
+        ``GaussianDiffusion.ddim_sample``, at the levels of ``blend_table``"""
+        known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
         audio = torch.randn(shape, device=self.device) if init_noise is None else init_noise.to(self.device, torch.float32).reshape(shape)
+        eps_k = audio if known_noise is None else known_noise
         if init_data is not None:
             audio = audio + init_data
         self.steps = torch.linspace(1., 0., step + 1, device=self.device)
@@ -98,16 +112,25 @@ class VDM(torch.nn.Module):
             cache = self.__dict__.setdefault("_steppers", {})
             _STEPPER_CACHES.add(self)            # (an engine invalidation drops this model's steppers: model._drop_steppers_of)
             key = (id(model), id(model.engine()), tuple(shape), bool(causal), bool(use_graph), int(step), float(self.embedding_scale),
-                   bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic))
+                   bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic), known is not None)
             st = cache.get(key)
             if st is not None and st.model is model and st.eng is model.engine():
                 st.rebind(conditioning)
             else:
-                st = DDIMStepper(self, model, shape, conditioning, causal, use_graph, None, 0, "vdm")
+                st = DDIMStepper(self, model, shape, conditioning, causal, use_graph, None, 0, "vdm", blend=known is not None)
                 if len(cache) >= 8:
                     cache.pop(next(iter(cache)))
                 cache[key] = st
+            if known is not None:
+                st.set_known(known, keep_mask, noise=eps_k)
             st.reset(audio)
+            if known is not None:
+                audios = [st.x.clone()]
+        elif known is not None:
+            kb, (p0, q0) = self.blend_table(step)
+            kb = kb.tolist()
+            audio = blend_known(audio, known, keep_mask, eps_k, p0, q0)
+            audios = [audio]
         B = shape[0]
         for i in range(step):
             drop = None
@@ -123,6 +146,8 @@ class VDM(torch.nn.Module):
                     audios.append(st.x.clone())
             else:
                 audio = self.p_sample(audio, i, model, conditioning, causal, drop)
+                if known is not None:
+                    audio = blend_known(audio, known, keep_mask, eps_k, *kb[i])
                 audios.append(audio)
         if fused:
             audio = st.x.clone()
