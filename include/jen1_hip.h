@@ -340,6 +340,22 @@ int jen1_step_tail_blend(const void* net, const float* x, const float* noise, co
                          float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                          const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
                          const jen1_blend_args* blend, void* stream);
+/* The multistep row of DPM-Solver++(2M), kind 4 = {sqrt_recip, sqrt_recipm1, b0, a, b1, 4, sqrt_alpha_t, sqrt(1 - alpha_t)}:
+ *   x_next = (b0 x0 + a x_t) + b1 x0_prev
+ * every product and sum rounded to float32 by itself.  hist [B][C][T] float32 stands where the entry points above take the noise table
+ * (this update draws none): the clipped x0 prediction of the previous step, read when b1 != 0 and rewritten with this step's x0 by
+ * every row (the kind-1 row included).  Non-null, 4-byte aligned, not the latents.  blend: the known-region blend on x_next as above
+ * (hist keeps the unblended x0), or NULL for none.  Rows of the other kinds are evaluated as above with their noise term at zero.
+ * Everything else as in jen1_cfg_ddim_step_pack / jen1_step_tail. */
+int jen1_cfg_ddim_step_pack_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out, int32_t* step_idx,
+                               uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                               float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                               const jen1_blend_args* blend, void* stream);
+int jen1_step_tail_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out, int32_t* step_idx,
+                      uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                      float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                      const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
+                      const jen1_blend_args* blend, void* stream);
 
 /* CFG combine + rescale only: writes the guided denoiser output [B][C][T] float32 (model.py:362-369). */
 int jen1_cfg_combine(const void* net, float* out, int B, int C, int T, int ld, float embedding_scale, int scale_cfg,

@@ -469,7 +469,13 @@ __device__ __forceinline__ float half_wave_sum(float v) {           // over the 
 // trajectory on the step's result, before it is stored, packed and summed:
 //   kn = p known + q eps_k;  x_next' = keep kn + (1 - keep) x_next      with (p, q) = kb[step], keep one value per (b, t)
 // every product and sum rounded to float32 by itself (the order of the torch expression keep * (p * known + q * eps_k) + (1 - keep) * xn)
-template <typename T, bool DDIM, bool BLEND = false>
+// MS (a compile-time variant as well): the multistep row of DPM-Solver++(2M), kind 4 = {.., .., b0, a, b1, 4, .., ..}:
+//   x_next = (b0 x0 + a x_t) + b1 x0_prev
+// x0_prev is this element of ``hist`` [B][C][T], where the previous step left its clipped x0 prediction, and this step's x0 goes back
+// into the same element (the thread that reads it is the one that writes it).  The variant reads no noise, and a row with b1 == 0 --
+// the first of a trajectory, every row at order 1 -- does not read the history either.  Before the blend: the history holds the
+// unblended x0.
+template <typename T, bool DDIM, bool BLEND = false, bool MS = false>
 __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, const float* __restrict__ x,
                                                   const float* __restrict__ noise, const float* __restrict__ coef,
                                                   float* __restrict__ x_out, float* __restrict__ eps_out,
@@ -479,11 +485,13 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
                                                   int32_t* adv_step, unsigned* __restrict__ adv_ticket,
                                                   T* __restrict__ rows, float* __restrict__ parts, int ld_rows,
                                                   const int bx, const int by, const int nbx, const int nby,
-                                                  const jen1_blend_args bl = jen1_blend_args{nullptr, nullptr, nullptr, nullptr}) {
+                                                  const jen1_blend_args bl = jen1_blend_args{nullptr, nullptr, nullptr, nullptr},
+                                                  float* __restrict__ hist = nullptr) {
   // (no implicit multiply-add fusion in here: the body is inlined into two kernels and, whichever one runs a step, the trajectory must
   // come out on the same bits; the statistics sums below fuse explicitly, as pack_input_kernel's do)
 #pragma clang fp contract(off)
   static_assert(DDIM || !BLEND, "the blend is part of the sampler step");
+  static_assert(DDIM || !MS, "the multistep row is part of the sampler step");
   extern __shared__ float tile[];   // [C][33] + one word per 8 channels
   float cf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float kp = 0.f, kq = 0.f;          // BLEND: the row of kb, read through the same counter value as coef (before the ticket below)
@@ -509,6 +517,10 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
   // phase-2 operands: [C][T]-major, 8 channels per 64-channel block and thread
   constexpr int NBLK = 4;           // C <= 256
   float xv[NBLK][8], nv[NBLK][8];
+  // MS: the previous x0 depends on the network output no more than x does and is requested with it, in the registers the noise has
+  // in the other variants (a clamped column or channel reads an element it does not own and never uses it)
+  float hp[MS ? NBLK : 1][8];
+  const bool hload = MS && cf[5] == 4.f && cf[4] != 0.f;               // (uniform)
 #pragma unroll
   for (int blk = 0; blk < NBLK; ++blk) {
     if (blk * 64 >= C) continue;     // uniform
@@ -517,7 +529,8 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
       const int c = blk * 64 + ty + 8 * k;
       const size_t idx = ((size_t)b * C + (c < C ? c : 0)) * Tn + tcl;
       xv[blk][k] = DDIM ? x[idx] : 0.f;
-      nv[blk][k] = (DDIM && noise && cf[4] != 0.f) ? noise[idx] : 0.f;   // (a deterministic row -- sigma = 0 -- reads no noise)
+      nv[blk][k] = (DDIM && !MS && noise && cf[4] != 0.f) ? noise[idx] : 0.f;   // (a deterministic row -- sigma = 0 -- reads no noise)
+      if (MS) hp[MS ? blk : 0][k] = hload ? hist[idx] : 0.f;
     }
   }
   // BLEND: the known latents and their noise are [C][T]-major like x and depend on the network output no more than x does: requested
@@ -627,13 +640,15 @@ __device__ __forceinline__ void cfg_step_vec_body(const T* __restrict__ net, con
         eps = (sr * xt - x0) / srm1;
       }
       float xn;
-      if (last == 3.f) {             // VDM row (see cfg_step_kernel)
+      if (MS && last == 4.f) xn = (sa_n * x0 + cc * xt) + sg * hp[MS ? blk : 0][k];
+      else if (last == 3.f) {        // VDM row (see cfg_step_kernel)
         x0 = sr * xt - srm1 * o;
         eps = srm1 * xt + sr * o;
         xn = sa_n * x0 + cc * eps;
       } else if (last == 1.f) xn = x0;
       else if (last == 2.f) xn = x0 * sa_n + cc * xt + sg * nv[blk][k];
       else xn = x0 * sa_n + cc * eps + sg * nv[blk][k];
+      if (MS) hist[idx] = x0;
       if (BLEND) xn = kw * kn[BLEND ? blk : 0][k] + (1.0f - kw) * xn;
       x_out[idx] = xn;
       if (eps_out) eps_out[idx] = eps;
@@ -695,6 +710,20 @@ __global__ __launch_bounds__(256) void cfg_step_vec_blend_kernel(const T* __rest
   cfg_step_vec_body<T, true, true>(net, x, noise, coef, x_out, nullptr, nullptr, adv_step, B, C, Tn, ld, nrep, scale, scale_cfg, phi,
                                    objective, clip_x0, adv_step, adv_ticket, rows, parts, ld_rows, blockIdx.x, blockIdx.y, gridDim.x,
                                    gridDim.y, bl);
+}
+
+// the step + pack launch with the multistep row, with or without the blend (jen1_cfg_ddim_step_pack_ms)
+template <typename T, bool BLEND>
+__global__ __launch_bounds__(256) void cfg_step_vec_ms_kernel(const T* __restrict__ net, const float* __restrict__ x,
+                                                               float* __restrict__ hist, const float* __restrict__ coef,
+                                                               float* __restrict__ x_out, int B, int C, int Tn, int ld, int nrep,
+                                                               float scale, int scale_cfg, float phi, int objective, int clip_x0,
+                                                               int32_t* adv_step, unsigned* __restrict__ adv_ticket,
+                                                               T* __restrict__ rows, float* __restrict__ parts, int ld_rows,
+                                                               const jen1_blend_args bl) {
+  cfg_step_vec_body<T, true, BLEND, true>(net, x, nullptr, coef, x_out, nullptr, nullptr, adv_step, B, C, Tn, ld, nrep, scale, scale_cfg,
+                                          phi, objective, clip_x0, adv_step, adv_ticket, rows, parts, ld_rows, blockIdx.x, blockIdx.y,
+                                          gridDim.x, gridDim.y, bl, hist);
 }
 
 // ---- the tail of a replayed sampler step as ONE launch: the first nbx * nby blocks are the CFG / DDIM step + the next step's packed input
@@ -761,6 +790,19 @@ __global__ __launch_bounds__(256) void step_tail_blend_kernel(const TailArgs a, 
     cfg_step_vec_body<T, true, true>((const T*)a.net, a.x, a.noise, a.coef, a.x_out, nullptr, nullptr, a.step_idx, a.B, a.C, a.Tn, a.ld,
                                      a.nrep, a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket, (T*)a.rows, a.parts,
                                      a.ld_rows, (int)blockIdx.x % nbx, (int)blockIdx.x / nbx, nbx, a.B, bl);
+    return;
+  }
+  tail_fill(a, (int)blockIdx.x - nstep);
+}
+
+// jen1_step_tail_ms: the same launch with the multistep variant of the step in its leading blocks (a.noise is not read)
+template <typename T, bool BLEND>
+__global__ __launch_bounds__(256) void step_tail_ms_kernel(const TailArgs a, float* __restrict__ hist, const jen1_blend_args bl) {
+  const int nbx = (a.Tn + 31) / 32, nstep = nbx * a.B;
+  if ((int)blockIdx.x < nstep) {
+    cfg_step_vec_body<T, true, BLEND, true>((const T*)a.net, a.x, nullptr, a.coef, a.x_out, nullptr, nullptr, a.step_idx, a.B, a.C, a.Tn,
+                                            a.ld, a.nrep, a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket,
+                                            (T*)a.rows, a.parts, a.ld_rows, (int)blockIdx.x % nbx, (int)blockIdx.x / nbx, nbx, a.B, bl, hist);
     return;
   }
   tail_fill(a, (int)blockIdx.x - nstep);
@@ -871,7 +913,8 @@ template <bool DDIM>
 static int launch_cfg(const void* net, const float* x, const float* noise, const float* coef, float* x_out, float* eps_out,
                       float* x0_out, const int32_t* step_idx, int B, int C, int T, int ld, int nrep, float scale, int scale_cfg, float phi,
                       int objective, int clip_x0, int dtype, void* stream, int32_t* adv_step = nullptr, unsigned* adv_ticket = nullptr,
-                      void* rows = nullptr, float* parts = nullptr, int ld_rows = 0, const jen1_blend_args* bl = nullptr) {
+                      void* rows = nullptr, float* parts = nullptr, int ld_rows = 0, const jen1_blend_args* bl = nullptr,
+                      float* hist = nullptr) {
   JEN1_CHECK(net && x_out, "cfg step: null pointer");
   JEN1_CHECK(nrep == 1 || nrep == 2, "cfg step: nrep must be 1 or 2");
   JEN1_CHECK(C >= 2 && C <= 256 && ld >= C, "cfg step: C must be in [2, 256]");
@@ -887,7 +930,22 @@ static int launch_cfg(const void* net, const float* x, const float* noise, const
     JEN1_CHECK(ld_rows >= C && ((size_t)ld_rows * esz) % 16 == 0 && ((uintptr_t)rows & 15) == 0 && ((uintptr_t)parts & 7) == 0,
                "cfg step + pack: rows must be 16-byte aligned with ld_rows >= C");
   }
-  if (bl) {
+  if (hist) {
+    JEN1_CHECK(rows && (dtype == JEN1_F32 || dtype == JEN1_BF16), "cfg step + multistep: only with the packed rows, in f32 or bf16");
+    const jen1_blend_args none{nullptr, nullptr, nullptr, nullptr};
+#define JEN1_MS_LAUNCH(TY, BL)                                                                                                          \
+    do {                                                                                                                                \
+      auto kern = cfg_step_vec_ms_kernel<TY, BL>;                                                                                       \
+      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);                                                                                              \
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const TY*)net, x, hist, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, \
+                         objective, clip_x0, adv_step, adv_ticket, (TY*)rows, parts, ld_rows, bl ? *bl : none);                         \
+    } while (0)
+    if (dtype == JEN1_F32 && bl) JEN1_MS_LAUNCH(float, true);
+    else if (dtype == JEN1_F32) JEN1_MS_LAUNCH(float, false);
+    else if (bl) JEN1_MS_LAUNCH(bf16_t, true);
+    else JEN1_MS_LAUNCH(bf16_t, false);
+#undef JEN1_MS_LAUNCH
+  } else if (bl) {
     JEN1_CHECK(rows && (dtype == JEN1_F32 || dtype == JEN1_BF16), "cfg step + blend: only with the packed rows, in f32 or bf16");
     if (dtype == JEN1_F32) {
       auto kern = cfg_step_vec_blend_kernel<float>;
@@ -984,7 +1042,7 @@ static int step_tail_impl(const void* net, const float* x, const float* noise, c
                           uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
                           float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                           const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
-                          const jen1_blend_args* bl);
+                          const jen1_blend_args* bl, float* hist = nullptr);
 
 extern "C" int jen1_step_tail(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
                              uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
@@ -1004,11 +1062,38 @@ extern "C" int jen1_step_tail_blend(const void* net, const float* x, const float
                         scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, blend);
 }
 
+// the multistep forms: ``hist`` (the previous step's x0, read and rewritten) stands where the plain entry points take the noise table,
+// which this update does not have; ``blend`` may be null (no known-region blend)
+extern "C" int jen1_cfg_ddim_step_pack_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out,
+                                          int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C,
+                                          int T, int ld, int nrep, float embedding_scale, int scale_cfg, float scale_phi,
+                                          int objective, int clip_x0, int dtype, const jen1_blend_args* blend, void* stream) {
+  JEN1_CHECK(x && coef && step_idx && ticket && rows && parts, "cfg_ddim_step_pack_ms: null x / coef / step_idx / ticket / rows / parts");
+  JEN1_CHECK(hist && ((uintptr_t)hist & 3) == 0, "cfg_ddim_step_pack_ms: the history buffer must be there and 4-byte aligned");
+  JEN1_CHECK(hist != x && hist != x_out, "cfg_ddim_step_pack_ms: the history buffer must not be the latents");
+  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_pack_ms: bad objective");
+  if (blend && check_blend(blend, "cfg_ddim_step_pack_ms")) return 1;
+  return launch_cfg<true>(net, x, nullptr, coef, x_out, nullptr, nullptr, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
+                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows, blend, hist);
+}
+
+extern "C" int jen1_step_tail_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out, int32_t* step_idx,
+                                 uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
+                                 float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                 const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
+                                 const jen1_blend_args* blend, void* stream) {
+  JEN1_CHECK(hist && ((uintptr_t)hist & 3) == 0, "step_tail_ms: the history buffer must be there and 4-byte aligned");
+  JEN1_CHECK(hist != x && hist != x_out, "step_tail_ms: the history buffer must not be the latents");
+  if (blend && check_blend(blend, "step_tail_ms")) return 1;
+  return step_tail_impl(net, x, nullptr, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
+                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, blend, hist);
+}
+
 static int step_tail_impl(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
                           uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
                           float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                           const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
-                          const jen1_blend_args* bl) {
+                          const jen1_blend_args* bl, float* hist) {
   JEN1_CHECK(net && x && coef && x_out && step_idx && ticket && rows && parts, "step_tail: null net / x / coef / x_out / step_idx / ticket / rows / parts");
   JEN1_CHECK(objective >= 0 && objective <= 2 && (nrep == 1 || nrep == 2), "step_tail: bad objective / nrep");
   JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "step_tail: bad dtype");
@@ -1031,7 +1116,20 @@ static int step_tail_impl(const void* net, const float* x, const float* noise, c
   const dim3 grid(nstep + 8 * (n_rows + zrows));
   const size_t lds = sizeof(float) * ((size_t)C * 33 + C / 8 + 1);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (bl && dtype == JEN1_F32) {
+  if (hist) {
+    const jen1_blend_args none{nullptr, nullptr, nullptr, nullptr};
+#define JEN1_MS_LAUNCH(TY, BL)                                                      \
+    do {                                                                            \
+      auto kern = step_tail_ms_kernel<TY, BL>;                                      \
+      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);                                          \
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, hist, bl ? *bl : none);  \
+    } while (0)
+    if (dtype == JEN1_F32 && bl) JEN1_MS_LAUNCH(float, true);
+    else if (dtype == JEN1_F32) JEN1_MS_LAUNCH(float, false);
+    else if (bl) JEN1_MS_LAUNCH(bf16_t, true);
+    else JEN1_MS_LAUNCH(bf16_t, false);
+#undef JEN1_MS_LAUNCH
+  } else if (bl && dtype == JEN1_F32) {
     auto kern = step_tail_blend_kernel<float>;
     JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, *bl);

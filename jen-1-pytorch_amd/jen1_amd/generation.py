@@ -136,9 +136,15 @@ class Jen1:
 
     def generate(self, prompt, seed: int = -1, steps: int = 100, batch_size: int = 1, seconds: int = 30, use_gdm: bool = False,
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
-                 inpainting_scope=None, preserve_known: bool = False) -> torch.Tensor:
+                 inpainting_scope=None, sampler: Optional[str] = None, preserve_known: bool = False) -> torch.Tensor:
         """``preserve_known`` (not in the reference): for music_inpaint / music_cont, pin the frames the mask keeps to the latents of
-        the given audio (the samplers' ``known`` / ``keep_mask``) instead of regenerating them from the conditioning alone"""
+        the given audio (the samplers' ``known`` / ``keep_mask``) instead of regenerating them from the conditioning alone.
+        ``sampler="dpmpp2m"`` (not in the reference; ``use_gdm=True`` only): DPM-Solver++(2M) over ``steps`` network evaluations,
+        ``GaussianDiffusion.dpm_sample``; None keeps the reference's samplers."""
+        if sampler not in (None, "dpmpp2m"):
+            raise ValueError(f"unknown sampler {sampler!r}: None or 'dpmpp2m'")
+        if sampler is not None and not use_gdm:
+            raise ValueError("sampler='dpmpp2m' needs use_gdm=True: there is no multistep solver for the variational diffusion model")
         if preserve_known and task == "text_guided":
             raise ValueError("preserve_known needs known audio: task 'music_inpaint' or 'music_cont'")
         torch.manual_seed(seed if seed != -1 else int(np.random.randint(0, 2 ** 32 - 1)))
@@ -149,11 +155,11 @@ class Jen1:
         start_s, end_s, causal = self._task_window(task, seconds, inpainting_scope, prefix)
         keep = self.get_mask(total, start_s, end_s, batch_size)                 # 1 = keep the known audio, 0 = generate
         return self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
-                            preserve_known=preserve_known)
+                            preserve_known=preserve_known, sampler=sampler)
 
     @torch.no_grad()
     def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
-                steps: int = 100, preserve_known: bool = False) -> torch.Tensor:
+                steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None) -> torch.Tensor:
         B = wav.shape[0]
         known = self.get_emb(wav.to(self.device)).to(self.device)               # [B, 128, T']
         keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
@@ -164,6 +170,8 @@ class Jen1:
         extra = {} if isinstance(diffusion, GaussianDiffusion) else {"step": steps}       # VDM.sample takes the step count itself (vdm.py:77)
         if preserve_known:               # (the concat context is the FIRST sample's, get_conditioning; the blend is per sample)
             extra.update(known=known, keep_mask=keep)
+        if sampler is not None:
+            extra["sampler"] = sampler
         z = diffusion.sample(model, tuple(known.shape), cond, causal=causal, init_data=known if seed_with_audio else None, **extra)
         # the reference hands the latents to its CPU decoder (generation.py:129-130); a decoder that lives on a device says so
         # (EncodecHIP.decoder_device) and gets them where they are
