@@ -474,6 +474,24 @@ int jen1_standardize_rows(const float* x, void* y, int rows, int C, int ldx, int
  * {const void* fixed; void* out; int32 C2; int32 0; int64 0}. */
 int jen1_kv_fixed_fill(const void* table_dev, int n_layers, const float* mask, int B, int rows, int dtype, void* stream);
 
+/*
+ * Sample-rate and channel conversion of float32 waveforms (csrc/audio.hip): what the reference gets from
+ * ``encodec.utils.convert_audio`` in front of the encoder (generation.py:95, dataset/dataloader.py:106) -- the channel rule, then
+ * torchaudio's default windowed-sinc resampler.  With o / n = sr / target_sr in lowest terms, per row and output channel:
+ *
+ *   y[j n + p] = sum_{t < W} taps[p][t] * xp[j o + first[p] + t],   xp[i] = mixed x[i - w], zero outside [0, L)
+ *
+ * x [rows][c_in][L], y [rows][c_out][L_out] with L_out = ceil(n L / o); c_in, c_out in {1, 2}: 2 -> 1 takes (l + r) * 0.5f before the
+ * filter, 1 -> 2 writes the filtered channel twice.  taps [n][W] float32 and first [n] int32 are DEVICE tables: the W taps of phase p
+ * that are not zero and where they start in the dense row of 2 w + o taps (jen1_amd/audio.py: resample_table; first[p] + W <= 2 w + o,
+ * enforced by clamping).  Sums run in float32 in ascending tap order, one thread per output: bit-reproducible.  No allocation and no
+ * synchronisation: capturable.  A frame's window (o + 2 w floats per staged channel) must fit 64 KiB of LDS.
+ */
+int jen1_resample(const float* x, float* y, const float* taps, const int32_t* first, int rows, int c_in, int c_out, int64_t L,
+                  int64_t L_out, int o, int n, int w, int W, void* stream);
+/* frames (o inputs -> n outputs each) one workgroup of jen1_resample owns: min(2048 / n, 4096 / o), at least 1 */
+int jen1_resample_tile_frames(int o, int n);
+
 const char* jen1_last_error(void);
 /* "gfx950" build tag + ABI version, for the loader's sanity check */
 const char* jen1_build_info(void);

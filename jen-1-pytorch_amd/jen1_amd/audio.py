@@ -1,0 +1,140 @@
+"""Sample-rate and channel conversion of waveforms on libjen1_hip.so (csrc/audio.hip: ``jen1_resample``).
+
+What the reference gets from ``encodec.utils.convert_audio(wav, sr, target_sr, target_channels)`` in front of the Encodec encoder
+(generation.py:95, dataset/dataloader.py:106): the channel rule (-> 1: mean over the channels; -> 2: mono duplicated, stereo kept;
+anything else is an error), then ``torchaudio.transforms.Resample(sr, target_sr)``, i.e. ``torchaudio.functional.resample`` with its
+defaults (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99), restated here from its formulas:
+
+    g = gcd(sr, target_sr);  o = sr // g;  n = target_sr // g
+    base = min(o, n) * 0.99;  w = ceil(6 * o / base);  K = 2 * w + o
+    t[p][k] = ((k - w) / o - p / n) * base, clamped to [-6, 6]                       p in [0, n), k in [0, K)
+    h[p][k] = sinc(t) * cos(pi t / 12)**2 * (base / o)                               float64, rounded to float32 once
+    xp[i] = x[i - w], zero outside [0, L);  y[j n + p] = sum_k h[p][k] * xp[j o + k];  len(y) = ceil(n L / o)
+
+``h[p]`` is exactly zero outside a short run of taps (the clamp parks the rest on the window's zero), so the kernel gets the compact
+form: ``taps [n, W]`` and ``first [n]`` with ``h[p][first[p] + t] = taps[p][t]`` and zeros elsewhere.  Neither torchaudio nor encodec is
+a dependency: parity with the packages themselves is not pinned.
+
+There is no fallback: whatever needs arithmetic runs on the HIP kernel of ``device``; only "nothing to do" returns without it.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Tuple
+
+import numpy as np
+import torch
+
+LOWPASS_FILTER_WIDTH = 6
+ROLLOFF = 0.99
+TABLE_MAX_BYTES = 256 * 1024     # cap on taps [n, W] float32: the table is meant to stay in L2; also keeps one frame's window within LDS
+_device_tables: Dict[Tuple[int, int, str], Tuple[int, int, int, int, torch.Tensor, torch.Tensor]] = {}
+
+
+def tile_frames(o: int, n: int) -> int:
+    """frames (o inputs -> n outputs each) one workgroup of the kernel owns for this rate pair: the library's own rule"""
+    from . import lib as L
+    return int(L.load().jen1_resample_tile_frames(int(o), int(n)))
+
+
+def resample_table(sr: int, target_sr: int):
+    """(o, n, w, taps float32 [n, W], first int32 [n]): the compact polyphase filter of ``sr -> target_sr``.  Host only (numpy, float64,
+    rounded to float32 once).  ``first[p]`` is the first non-zero tap of phase p in the dense row of K = 2 w + o taps, moved down where
+    the W-tap row would otherwise run past K (the taps in front are zeros of the dense row).  Equal rates give the identity filter
+    (o = n = 1, w = 0, one tap of 1.0)."""
+    sr, target_sr = int(sr), int(target_sr)
+    if sr <= 0 or target_sr <= 0:
+        raise ValueError(f"sample rates must be positive, not {sr} -> {target_sr}")
+    if sr == target_sr:
+        return 1, 1, 0, np.ones((1, 1), np.float32), np.zeros((1,), np.int32)
+    g = math.gcd(sr, target_sr)
+    o, n = sr // g, target_sr // g
+    base = min(o, n) * ROLLOFF
+    w = int(math.ceil(LOWPASS_FILTER_WIDTH * o / base))
+    K = 2 * w + o
+    # |t| < 6 only for the k within 6 o / base of the phase's centre w + p o / n; everywhere else the clamp puts the window at
+    # cos(pi / 2)**2 ~ 4e-33 and the product rounds to 0 in float32.  So only a band of Kb taps per phase is ever evaluated.
+    half = LOWPASS_FILTER_WIDTH * o / base
+    Kb = min(K, int(2 * half) + 6)
+    if n * (Kb - 6) * 4 > TABLE_MAX_BYTES:
+        raise ValueError(f"resample {sr} -> {target_sr}: the filter table ({n} phases of about {Kb - 5} taps) exceeds {TABLE_MAX_BYTES} bytes")
+    pi = np.arange(n, dtype=np.int64)
+    k0 = np.clip(w + (pi * o) // n - int(half) - 3, 0, K - Kb)          # first tap of the band of phase p
+    k = (k0[:, None] + np.arange(Kb, dtype=np.int64)[None, :]).astype(np.float64)
+    p = pi.astype(np.float64)[:, None]
+    t = np.clip(((k - w) / o - p / n) * base, -LOWPASS_FILTER_WIDTH, LOWPASS_FILTER_WIDTH)
+    tz = np.where(t == 0, 1.0, t)
+    sinc = np.where(t == 0, 1.0, np.sin(np.pi * tz) / (np.pi * tz))
+    h = (sinc * np.cos(np.pi * t / (2 * LOWPASS_FILTER_WIDTH)) ** 2 * (base / o)).astype(np.float32)
+    nz = h != 0
+    lo = np.argmax(nz, axis=1)
+    hi = Kb - np.argmax(nz[:, ::-1], axis=1)               # one past the last non-zero tap
+    W = int((hi - lo).max())
+    if n * W * 4 > TABLE_MAX_BYTES:
+        raise ValueError(f"resample {sr} -> {target_sr}: the filter table ({n} x {W} float32) exceeds {TABLE_MAX_BYTES} bytes")
+    lo = np.minimum(lo, Kb - W)
+    taps = np.take_along_axis(h, lo[:, None] + np.arange(W)[None, :], axis=1)
+    return o, n, w, np.ascontiguousarray(taps), (k0 + lo).astype(np.int32)
+
+
+def _tables(sr: int, target_sr: int, device: torch.device):
+    g = math.gcd(int(sr), int(target_sr))
+    key = (int(sr) // g, int(target_sr) // g, str(device))
+    hit = _device_tables.get(key)
+    if hit is None:
+        o, n, w, taps, first = resample_table(sr, target_sr)
+        hit = _device_tables[key] = (o, n, w, taps.shape[1], torch.from_numpy(taps).to(device), torch.from_numpy(first).to(device))
+    return hit
+
+
+def _run(wav: torch.Tensor, sr: int, target_sr: int, c_out: int, device) -> torch.Tensor:
+    """wav [..., C, L] float32 -> [..., c_out, ceil(n L / o)] on the kernel of ``device``, returned on wav's device"""
+    from . import lib as L
+    if wav.dtype != torch.float32:
+        raise TypeError(f"waveforms are float32, not {wav.dtype}")
+    src = wav.device
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise L.Jen1HipError(f"the resampler runs on a GPU, not on {dev}: there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    lib = L.load()
+    lead, c_in, n_in = tuple(wav.shape[:-2]), int(wav.shape[-2]), int(wav.shape[-1])
+    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    o, n, w, W, taps, first = _tables(sr, target_sr, dev)
+    n_out = -(-n * n_in // o)
+    x = wav.to(dev).contiguous()
+    y = torch.empty(lead + (c_out, n_out), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.jen1_resample(x.data_ptr(), y.data_ptr(), taps.data_ptr(), first.data_ptr(), rows, c_in, c_out, n_in, n_out,
+                                  o, n, w, W, torch.cuda.current_stream(dev).cuda_stream), "jen1_resample")
+    return y.to(src)
+
+
+def resample(wav: torch.Tensor, sr: int, target_sr: int, device="cuda") -> torch.Tensor:
+    """``torchaudio.functional.resample(wav, sr, target_sr)`` over the last axis of a float32 tensor with any leading axes.  Equal rates
+    return ``wav`` itself."""
+    if int(sr) <= 0 or int(target_sr) <= 0:
+        raise ValueError(f"sample rates must be positive, not {sr} -> {target_sr}")
+    if int(sr) == int(target_sr):
+        return wav
+    if wav.dim() < 1:
+        raise ValueError("resample needs a time axis")
+    return _run(wav.unsqueeze(-2), sr, target_sr, 1, device).squeeze(-2)
+
+
+def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: int, device="cuda") -> torch.Tensor:
+    """``encodec.utils.convert_audio``: wav [..., C, L] with C in {1, 2} -> [..., target_channels, ceil(n L / o)].  The channel rule is
+    applied in front of the filter, in the same launch.  Same rate and same channel count: ``wav`` itself, nothing is loaded."""
+    if wav.dim() < 2:
+        raise RuntimeError("convert_audio: audio must have at least a channel and a time axis")
+    c_in = int(wav.shape[-2])
+    if c_in not in (1, 2):
+        raise RuntimeError(f"convert_audio: audio must have one or two channels, not {c_in}")
+    if target_channels not in (1, 2):
+        raise RuntimeError(f"convert_audio: impossible to convert from {c_in} to {target_channels} channels")
+    if int(sr) <= 0 or int(target_sr) <= 0:
+        raise ValueError(f"sample rates must be positive, not {sr} -> {target_sr}")
+    if int(sr) == int(target_sr) and c_in == target_channels:
+        return wav
+    return _run(wav, sr, target_sr, int(target_channels), device)

@@ -1,8 +1,8 @@
 """``Jen1``: the top-level generate() surface of the reference around the HIP denoiser path.
 
 Host-side mirror of /root/reference/generation.py:16-192 -- same constructor arguments, ``get_model_and_diffusion``,
-``generate(prompt, seed, steps, batch_size, seconds, use_gdm, task, init_audio, init_audio_sr, inpainting_scope)``,
-``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
+``generate(prompt, seed, steps, batch_size, seconds, use_gdm, task, init_audio, init_audio_sr, inpainting_scope)`` (plus the keyword
+additions ``sampler``, ``preserve_known`` and ``output_sr``), ``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
 passed in instead (they are outside this build):
 
   * ``audio_encoder``: the object the reference gets from ``EncodecModel.encodec_model_48khz()``; used exactly as
@@ -10,10 +10,13 @@ passed in instead (they are outside this build):
     ``.decoder(emb)``  (generation.py:34, :95, :113, :130, :145-150);
   * ``conditioner``: the ``MultiConditioner`` of ``create_multi_conditioner`` (generation.py:29, :121-122),
     ``conditioner(batch_metadata, device) -> {"prompt": (emb [B,128,1024], mask [B,128])}``;
-  * ``convert_audio``: ``encodec.utils.convert_audio`` (generation.py:95), identity by default.
+  * ``convert_audio``: ``encodec.utils.convert_audio`` (generation.py:95).  Optional: the default is ``jen1_amd.audio.convert_audio``, the
+    same channel rule and windowed-sinc resampler as one HIP kernel on ``device`` (csrc/audio.hip).  Audio that already has the model's
+    sample rate and channel count is passed through untouched, without loading the library.
 
 Everything between them -- the masks, the conditioning dict, the 100-step DDIM loop over the UNet with the CFG pair,
-captured as one HIP graph per shape -- runs on libjen1_hip.so through ``GaussianDiffusion.sample``.
+captured as one HIP graph per shape -- runs on libjen1_hip.so through ``GaussianDiffusion.sample``; ``generate(output_sr=...)`` resamples
+the decoder's output with the kernel of ``convert_audio``.
 
 Differences, all deliberate and visible:
   * ``use_gdm=False`` (the reference default) selects ``VDM``, which cannot run in the reference (SURVEY.md Appendix
@@ -60,13 +63,22 @@ class Jen1:
         self.ckpt_path, self.device, self.sample_rate, self.weights = ckpt_path, device, sample_rate, weights
         self.conditioner, self.audio_encoder = conditioner, audio_encoder
         self.cross_attn_cond_ids, self.global_cond_ids, self.input_concat_ids = cross_attn_cond_ids, global_cond_ids, input_concat_ids
-        self.convert_audio = convert_audio or (lambda wav, sr, target_sr, target_channels: wav)
+        self.convert_audio = convert_audio or self._convert_audio
         self.model_config = dict(model_config or full_model_config())
         self.diffusion_config = diffusion_config or GDMConfig()
         self.vdm_config = vdm_config or VDMConfig()
         self.compute_dtype = compute_dtype
         self._model: Optional[UNetCFG1d] = None
         self.batch_size = 1
+
+    def _convert_audio(self, wav: torch.Tensor, sr: Optional[int], target_sr: int, target_channels: int) -> torch.Tensor:
+        """the default ``convert_audio``: jen1_amd.audio.convert_audio on ``self.device``; ``sr=None`` means the model's own rate.  Audio
+        that needs neither resampling nor a channel conversion is returned as it is and nothing is imported or loaded."""
+        sr = target_sr if sr is None else sr
+        if sr == target_sr and wav.shape[-2] == target_channels:
+            return wav
+        from . import audio
+        return audio.convert_audio(wav, sr, target_sr, target_channels, device=self.device)
 
     # generation.py:36-74
     def get_model_and_diffusion(self, steps: int, use_gdm: bool):
@@ -136,11 +148,16 @@ class Jen1:
 
     def generate(self, prompt, seed: int = -1, steps: int = 100, batch_size: int = 1, seconds: int = 30, use_gdm: bool = False,
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
-                 inpainting_scope=None, sampler: Optional[str] = None, preserve_known: bool = False) -> torch.Tensor:
+                 inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
+                 preserve_known: bool = False) -> torch.Tensor:
         """``preserve_known`` (not in the reference): for music_inpaint / music_cont, pin the frames the mask keeps to the latents of
         the given audio (the samplers' ``known`` / ``keep_mask``) instead of regenerating them from the conditioning alone.
         ``sampler="dpmpp2m"`` (not in the reference; ``use_gdm=True`` only): DPM-Solver++(2M) over ``steps`` network evaluations,
-        ``GaussianDiffusion.dpm_sample``; None keeps the reference's samplers."""
+        ``GaussianDiffusion.dpm_sample``; None keeps the reference's samplers.
+        ``output_sr`` (not in the reference): return the audio at this sample rate instead of the model's, resampled by
+        ``jen1_amd.audio.resample`` (the HIP kernel of ``convert_audio``); None or the model's own rate changes nothing."""
+        if output_sr is not None and int(output_sr) <= 0:
+            raise ValueError(f"output_sr must be a positive sample rate, not {output_sr!r}")
         if sampler not in (None, "dpmpp2m"):
             raise ValueError(f"unknown sampler {sampler!r}: None or 'dpmpp2m'")
         if sampler is not None and not use_gdm:
@@ -154,8 +171,13 @@ class Jen1:
         wav, placeholder, prefix = self._known_audio(task, init_audio, init_audio_sr, batch_size, total)
         start_s, end_s, causal = self._task_window(task, seconds, inpainting_scope, prefix)
         keep = self.get_mask(total, start_s, end_s, batch_size)                 # 1 = keep the known audio, 0 = generate
-        return self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
-                            preserve_known=preserve_known, sampler=sampler)
+        out = self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
+                           preserve_known=preserve_known, sampler=sampler)
+        if output_sr is not None and int(output_sr) != self.sample_rate:
+            from . import audio
+            # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
+            out = audio.resample(out, self.sample_rate, int(output_sr), device=out.device if out.device.type == "cuda" else self.device)
+        return out
 
     @torch.no_grad()
     def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
