@@ -216,7 +216,8 @@ int jen1_lstm_layer_multi(const float* gin, const void* whh, const void* skip, v
  * jen1_cfg_loss_forward / _backward: on the network's output rows net[(r B + b) T + t][0..C) (`dtype`): the CFG combine
  *   out_masked + (out - out_masked) s and the unbiased-std rescale (model.py:362-369), the elementwise l2 / l1 against tgt and the
  *   mean over (C, T) (gdm.py:268-272) -> loss_ps[b] (float32, zeroed by the call); backward: dnet = d loss / d net for
- *   upstream gradients gps[b] of the per-sample losses, both halves of the pair, padding columns zeroed. */
+ *   upstream gradients gps[b] of the per-sample losses, both halves of the pair, the padding columns C..ld zeroed (any ld >= C,
+ *   beyond 256 too).  2 <= C <= 256; the padding columns of net are never read. */
 int jen1_train_pack_input(const float* x0, const float* noise, const float* ca, const float* cb, const float* ctx, void* y, int B, int C, int Cc,
                           int T, int ld, int nrep, const float* ta, const float* tb, float* tgt, int dtype, void* stream);
 int jen1_train_context(const float* emb, const float* tok, const float* fixed, const uint8_t* drop, void* out, int B, int NL, int N, int F,

@@ -258,6 +258,10 @@ __global__ __launch_bounds__(256) void cfg_loss_bwd_kernel(const T* __restrict__
         if (nrep == 2) du[c] = (T)0.f;
       }
     }
+    for (int c = lane + 64 * CPL; c < ld; c += 64) {        // a pitch beyond the lanes' four slots: the rest of the padding
+      dc[c] = (T)0.f;
+      if (nrep == 2) du[c] = (T)0.f;
+    }
   }
 }
 

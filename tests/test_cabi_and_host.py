@@ -89,6 +89,21 @@ def test_training_ops_validate_arguments_without_a_gpu(lib):
     assert lib.jen1_softmax_forward(16, 16, 7, 2, 4, 4, 4, 0, L.F32, None) != 0     # rows not a multiple of Nq
     assert lib.jen1_colsum(None, None, 1, 1, 1, L.F32, None) != 0
     assert lib.jen1_convert_clear(16, 16, 6, L.F32, None) != 0 and b"multiple of 4" in lib.jen1_last_error()
+    # the two ends of a training pass (csrc/train_glue.hip): every refusal leaves its message; all other arguments are valid ones
+    def refused(rc, what):
+        return rc != 0 and what in lib.jen1_last_error()
+    p = 16                                                                    # any aligned non-NULL pointer: nothing is launched
+    for C_, ld in ((1, 8), (257, 264), (128, 120)):                           # C < 2, C > 256, ld < C
+        assert refused(lib.jen1_cfg_loss_forward(p, p, p, 2, C_, 4, ld, 2, 0.8, 1, 0.7, 0, L.F32, None), b"cfg_loss_forward: bad arguments")
+        assert refused(lib.jen1_cfg_loss_backward(p, p, p, p, 2, C_, 4, ld, 2, 0.8, 1, 0.7, 0, L.F32, None), b"cfg_loss_backward: bad arguments")
+    assert refused(lib.jen1_train_pack_input(p, p, p, p, p, p, 2, 5, 4, 6, 12, 1, None, None, None, L.F32, None), b"train_pack_input: bad arguments")   # ld % 8
+    assert refused(lib.jen1_train_pack_input(p, p, p, p, p, p, 2, 5, 4, 6, 16, 1, None, p, p, L.F32, None), b"train_pack_input: bad arguments")         # tgt, no ta
+    assert refused(lib.jen1_train_context(p, p, p, None, p, 2, 5, 6, 6, 2, L.F32, None), b"train_context: bad arguments")                               # F % 4
+    assert refused(lib.jen1_train_context(p, p, p, None, p, 2, 5, 7, 8, 2, L.F32, None), b"train_context: bad arguments")                               # N = NL + 2
+    assert refused(lib.jen1_train_context(p, None, p, None, p, 2, 5, 6, 8, 2, L.F32, None), b"train_context: bad arguments")                            # N = NL + 1, no tok
+    assert refused(lib.jen1_time_features_fwd(p, 0, p, p, 4, 16, 32, None), b"time_features_fwd: bad arguments")                                        # ld < 2 half + 1
+    assert refused(lib.jen1_sum_rows_inplace(p, 2, 12, L.F32, None), b"sum_rows_inplace: bad arguments")                                                # n % 8
+    assert refused(lib.jen1_sum_rows_inplace(p + 8, 2, 16, L.F32, None), b"sum_rows_inplace: bad arguments")                                            # 16-byte alignment
 
 
 def test_argument_validation_reports_errors_without_a_gpu(lib):
