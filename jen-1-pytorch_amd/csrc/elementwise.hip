@@ -909,74 +909,123 @@ extern "C" int jen1_linear_f32(const float* x, const float* w, const float* bias
   return 0;
 }
 
-template <bool DDIM>
-static int launch_cfg(const void* net, const float* x, const float* noise, const float* coef, float* x_out, float* eps_out,
-                      float* x0_out, const int32_t* step_idx, int B, int C, int T, int ld, int nrep, float scale, int scale_cfg, float phi,
-                      int objective, int clip_x0, int dtype, void* stream, int32_t* adv_step = nullptr, unsigned* adv_ticket = nullptr,
-                      void* rows = nullptr, float* parts = nullptr, int ld_rows = 0, const jen1_blend_args* bl = nullptr,
-                      float* hist = nullptr) {
-  JEN1_CHECK(net && x_out, "cfg step: null pointer");
-  JEN1_CHECK(nrep == 1 || nrep == 2, "cfg step: nrep must be 1 or 2");
-  JEN1_CHECK(C >= 2 && C <= 256 && ld >= C, "cfg step: C must be in [2, 256]");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid((T + 31) / 32, B);
-  const size_t lds = sizeof(float) * ((size_t)C * 33 + C / 8 + 1);
-  // rows of 8-channel vectors on 16-byte boundaries: the vector form (JEN1_CFG_STEP_SCALAR=1 keeps the general kernel: A-B switch)
-  static const bool scalar_only = getenv("JEN1_CFG_STEP_SCALAR") != nullptr;
-  const int esz = dtype == JEN1_F32 ? 4 : 2;
-  const bool vec = !scalar_only && C % 8 == 0 && ld % 8 == 0 && ((uintptr_t)net & 15) == 0 && ((size_t)ld * esz) % 16 == 0;
-  if (rows) {
-    JEN1_CHECK(vec && DDIM && parts, "cfg step + pack: needs the vector form (C % 8 == 0, 16-byte rows) and the partials buffer");
-    JEN1_CHECK(ld_rows >= C && ((size_t)ld_rows * esz) % 16 == 0 && ((uintptr_t)rows & 15) == 0 && ((uintptr_t)parts & 7) == 0,
-               "cfg step + pack: rows must be 16-byte aligned with ld_rows >= C");
+// ---- the sampler step's host side.  Every entry point below fills one StepCall by name, says which form it is and which optional
+// operands it cannot do without, and calls step_run: one validator, one choice of kernel, one launch.
+enum StepForm { STEP_COMBINE, STEP_PLAIN, STEP_ADV, STEP_PACK, STEP_TAIL };   // (ordered: each form requires what the one before it does)
+enum { STEP_HIST = 1, STEP_BLEND = 2 };
+struct StepCall {
+  TailArgs a;                      // what every form shares, and the tail form's sentinel table and zeroed area (a.z_rows: set at the launch);
+                                   // a.step_idx / a.ticket: the counter the launch advances (null: none)
+  float* eps_out; float* x0_out;   // extra outputs of the unpacked forms (may be null)
+  const int32_t* step_idx;         // the counter the launch reads (null: row 0 of the tables)
+  float* hist;                     // the multistep forms' previous x0
+  const jen1_blend_args* blend;    // the known-region blend's operands, or null
+  int dtype; void* stream;
+};
+
+// the known-region blend's own operands: all there, float32-aligned
+static int check_blend(const jen1_blend_args* bl, const char* who) {
+  JEN1_CHECK(bl, "%s: null blend arguments", who);
+  JEN1_CHECK(bl->known && bl->eps_k && bl->keep && bl->kb, "%s: null known / eps_k / keep / kb", who);
+  JEN1_CHECK((((uintptr_t)bl->known | (uintptr_t)bl->eps_k | (uintptr_t)bl->keep | (uintptr_t)bl->kb) & 3) == 0,
+             "%s: known / eps_k / keep / kb must be 4-byte aligned", who);
+  return 0;
+}
+
+// every refusal of the nine entry points (``who``: the entry point, for the message; ``vec``: the vector form can serve the call);
+// nothing is launched before this returns 0
+static int step_check(const StepCall& c, const char* who, StepForm form, int need, bool vec) {
+  static const char* const required[] = {"net / out", "net / x / coef / x_out", "net / x / coef / x_out / step_idx / ticket",
+                                         "net / x / coef / x_out / step_idx / ticket / rows / parts",
+                                         "net / x / coef / x_out / step_idx / ticket / rows / parts"};
+  const TailArgs& a = c.a;
+  JEN1_CHECK(a.net && a.x_out && (form < STEP_PLAIN || (a.x && a.coef)) && (form < STEP_ADV || (a.step_idx && a.ticket)) &&
+             (form < STEP_PACK || (a.rows && a.parts)), "%s: null %s", who, required[form]);
+  JEN1_CHECK(a.objective >= 0 && a.objective <= 2, "%s: bad objective", who);
+  JEN1_CHECK(a.nrep == 1 || a.nrep == 2, "%s: nrep must be 1 or 2", who);
+  JEN1_CHECK(c.dtype == JEN1_F32 || c.dtype == JEN1_BF16, "%s: bad dtype", who);
+  if (need & STEP_HIST) {
+    JEN1_CHECK(c.hist && ((uintptr_t)c.hist & 3) == 0, "%s: the history buffer must be there and 4-byte aligned", who);
+    JEN1_CHECK(c.hist != a.x && c.hist != a.x_out, "%s: the history buffer must not be the latents", who);
   }
-  if (hist) {
-    JEN1_CHECK(rows && (dtype == JEN1_F32 || dtype == JEN1_BF16), "cfg step + multistep: only with the packed rows, in f32 or bf16");
-    const jen1_blend_args none{nullptr, nullptr, nullptr, nullptr};
-#define JEN1_MS_LAUNCH(TY, BL)                                                                                                          \
-    do {                                                                                                                                \
-      auto kern = cfg_step_vec_ms_kernel<TY, BL>;                                                                                       \
-      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);                                                                                              \
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const TY*)net, x, hist, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, \
-                         objective, clip_x0, adv_step, adv_ticket, (TY*)rows, parts, ld_rows, bl ? *bl : none);                         \
-    } while (0)
-    if (dtype == JEN1_F32 && bl) JEN1_MS_LAUNCH(float, true);
-    else if (dtype == JEN1_F32) JEN1_MS_LAUNCH(float, false);
-    else if (bl) JEN1_MS_LAUNCH(bf16_t, true);
-    else JEN1_MS_LAUNCH(bf16_t, false);
-#undef JEN1_MS_LAUNCH
-  } else if (bl) {
-    JEN1_CHECK(rows && (dtype == JEN1_F32 || dtype == JEN1_BF16), "cfg step + blend: only with the packed rows, in f32 or bf16");
-    if (dtype == JEN1_F32) {
-      auto kern = cfg_step_vec_blend_kernel<float>;
-      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const float*)net, x, noise, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (float*)rows, parts, ld_rows, *bl);
-    } else {
-      auto kern = cfg_step_vec_blend_kernel<bf16_t>;
-      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16_t*)net, x, noise, coef, x_out, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (bf16_t*)rows, parts, ld_rows, *bl);
-    }
-  } else if (vec && dtype == JEN1_F32) {
-    auto kern = cfg_step_vec_kernel<float, DDIM>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const float*)net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (float*)rows, parts, ld_rows);
-  } else if (vec && dtype == JEN1_BF16) {
-    auto kern = cfg_step_vec_kernel<bf16_t, DDIM>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16_t*)net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket, (bf16_t*)rows, parts, ld_rows);
-  } else if (dtype == JEN1_F32) {
-    auto kern = cfg_step_kernel<float, DDIM>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const float*)net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket);
-  } else if (dtype == JEN1_BF16) {
-    auto kern = cfg_step_kernel<bf16_t, DDIM>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16_t*)net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, scale, scale_cfg, phi, objective, clip_x0, adv_step, adv_ticket);
-  } else {
-    return jen1_set_error("cfg step: bad dtype");
+  if (((need & STEP_BLEND) || c.blend) && check_blend(c.blend, who)) return 1;
+  if (form < STEP_PACK) {          // the general kernel serves what the vector form cannot
+    JEN1_CHECK(a.C >= 2 && a.C <= 256 && a.ld >= a.C, "%s: C must be in [2, 256] and ld >= C", who);
+    return 0;
   }
+  JEN1_CHECK(vec && a.C >= 8 && a.C <= 256 && a.ld >= a.C,
+             "%s: needs the vector form: a network output of 16-byte rows of C %% 8 == 0 channels (C <= 256)", who);
+  const int esz = c.dtype == JEN1_F32 ? 4 : 2;
+  JEN1_CHECK(a.ld_rows >= a.C && ((size_t)a.ld_rows * esz) % 16 == 0 && ((uintptr_t)a.rows & 15) == 0 && ((uintptr_t)a.parts & 7) == 0,
+             "%s: rows must be 16-byte aligned with ld_rows >= C", who);
+  if (form == STEP_TAIL) {
+    JEN1_CHECK(a.tab && a.n_tab >= 1 && a.n_tab <= 60000, "%s: bad sentinel table", who);
+    JEN1_CHECK(a.zero_ptr && (int64_t)a.zero_bytes > 0 && (a.zero_bytes & 15) == 0 && ((uintptr_t)a.zero_ptr & 15) == 0,
+               "%s: the zeroed area must be 16-byte aligned and sized", who);
+  }
+  return 0;
+}
+
+// (a template over the kernel itself, not its type: the function-local mask of JEN1_MAX_LDS_ONCE stays one per kernel)
+template <auto Kern, typename... Args>
+static int step_launch(dim3 grid, size_t lds, void* stream, Args... args) {
+  JEN1_MAX_LDS_ONCE(Kern, 160 * 1024);
+  hipLaunchKernelGGL(Kern, grid, dim3(256), lds, reinterpret_cast<hipStream_t>(stream), args...);
   JEN1_HIP(hipGetLastError());
   return 0;
+}
+
+// the kernel of a checked call: the form, then MS (c.hist) x BLEND (c.blend); ``vec``: the vector form serves it
+template <typename T, bool DDIM>
+static int step_dispatch(const StepCall& c, StepForm form, bool vec) {
+  const TailArgs& a = c.a;
+  const T* net = (const T*)a.net;
+  T* rows = (T*)a.rows;
+  const jen1_blend_args bl = c.blend ? *c.blend : jen1_blend_args{nullptr, nullptr, nullptr, nullptr};
+  const dim3 grid((a.Tn + 31) / 32, a.B);
+  const size_t lds = sizeof(float) * ((size_t)a.C * 33 + a.C / 8 + 1);
+  if constexpr (DDIM) {
+    if (form == STEP_TAIL) {
+      TailArgs t = a;
+      const int zrows = (int)((a.zero_bytes + (1 << 18) - 1) >> 18);
+      t.z_rows = zrows < 1 ? 1 : (zrows > 64 ? 64 : zrows);
+      const dim3 tgrid(grid.x * a.B + 8 * (a.n_tab + t.z_rows));
+      if (c.hist && c.blend) return step_launch<step_tail_ms_kernel<T, true>>(tgrid, lds, c.stream, t, c.hist, bl);
+      if (c.hist) return step_launch<step_tail_ms_kernel<T, false>>(tgrid, lds, c.stream, t, c.hist, bl);
+      if (c.blend) return step_launch<step_tail_blend_kernel<T>>(tgrid, lds, c.stream, t, bl);
+      return step_launch<step_tail_kernel<T>>(tgrid, lds, c.stream, t);
+    }
+    if (c.hist && c.blend)
+      return step_launch<cfg_step_vec_ms_kernel<T, true>>(grid, lds, c.stream, net, a.x, c.hist, a.coef, a.x_out, a.B, a.C, a.Tn, a.ld, a.nrep,
+                                                          a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket, rows, a.parts,
+                                                          a.ld_rows, bl);
+    if (c.hist)
+      return step_launch<cfg_step_vec_ms_kernel<T, false>>(grid, lds, c.stream, net, a.x, c.hist, a.coef, a.x_out, a.B, a.C, a.Tn, a.ld, a.nrep,
+                                                           a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket, rows, a.parts,
+                                                           a.ld_rows, bl);
+    if (c.blend)
+      return step_launch<cfg_step_vec_blend_kernel<T>>(grid, lds, c.stream, net, a.x, a.noise, a.coef, a.x_out, a.B, a.C, a.Tn, a.ld, a.nrep, a.scale,
+                                                       a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket, rows, a.parts, a.ld_rows,
+                                                       bl);
+  }
+  if (vec)
+    return step_launch<cfg_step_vec_kernel<T, DDIM>>(grid, lds, c.stream, net, a.x, a.noise, a.coef, a.x_out, c.eps_out, c.x0_out, c.step_idx, a.B,
+                                                     a.C, a.Tn, a.ld, a.nrep, a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx,
+                                                     a.ticket, rows, a.parts, a.ld_rows);
+  return step_launch<cfg_step_kernel<T, DDIM>>(grid, lds, c.stream, net, a.x, a.noise, a.coef, a.x_out, c.eps_out, c.x0_out, c.step_idx, a.B, a.C,
+                                               a.Tn, a.ld, a.nrep, a.scale, a.scale_cfg, a.phi, a.objective, a.clip_x0, a.step_idx, a.ticket);
+}
+
+static int step_run(const StepCall& c, const char* who, StepForm form, int need) {
+  // rows of 8-channel vectors on 16-byte boundaries: the vector form (JEN1_CFG_STEP_SCALAR=1 keeps the general kernel: A-B switch of the
+  // forms that have one, which the tail launch does not)
+  static const bool scalar_only = getenv("JEN1_CFG_STEP_SCALAR") != nullptr;
+  const int esz = c.dtype == JEN1_F32 ? 4 : 2;
+  const bool vec = (!scalar_only || form == STEP_TAIL) && c.a.C % 8 == 0 && c.a.ld % 8 == 0 && ((uintptr_t)c.a.net & 15) == 0 &&
+                   ((size_t)c.a.ld * esz) % 16 == 0;
+  if (const int rc = step_check(c, who, form, need, vec)) return rc;
+  if (form == STEP_COMBINE) return c.dtype == JEN1_F32 ? step_dispatch<float, false>(c, form, vec) : step_dispatch<bf16_t, false>(c, form, vec);
+  return c.dtype == JEN1_F32 ? step_dispatch<float, true>(c, form, vec) : step_dispatch<bf16_t, true>(c, form, vec);
 }
 
 __global__ void step_advance_kernel(int32_t* step_idx) { step_idx[0] += 1; }
@@ -992,166 +1041,108 @@ extern "C" int jen1_cfg_ddim_step(const void* net, const float* x, const float* 
                                   float* eps_out, float* x0_out, const int32_t* step_idx, int B, int C, int T, int ld,
                                   int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective,
                                   int clip_x0, int dtype, void* stream) {
-  JEN1_CHECK(x && coef, "cfg_ddim_step: null x/coef");
-  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step: bad objective");
-  return launch_cfg<true>(net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                          scale_phi, objective, clip_x0, dtype, stream);
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.eps_out = eps_out; c.x0_out = x0_out;
+  c.step_idx = step_idx; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep; c.a.scale = embedding_scale;
+  c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0; c.dtype = dtype; c.stream = stream;
+  return step_run(c, "cfg_ddim_step", STEP_PLAIN, 0);
 }
 
 extern "C" int jen1_cfg_ddim_step_adv(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
                                       float* eps_out, float* x0_out, int32_t* step_idx, uint32_t* ticket, int B, int C, int T, int ld,
                                       int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective,
                                       int clip_x0, int dtype, void* stream) {
-  JEN1_CHECK(x && coef && step_idx && ticket, "cfg_ddim_step_adv: null x / coef / step_idx / ticket");
-  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_adv: bad objective");
-  return launch_cfg<true>(net, x, noise, coef, x_out, eps_out, x0_out, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket);
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.eps_out = eps_out; c.x0_out = x0_out;
+  c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.dtype = dtype; c.stream = stream;
+  return step_run(c, "cfg_ddim_step_adv", STEP_ADV, 0);
 }
 
 extern "C" int jen1_cfg_ddim_step_pack(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
-                                       int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T,
-                                       int ld, int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective,
-                                       int clip_x0, int dtype, void* stream) {
-  JEN1_CHECK(x && coef && step_idx && ticket && rows && parts, "cfg_ddim_step_pack: null x / coef / step_idx / ticket / rows / parts");
-  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_pack: bad objective");
-  return launch_cfg<true>(net, x, noise, coef, x_out, nullptr, nullptr, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows);
-}
-
-// the known-region blend's own operands (the *_blend entry points): all there, float32-aligned
-static int check_blend(const jen1_blend_args* bl, const char* who) {
-  JEN1_CHECK(bl, "%s: null blend arguments", who);
-  JEN1_CHECK(bl->known && bl->eps_k && bl->keep && bl->kb, "%s: null known / eps_k / keep / kb", who);
-  JEN1_CHECK((((uintptr_t)bl->known | (uintptr_t)bl->eps_k | (uintptr_t)bl->keep | (uintptr_t)bl->kb) & 3) == 0,
-             "%s: known / eps_k / keep / kb must be 4-byte aligned", who);
-  return 0;
+                                       int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                                       int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                       void* stream) {
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.dtype = dtype; c.stream = stream;
+  return step_run(c, "cfg_ddim_step_pack", STEP_PACK, 0);
 }
 
 extern "C" int jen1_cfg_ddim_step_pack_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
-                                             int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C,
-                                             int T, int ld, int nrep, float embedding_scale, int scale_cfg, float scale_phi,
-                                             int objective, int clip_x0, int dtype, const jen1_blend_args* blend, void* stream) {
-  JEN1_CHECK(x && coef && step_idx && ticket && rows && parts, "cfg_ddim_step_pack_blend: null x / coef / step_idx / ticket / rows / parts");
-  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_pack_blend: bad objective");
-  if (check_blend(blend, "cfg_ddim_step_pack_blend")) return 1;
-  return launch_cfg<true>(net, x, noise, coef, x_out, nullptr, nullptr, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows, blend);
+                                             int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                                             int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                             const jen1_blend_args* blend, void* stream) {
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.dtype = dtype; c.blend = blend; c.stream = stream;
+  return step_run(c, "cfg_ddim_step_pack_blend", STEP_PACK, STEP_BLEND);
 }
 
-static int step_tail_impl(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
-                          uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
-                          float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
-                          const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
-                          const jen1_blend_args* bl, float* hist = nullptr);
-
-extern "C" int jen1_step_tail(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
-                             uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
-                             float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
-                             const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream) {
-  return step_tail_impl(net, x, noise, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, nullptr);
+extern "C" int jen1_step_tail(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
+                              int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                              int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                              const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream) {
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.a.tab = reinterpret_cast<const TailPoisonEntry*>(poison_table); c.a.n_tab = n_rows; c.a.sync = sync; c.a.zero_ptr = zero_ptr;
+  c.a.zero_bytes = (unsigned long long)zero_bytes; c.dtype = dtype; c.stream = stream;
+  return step_run(c, "step_tail", STEP_TAIL, 0);
 }
 
-extern "C" int jen1_step_tail_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
-                                    uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
-                                    float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+extern "C" int jen1_step_tail_blend(const void* net, const float* x, const float* noise, const float* coef, float* x_out,
+                                    int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                                    int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                                     const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
                                     const jen1_blend_args* blend, void* stream) {
-  if (check_blend(blend, "step_tail_blend")) return 1;
-  return step_tail_impl(net, x, noise, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, blend);
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.a.noise = noise; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.a.tab = reinterpret_cast<const TailPoisonEntry*>(poison_table); c.a.n_tab = n_rows; c.a.sync = sync; c.a.zero_ptr = zero_ptr;
+  c.a.zero_bytes = (unsigned long long)zero_bytes; c.dtype = dtype; c.blend = blend; c.stream = stream;
+  return step_run(c, "step_tail_blend", STEP_TAIL, STEP_BLEND);
 }
 
 // the multistep forms: ``hist`` (the previous step's x0, read and rewritten) stands where the plain entry points take the noise table,
 // which this update does not have; ``blend`` may be null (no known-region blend)
 extern "C" int jen1_cfg_ddim_step_pack_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out,
-                                          int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C,
-                                          int T, int ld, int nrep, float embedding_scale, int scale_cfg, float scale_phi,
-                                          int objective, int clip_x0, int dtype, const jen1_blend_args* blend, void* stream) {
-  JEN1_CHECK(x && coef && step_idx && ticket && rows && parts, "cfg_ddim_step_pack_ms: null x / coef / step_idx / ticket / rows / parts");
-  JEN1_CHECK(hist && ((uintptr_t)hist & 3) == 0, "cfg_ddim_step_pack_ms: the history buffer must be there and 4-byte aligned");
-  JEN1_CHECK(hist != x && hist != x_out, "cfg_ddim_step_pack_ms: the history buffer must not be the latents");
-  JEN1_CHECK(objective >= 0 && objective <= 2, "cfg_ddim_step_pack_ms: bad objective");
-  if (blend && check_blend(blend, "cfg_ddim_step_pack_ms")) return 1;
-  return launch_cfg<true>(net, x, nullptr, coef, x_out, nullptr, nullptr, step_idx, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                          scale_phi, objective, clip_x0, dtype, stream, step_idx, ticket, rows, parts, ld_rows, blend, hist);
+                                          int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                                          int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+                                          const jen1_blend_args* blend, void* stream) {
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.hist = hist; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.dtype = dtype; c.blend = blend; c.stream = stream;
+  return step_run(c, "cfg_ddim_step_pack_ms", STEP_PACK, STEP_HIST);
 }
 
-extern "C" int jen1_step_tail_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out, int32_t* step_idx,
-                                 uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
-                                 float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
+extern "C" int jen1_step_tail_ms(const void* net, const float* x, float* hist, const float* coef, float* x_out,
+                                 int32_t* step_idx, uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld,
+                                 int nrep, float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
                                  const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes,
                                  const jen1_blend_args* blend, void* stream) {
-  JEN1_CHECK(hist && ((uintptr_t)hist & 3) == 0, "step_tail_ms: the history buffer must be there and 4-byte aligned");
-  JEN1_CHECK(hist != x && hist != x_out, "step_tail_ms: the history buffer must not be the latents");
-  if (blend && check_blend(blend, "step_tail_ms")) return 1;
-  return step_tail_impl(net, x, nullptr, coef, x_out, step_idx, ticket, rows, parts, ld_rows, B, C, T, ld, nrep, embedding_scale, scale_cfg,
-                        scale_phi, objective, clip_x0, dtype, poison_table, n_rows, sync, zero_ptr, zero_bytes, stream, blend, hist);
-}
-
-static int step_tail_impl(const void* net, const float* x, const float* noise, const float* coef, float* x_out, int32_t* step_idx,
-                          uint32_t* ticket, void* rows, float* parts, int ld_rows, int B, int C, int T, int ld, int nrep,
-                          float embedding_scale, int scale_cfg, float scale_phi, int objective, int clip_x0, int dtype,
-                          const void* poison_table, int n_rows, uint32_t* sync, void* zero_ptr, int64_t zero_bytes, void* stream,
-                          const jen1_blend_args* bl, float* hist) {
-  JEN1_CHECK(net && x && coef && x_out && step_idx && ticket && rows && parts, "step_tail: null net / x / coef / x_out / step_idx / ticket / rows / parts");
-  JEN1_CHECK(objective >= 0 && objective <= 2 && (nrep == 1 || nrep == 2), "step_tail: bad objective / nrep");
-  JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "step_tail: bad dtype");
-  const int esz = dtype == JEN1_F32 ? 4 : 2;
-  JEN1_CHECK(C >= 8 && C <= 256 && C % 8 == 0 && ld >= C && ld % 8 == 0 && ((uintptr_t)net & 15) == 0 && ((size_t)ld * esz) % 16 == 0,
-             "step_tail: the network output must be 16-byte rows of C %% 8 == 0 channels (C <= 256)");
-  JEN1_CHECK(ld_rows >= C && ((size_t)ld_rows * esz) % 16 == 0 && ((uintptr_t)rows & 15) == 0 && ((uintptr_t)parts & 7) == 0,
-             "step_tail: rows must be 16-byte aligned with ld_rows >= C");
-  JEN1_CHECK(poison_table && n_rows >= 1 && n_rows <= 60000, "step_tail: bad sentinel table");
-  JEN1_CHECK(zero_ptr && zero_bytes > 0 && (zero_bytes & 15) == 0 && ((uintptr_t)zero_ptr & 15) == 0, "step_tail: the zeroed area must be 16-byte aligned and sized");
-  int zrows = (int)((zero_bytes + (1 << 18) - 1) >> 18);
-  zrows = zrows < 1 ? 1 : (zrows > 64 ? 64 : zrows);
-  TailArgs a;
-  a.net = net; a.x = x; a.noise = noise; a.coef = coef; a.x_out = x_out; a.step_idx = step_idx; a.ticket = ticket;
-  a.rows = rows; a.parts = parts; a.ld_rows = ld_rows; a.B = B; a.C = C; a.Tn = T; a.ld = ld; a.nrep = nrep;
-  a.scale = embedding_scale; a.scale_cfg = scale_cfg; a.phi = scale_phi; a.objective = objective; a.clip_x0 = clip_x0;
-  a.tab = reinterpret_cast<const TailPoisonEntry*>(poison_table); a.n_tab = n_rows; a.z_rows = zrows; a.sync = sync;
-  a.zero_ptr = zero_ptr; a.zero_bytes = (unsigned long long)zero_bytes;
-  const int nstep = ((T + 31) / 32) * B;
-  const dim3 grid(nstep + 8 * (n_rows + zrows));
-  const size_t lds = sizeof(float) * ((size_t)C * 33 + C / 8 + 1);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (hist) {
-    const jen1_blend_args none{nullptr, nullptr, nullptr, nullptr};
-#define JEN1_MS_LAUNCH(TY, BL)                                                      \
-    do {                                                                            \
-      auto kern = step_tail_ms_kernel<TY, BL>;                                      \
-      JEN1_MAX_LDS_ONCE(kern, 160 * 1024);                                          \
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, hist, bl ? *bl : none);  \
-    } while (0)
-    if (dtype == JEN1_F32 && bl) JEN1_MS_LAUNCH(float, true);
-    else if (dtype == JEN1_F32) JEN1_MS_LAUNCH(float, false);
-    else if (bl) JEN1_MS_LAUNCH(bf16_t, true);
-    else JEN1_MS_LAUNCH(bf16_t, false);
-#undef JEN1_MS_LAUNCH
-  } else if (bl && dtype == JEN1_F32) {
-    auto kern = step_tail_blend_kernel<float>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, *bl);
-  } else if (bl) {
-    auto kern = step_tail_blend_kernel<bf16_t>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, *bl);
-  } else if (dtype == JEN1_F32) {
-    auto kern = step_tail_kernel<float>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  } else {
-    auto kern = step_tail_kernel<bf16_t>;
-    JEN1_MAX_LDS_ONCE(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  }
-  JEN1_HIP(hipGetLastError());
-  return 0;
+  StepCall c{};
+  c.a.net = net; c.a.x = x; c.hist = hist; c.a.coef = coef; c.a.x_out = x_out; c.step_idx = c.a.step_idx = step_idx; c.a.ticket = ticket;
+  c.a.rows = rows; c.a.parts = parts; c.a.ld_rows = ld_rows; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = nrep;
+  c.a.scale = embedding_scale; c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.a.objective = objective; c.a.clip_x0 = clip_x0;
+  c.a.tab = reinterpret_cast<const TailPoisonEntry*>(poison_table); c.a.n_tab = n_rows; c.a.sync = sync; c.a.zero_ptr = zero_ptr;
+  c.a.zero_bytes = (unsigned long long)zero_bytes; c.dtype = dtype; c.blend = blend; c.stream = stream;
+  return step_run(c, "step_tail_ms", STEP_TAIL, STEP_HIST);
 }
 
 extern "C" int jen1_cfg_combine(const void* net, float* out, int B, int C, int T, int ld, float embedding_scale,
                                 int scale_cfg, float scale_phi, int dtype, void* stream) {
-  return launch_cfg<false>(net, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, B, C, T, ld, 2, embedding_scale,
-                           scale_cfg, scale_phi, 0, 0, dtype, stream);
+  StepCall c{};
+  c.a.net = net; c.a.x_out = out; c.a.B = B; c.a.C = C; c.a.Tn = T; c.a.ld = ld; c.a.nrep = 2; c.a.scale = embedding_scale;
+  c.a.scale_cfg = scale_cfg; c.a.phi = scale_phi; c.dtype = dtype; c.stream = stream;
+  return step_run(c, "cfg_combine", STEP_COMBINE, 0);
 }

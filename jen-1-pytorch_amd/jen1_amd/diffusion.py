@@ -14,8 +14,9 @@ from __future__ import annotations
 import math
 import os
 from ctypes import byref as C_byref
+from dataclasses import dataclass
 from functools import partial
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -541,6 +542,24 @@ def _check_model_errors(model) -> None:
         chk()
 
 
+@dataclass
+class StepPart:
+    """one sub-batch of a ``DDIMStepper``: its rows of the batch, its plan, and the buffers whose addresses its captured step holds"""
+    sl: slice
+    plan: object
+    noise: torch.Tensor                               # its noise table [S, nb, C, T] (``noise_all`` itself while the batch is in one part)
+    hist: Optional[torch.Tensor]                      # dpmpp: the previous step's x0 [nb, C, T]
+    blend: Optional[tuple]                            # blend=True: (known [nb, C, T], eps_k [nb, C, T], keep [nb, 1, T], BlendArgs)
+    ticket: torch.Tensor                              # the word on which the step kernel's blocks find the last one (it advances the counter)
+    fused: bool                                       # the step kernel writes the next step's network input
+    tail: bool                                        # ... and sets its sentinels and zeroes its statistics arena
+    run: Optional[Callable] = None                    # run(stream): enqueue one step of this part
+
+    def __iter__(self):
+        """unpacks as the ``(slice, plan, run, noise table)`` tuple this record replaced"""
+        return iter((self.sl, self.plan, self.run, self.noise))
+
+
 class DDIMStepper:
     """One fused denoiser step = denoiser plan + ``jen1_cfg_ddim_step`` (CFG combine, std rescale,
     x0/eps prediction, DDIM update) + ``jen1_step_advance``, captured once as a hipGraph.
@@ -602,21 +621,18 @@ class DDIMStepper:
             self.kb = kb.to(dev, torch.float32).contiguous()
             assert tuple(self.kb.shape) == (S, 2)
             self._kb_host = self.kb.tolist()
-            self._blend_bufs = []                     # per part: (known [nb, C, T], eps_k [nb, C, T], keep [nb, 1, T], BlendArgs)
         # per-step noise table [S][B][C][T] (614 MB at B=8, T=1500: nothing against 288 GB of HBM); VDM's update draws none
         self.noise_all = torch.zeros(((S,) + tuple(shape)) if not noiseless else (1, 1, 1, 1), dtype=torch.float32, device=dev)
-        self.hist = []                                # dpmpp, per part: the previous step's x0 [nb, C, T]
         self._noise_fresh = False
         self._cond = conditioning                     # keep the conditioning tensors alive
-        Co = model.spec.out_channels
-        lib = self.lib
         self.plan_slot = plan_slot
         self._token = object()                        # (a plan's ``_stepper_token``: the stepper whose tables and conditioning it holds)
         self.parts = []
         b0 = 0
         used = {}
         s0 = torch.cuda.current_stream(dev).cuda_stream
-        for i, nb in enumerate(sizes):
+        zeros = partial(torch.zeros, dtype=torch.float32, device=dev)
+        for nb in sizes:
             slot = used.get(nb, 0)
             used[nb] = slot + 1
             # plan_slot: independent samplers of the same shape that run concurrently (serving) own separate buffers
@@ -624,22 +640,6 @@ class DDIMStepper:
             sl = slice(b0, b0 + nb)
             self._bind(plan, sl, conditioning)
             self._fill_times(plan, s0)                # FiLM / time-token K/V tables for all S timesteps
-            net = plan.net_out
-            # noise table slice of this sub-batch: row stride is the full batch, so give each part its own
-            # contiguous table when the batch is split
-            ntab = self.noise_all if (len(sizes) == 1 or noiseless) else torch.zeros((S, nb, C, T), dtype=torch.float32, device=dev)
-            if mode == "dpmpp":
-                self.hist.append(torch.zeros((nb, C, T), dtype=torch.float32, device=dev))
-            # (the third argument: the noise table, or the history buffer of the multistep entry points)
-            args = (net.t.data_ptr(), plan.x_in.data_ptr(),
-                    self.hist[-1].data_ptr() if mode == "dpmpp" else (ntab.data_ptr() if mode != "vdm" else None), self.coef.data_ptr(),
-                    plan.x_in.data_ptr(), None, None, plan.step_idx.data_ptr(), nb, Co, T, net.ld, self.nrep,
-                    float(gd.embedding_scale), 1 if (cfg and gd.scale_cfg) else 0, 0.7, _OBJ[getattr(gd, "objective", "v")],
-                    0 if mode == "vdm" else 1, eng.dt)
-            sp = plan.step_idx.data_ptr()
-            # the step counter advances inside the CFG / DDIM kernel (its last block; jen1_cfg_ddim_step_adv): one launch fewer per step
-            ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
-            adv_args = args[:7] + (sp, ticket.data_ptr()) + args[8:]
             # fused step (JEN1_STEP_PACK, default on): the step kernel also writes the next step's network input -- rows in the compute
             # dtype + the statistics partials -- so a replayed step has no pack launch at its head; the plan's own pack runs once per
             # trajectory (``_pack_dirty``: after reset / rebind, before the first step)
@@ -649,45 +649,24 @@ class DDIMStepper:
                                    "or environment (JEN1_STEP_PACK=0 / JEN1_CFG_STEP_SCALAR) rules out; use GaussianDiffusion.dpm_sample")
             # ... and (JEN1_STEP_TAIL, default on) the same launch sets the next step's sentinels and zeroes its statistics arena, the
             # job of the node at the head of a step: a replayed step is the three persistent launches + jen1_step_tail + the partials' sum
+            # (per sub-batch: a plan without persistent launches keeps its sentinel-free head)
             tail = fused and os.environ.get("JEN1_STEP_TAIL", "1") == "1" and _tail_eligible(plan.poison_args)
-            bl = None
+            blend = None
             if self.blend:
-                kn, ek = (torch.zeros((nb, C, T), dtype=torch.float32, device=dev) for _ in range(2))
-                kp = torch.zeros((nb, 1, T), dtype=torch.float32, device=dev)
-                bl = L.BlendArgs(kn.data_ptr(), ek.data_ptr(), kp.data_ptr(), self.kb.data_ptr())
-                self._blend_bufs.append((kn, ek, kp, bl))
-            if fused:
-                rows_ptr, parts_ptr, ld_rows = plan.pack_rows
-                pk_args = args[:5] + (sp, ticket.data_ptr(), rows_ptr, parts_ptr, ld_rows) + args[8:]
-                tl_args = pk_args + plan.poison_args if tail else None
-                if mode == "dpmpp":
-                    tail_fn, pack_fn, extra = lib.jen1_step_tail_ms, lib.jen1_cfg_ddim_step_pack_ms, (None if bl is None else C_byref(bl),)
-                else:
-                    tail_fn, pack_fn, extra = ((lib.jen1_step_tail, lib.jen1_cfg_ddim_step_pack, ()) if bl is None else
-                                               (lib.jen1_step_tail_blend, lib.jen1_cfg_ddim_step_pack_blend, (C_byref(bl),)))
-
-                def run(s, plan=plan, pk_args=pk_args, tl_args=tl_args, ticket=ticket, tail_fn=tail_fn, pack_fn=pack_fn, extra=extra):
-                    if tl_args is not None:
-                        plan.run(s, pack=False, poison=False)
-                        L.check(tail_fn(*tl_args, *extra, s), "jen1_step_tail")
-                    else:
-                        plan.run(s, pack=False)
-                        L.check(pack_fn(*pk_args, *extra, s), "jen1_cfg_ddim_step_pack")
-                    plan.pack_stats_op(s)
-            else:
-                def run(s, plan=plan, adv_args=adv_args, ticket=ticket):
-                    plan.run(s)
-                    L.check(lib.jen1_cfg_ddim_step_adv(*adv_args, s), "jen1_cfg_ddim_step_adv")
-            # (per sub-batch: a plan without persistent launches keeps its sentinel-free head; the stepper-level flags say "every part")
-            if not hasattr(self, "_part_fused"):
-                self._part_fused = {}
-            self._part_fused[id(plan)] = (fused, tail)
-            self.fused_pack = getattr(self, "fused_pack", True) and fused
-            self.fused_tail = getattr(self, "fused_tail", True) and tail
-
-            self.parts.append((sl, plan, run, ntab))
+                kn, ek, kp = zeros((nb, C, T)), zeros((nb, C, T)), zeros((nb, 1, T))
+                blend = (kn, ek, kp, L.BlendArgs(kn.data_ptr(), ek.data_ptr(), kp.data_ptr(), self.kb.data_ptr()))
+            # noise table slice of this sub-batch: row stride is the full batch, so give each part its own
+            # contiguous table when the batch is split
+            part = StepPart(sl=sl, plan=plan, noise=self.noise_all if (len(sizes) == 1 or noiseless) else zeros((S, nb, C, T)),
+                            hist=zeros((nb, C, T)) if mode == "dpmpp" else None, blend=blend,
+                            ticket=torch.zeros((1,), dtype=torch.int32, device=dev), fused=fused, tail=tail)
+            part.run = self._runner(part)
+            self.parts.append(part)
             b0 += nb
-        self.plan = self.parts[0][1]                  # (first sub-plan; used by the bench's per-launch roofline)
+        self.plan = self.parts[0].plan                # (first sub-plan; used by the bench's per-launch roofline)
+        self.hist = [p.hist for p in self.parts if p.hist is not None]
+        self.fused_pack = all(p.fused for p in self.parts)       # (the stepper-level flags say "every part")
+        self.fused_tail = all(p.tail for p in self.parts)
         self.streams = [torch.cuda.Stream(dev) for _ in self.parts] if len(self.parts) > 1 else []
         self._next = 0
         self._pack_dirty = True
@@ -703,9 +682,42 @@ class DDIMStepper:
             self._capture()
             self.reset(saved)                         # the warm-up advanced x and the step counter: restore
 
+    def _step_call(self, p: StepPart):
+        """the step launch of one part: the entry point and its arguments up to the stream, each by name and in the order
+        include/jen1_hip.h declares them"""
+        gd, plan, mode = self.gd, p.plan, self.mode
+        net, x, coef = plan.net_out.t.data_ptr(), plan.x_in.data_ptr(), self.coef.data_ptr()        # (x: updated in place)
+        step_idx, ticket = plan.step_idx.data_ptr(), p.ticket.data_ptr()
+        # the third operand: the noise table (VDM's update draws none), or the history buffer of the multistep entry points
+        third = p.hist.data_ptr() if mode == "dpmpp" else (None if mode == "vdm" else p.noise.data_ptr())
+        shape = (p.sl.stop - p.sl.start, self.model.spec.out_channels, self.shape[2], plan.net_out.ld, self.nrep, float(gd.embedding_scale),
+                 1 if (self.nrep == 2 and gd.scale_cfg) else 0, 0.7, _OBJ[getattr(gd, "objective", "v")], 0 if mode == "vdm" else 1, self.eng.dt)
+        if not p.fused:    # the step counter advances inside the CFG / DDIM kernel (its last block): no jen1_step_advance launch
+            return self.lib.jen1_cfg_ddim_step_adv, (net, x, third, coef, x, None, None, step_idx, ticket) + shape
+        rows, parts, ld_rows = plan.pack_rows
+        args = (net, x, third, coef, x, step_idx, ticket, rows, parts, ld_rows) + shape
+        name = "jen1_cfg_ddim_step_pack"
+        if p.tail:
+            name, args = "jen1_step_tail", args + plan.poison_args       # (sentinel table, its rows, sync word, zeroed area, its bytes)
+        if mode == "dpmpp":
+            name, args = name + "_ms", args + (None if p.blend is None else C_byref(p.blend[3]),)
+        elif p.blend is not None:
+            name, args = name + "_blend", args + (C_byref(p.blend[3]),)
+        return getattr(self.lib, name), args
+
+    def _runner(self, p: StepPart):
+        fn, args = self._step_call(p)
+
+        def run(s):
+            p.plan.run(s, pack=not p.fused, poison=not p.tail)
+            L.check(fn(*args, s), fn.__name__)
+            if p.fused:
+                p.plan.pack_stats_op(s)
+        return run
+
     def _modes(self):
         """scheduling form of every persistent launch of the step (static / tickets): recorded into a captured graph"""
-        return tuple(bool(plan.progs[0].exclusive) for _, plan, _, _ in self.parts if getattr(plan, "progs", None))
+        return tuple(bool(p.plan.progs[0].exclusive) for p in self.parts if getattr(p.plan, "progs", None))
 
     def _capture(self):
         """warm-up + capture of one step (called again when the scheduling form of a persistent launch changed hands)"""
@@ -720,10 +732,10 @@ class DDIMStepper:
         self.graph, self.graphs = None, None
         if self.streams and os.environ.get("JEN1_GRAPH_PER_STREAM", "1") == "1":
             self.graphs = []
-            for _, _, run, _ in self.parts:
+            for p in self.parts:
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    run(torch.cuda.current_stream(dev).cuda_stream)
+                    p.run(torch.cuda.current_stream(dev).cuda_stream)
                 self.graphs.append(g)
         else:
             g = torch.cuda.CUDAGraph()
@@ -736,16 +748,16 @@ class DDIMStepper:
         """the static schedule of the persistent launch belongs to the program used most recently (engine.DeepProgram.claim_static):
         ask for it at the start of a trajectory, and re-capture when the form recorded in the graph is no longer the program's"""
         if claim:
-            for _, plan, _, _ in self.parts:
-                if getattr(plan, "progs", None):
-                    plan.progs[0].claim_static()
+            for p in self.parts:
+                if getattr(p.plan, "progs", None):
+                    p.plan.progs[0].claim_static()
         if self.use_graph and self._cap_modes is not None and self._cap_modes != self._modes():
             saved, nxt = self.x.clone(), self._next
             saved_hist = [h.clone() for h in self.hist]
             self._set_step(0)                      # (the warm-up pass reads the tables of the current step: keep it inside them)
             self._capture()
-            for sl, plan, _, _ in self.parts:
-                plan.x_in.copy_(saved[sl])
+            for p in self.parts:
+                p.plan.x_in.copy_(saved[p.sl])
             for h, old in zip(self.hist, saved_hist):   # (the warm-up pass left its own x0 in the history)
                 h.copy_(old)
             self._pack_dirty = True
@@ -769,10 +781,10 @@ class DDIMStepper:
     def _claim(self) -> None:
         """take over every plan that another stepper of the same shape has filled since this one last did: its conditioning and
         schedule tables (the plans are shared, ``Engine.plan``), then a re-pack of the network input"""
-        for sl, plan, _, _ in self.parts:
-            if getattr(plan, "_stepper_token", None) is not self._token:
-                self._bind(plan, sl, self._cond)
-                self._fill_times(plan)
+        for p in self.parts:
+            if getattr(p.plan, "_stepper_token", None) is not self._token:
+                self._bind(p.plan, p.sl, self._cond)
+                self._fill_times(p.plan)
                 self._pack_dirty = True
 
     def rebind(self, conditioning) -> None:
@@ -780,18 +792,17 @@ class DDIMStepper:
         the schedule tables and the captured graph stay (they depend on the weights and the shape only) unless another stepper has
         filled the plan since"""
         self._cond = conditioning
-        for sl, plan, _, _ in self.parts:
-            self._bind(plan, sl, conditioning)
-            if getattr(plan, "_stepper_token", None) is not self._token:
-                self._fill_times(plan)
+        for p in self.parts:
+            self._bind(p.plan, p.sl, conditioning)
+            if getattr(p.plan, "_stepper_token", None) is not self._token:
+                self._fill_times(p.plan)
         self._pack_dirty = True                    # (the concat context is part of the packed rows)
 
     @property
     def launches_per_step(self) -> int:
         """kernel launches of one replayed step (first sub-batch): the plan's, minus what the fused step kernel took over, plus that kernel
         and the sum of its statistics partials"""
-        plan = self.plan
-        fused, tail = self._part_fused[id(plan)]
+        plan, fused, tail = self.plan, self.parts[0].fused, self.parts[0].tail
         skip = (("pack",) if fused else ()) + (("deep_poison",) if tail else ())
         n = sum(1 for op in plan.ops if getattr(op, "kind", "") not in skip) + (0 if plan.table_mode else len(plan.time_ops))
         return n + 1 + (1 if fused else 0)
@@ -806,8 +817,8 @@ class DDIMStepper:
         network input from them"""
         x = x.to(self.gd.device, torch.float32)
         assert tuple(x.shape) == self.shape, f"set_x: latents of shape {tuple(x.shape)}, this stepper samples {self.shape}"
-        for sl, plan, _, _ in self.parts:
-            plan.x_in.copy_(x[sl])
+        for p in self.parts:
+            p.plan.x_in.copy_(x[p.sl])
         self._pack_dirty = True
 
     def set_known(self, known: torch.Tensor, keep: torch.Tensor, noise: Optional[torch.Tensor] = None) -> None:
@@ -820,36 +831,37 @@ class DDIMStepper:
         known, keep, noise = check_known(self.shape, known, keep, noise, self.gd.device)
         if known is None:
             raise ValueError("set_known needs the known latents and the keep mask")
-        for (sl, _, _, _), (kn, ek, kp, _) in zip(self.parts, self._blend_bufs):
-            kn.copy_(known[sl])
-            kp.copy_(keep[sl])
+        for p in self.parts:
+            kn, ek, kp, _ = p.blend
+            kn.copy_(known[p.sl])
+            kp.copy_(keep[p.sl])
             if noise is None:
                 ek.normal_()
             else:
-                ek.copy_(noise[sl])
+                ek.copy_(noise[p.sl])
         self._known_set = True
 
     def _blend_parts(self, p: float, q: float, only_unfused: bool) -> None:
         """the blend in torch, on the plans' latents: the start of a trajectory (every part), and after a step of a part whose step
         kernel has no blend form (the scalar / unpacked kernels); the edit goes through the dirty mechanism like any other"""
-        for (_, plan, _, _), (kn, ek, kp, _) in zip(self.parts, self._blend_bufs):
-            if only_unfused and self._part_fused[id(plan)][0]:
+        for part in self.parts:
+            if only_unfused and part.fused:
                 continue
-            plan.x_in.copy_(blend_known(plan.x_in, kn, kp, ek, p, q))
+            kn, ek, kp, _ = part.blend
+            part.plan.x_in.copy_(blend_known(part.plan.x_in, kn, kp, ek, p, q))
             self._pack_dirty = True
 
     def _versions(self):
-        return tuple((plan.x_in._version, plan.ctx_in._version) for _, plan, _, _ in self.parts)
+        return tuple((p.plan.x_in._version, p.plan.ctx_in._version) for p in self.parts)
 
     def _pack_if_dirty(self):
         if self._pack_dirty:
             s = torch.cuda.current_stream(self.gd.device).cuda_stream
-            for _, plan, _, _ in self.parts:
-                fused, tail = self._part_fused[id(plan)]
-                if fused:
-                    plan.run_pack(s)
-                if tail:
-                    plan.run_poison(s)
+            for p in self.parts:
+                if p.fused:
+                    p.plan.run_pack(s)
+                if p.tail:
+                    p.plan.run_poison(s)
         self._pack_dirty = False
 
     def _run_all(self):
@@ -857,12 +869,12 @@ class DDIMStepper:
         dev = self.gd.device
         cur = torch.cuda.current_stream(dev)
         if not self.streams:
-            self.parts[0][2](cur.cuda_stream)
+            self.parts[0].run(cur.cuda_stream)
             return
-        for st, (_, _, run, _) in zip(self.streams, self.parts):
+        for st, p in zip(self.streams, self.parts):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                run(st.cuda_stream)
+                p.run(st.cuda_stream)
         for st in self.streams:
             cur.wait_stream(st)
 
@@ -872,22 +884,22 @@ class DDIMStepper:
         and an in-place edit of it between steps is taken up by the next step; with the batch split over several parts it is a
         concatenated COPY, and writes into it do not reach the sampler: edit through ``set_x``."""
         if len(self.parts) == 1:
-            return self.parts[0][1].x_in
-        return torch.cat([p.x_in for _, p, _, _ in self.parts], dim=0)
+            return self.parts[0].plan.x_in
+        return torch.cat([p.plan.x_in for p in self.parts], dim=0)
 
     def check(self) -> None:
         """once per sampling run (one host sync): a dependency wait of the persistent deep-level launch that timed out leaves an
         error word behind instead of hanging the GPU; results are garbage then and must not be returned silently"""
-        for _, plan, _, _ in self.parts:
-            if getattr(plan, "progs", None):
-                e = plan.take_error()
+        for p in self.parts:
+            if getattr(p.plan, "progs", None):
+                e = p.plan.take_error()
                 if e:
                     raise L.Jen1HipError(f"persistent deep-level launch: the wait for phase {e - 1} timed out "
                                          "(another persistent launch on the same GPU?); the error word was cleared")
 
     def _set_step(self, i: int):
-        for _, plan, _, _ in self.parts:
-            plan.step_idx.fill_(i)
+        for p in self.parts:
+            p.plan.step_idx.fill_(i)
         self._next = i
 
     def reset(self, x0: torch.Tensor, fresh_noise: bool = True):
@@ -897,8 +909,8 @@ class DDIMStepper:
         self._claim()                              # (another stepper of the same shape may have filled the shared plan since)
         if self._cap_modes is not None or not self.use_graph:
             self._sync_modes(claim=True)
-        for sl, plan, _, _ in self.parts:
-            plan.x_in.copy_(x0[sl])
+        for p in self.parts:
+            p.plan.x_in.copy_(x0[p.sl])
         if self.blend and self._known_set:          # the level the latents are at before step 0
             self._blend_parts(*self._kb_start, only_unfused=False)
         self._pack_dirty = True
@@ -915,15 +927,15 @@ class DDIMStepper:
     def _push_noise(self, i):
         if len(self.parts) == 1 or self.mode in ("vdm", "dpmpp"):
             return
-        for sl, _, _, ntab in self.parts:
+        for p in self.parts:
             if i is None:
-                ntab.copy_(self.noise_all[:, sl])
+                p.noise.copy_(self.noise_all[:, p.sl])
             else:
-                ntab[i].copy_(self.noise_all[i, sl])
+                p.noise[i].copy_(self.noise_all[i, p.sl])
 
     def step(self, i: int, noise: Optional[torch.Tensor] = None, drop_rows=None, set_rows=False):
-        for _, plan, _, _ in self.parts:
-            if getattr(plan, "_stepper_token", None) is not self._token:
+        for p in self.parts:
+            if getattr(p.plan, "_stepper_token", None) is not self._token:
                 raise RuntimeError(f"DDIMStepper.step: another stepper of shape {self.shape} and plan_slot={self.plan_slot} has used the "
                                    "same plan since this one's reset(): its latents, tables and conditioning are gone.  Call reset() "
                                    "to start again, or give samplers that run interleaved different plan_slot values")
@@ -931,16 +943,16 @@ class DDIMStepper:
             self._set_step(i)
         if self._cap_modes is not None and self._cap_modes != self._modes():
             self._sync_modes(claim=False)
-        for _, plan, _, _ in self.parts:           # (a replayed graph does not pass through DeepProgram.launch: mark the use here)
-            if getattr(plan, "progs", None):
-                plan.progs[0].touch()
+        for p in self.parts:                       # (a replayed graph does not pass through DeepProgram.launch: mark the use here)
+            if getattr(p.plan, "progs", None):
+                p.plan.progs[0].touch()
         if set_rows:
-            for sl, plan, _, _ in self.parts:
-                plan.set_rows(None if drop_rows is None else torch.as_tensor(drop_rows)[sl])
+            for p in self.parts:
+                p.plan.set_rows(None if drop_rows is None else torch.as_tensor(drop_rows)[p.sl])
         if noise is not None and i < self.num_steps - 1 and self.mode not in ("vdm", "dpmpp"):
             self.noise_all[i].copy_(noise.to(self.noise_all.device, torch.float32))
             self._push_noise(i)
-        if DeepProgram.host_serial[0] != self._seen_serial and any(t for _, t in self._part_fused.values()):
+        if DeepProgram.host_serial[0] != self._seen_serial and any(p.tail for p in self.parts):
             self._pack_dirty = True                # (somebody launched a persistent program from the host since this stepper's last step)
         if self._versions() != self._seen_versions:
             self._pack_dirty = True                # (x_in / ctx_in written in place since the last step: st.x[..., a:b] = known)

@@ -135,6 +135,81 @@ def test_argument_validation_reports_errors_without_a_gpu(lib):
     assert lib.jen1_norm_apply(C.byref(n), None) != 0
 
 
+# ---- the sampler step's nine entry points: every refusal, each made before anything is launched (B = 1, C = 8, T = 32; the pointers
+# are aligned non-NULL numbers that nothing reads).  A row = (what to change in the valid call, words of the refusal); the message
+# also names the entry point or its family ("cfg step" / "step_tail").
+_P0 = 4096
+_STEP_VALID = dict(net=_P0, x=2 * _P0, noise=3 * _P0, hist=3 * _P0, coef=4 * _P0, x_out=2 * _P0, out=2 * _P0, eps_out=None, x0_out=None,
+                   step_idx=5 * _P0, ticket=6 * _P0, rows=7 * _P0, parts=8 * _P0, ld_rows=8, B=1, C=8, T=32, ld=8, nrep=2, scale=0.8,
+                   scale_cfg=1, phi=0.7, objective=0, clip_x0=1, dtype=L.F32, poison_table=9 * _P0, n_rows=4, sync=None,
+                   zero_ptr=10 * _P0, zero_bytes=1024, blend=None)
+_SHAPE = "B C T ld nrep scale scale_cfg phi objective clip_x0 dtype"
+_PACK = "net x noise coef x_out step_idx ticket rows parts ld_rows " + _SHAPE
+_TAIL = " poison_table n_rows sync zero_ptr zero_bytes"
+_STEP_ORDER = {
+    "cfg_ddim_step": "net x noise coef x_out eps_out x0_out step_idx " + _SHAPE,
+    "cfg_ddim_step_adv": "net x noise coef x_out eps_out x0_out step_idx ticket " + _SHAPE,
+    "cfg_ddim_step_pack": _PACK,
+    "cfg_ddim_step_pack_blend": _PACK + " blend",
+    "cfg_ddim_step_pack_ms": _PACK.replace("noise", "hist") + " blend",
+    "step_tail": _PACK + _TAIL,
+    "step_tail_blend": _PACK + _TAIL + " blend",
+    "step_tail_ms": _PACK.replace("noise", "hist") + _TAIL + " blend",
+    "cfg_combine": "net out B C T ld scale scale_cfg phi dtype",
+}
+_NULLS = {"cfg_ddim_step": "net x coef x_out", "cfg_ddim_step_adv": "net x coef x_out step_idx ticket", "cfg_combine": "net out"}
+_BLEND_OK = (16, 32, 48, 64)
+
+
+def _step_refusals(name):
+    """the rows of one entry point"""
+    unpacked = name in ("cfg_ddim_step", "cfg_ddim_step_adv", "cfg_combine")
+    tail, ms, blend = name.startswith("step_tail"), name.endswith("_ms"), name.endswith("_blend")
+    rows = [({p: None}, b"null") for p in _NULLS.get(name, "net x coef x_out step_idx ticket rows parts").split()]
+    if name != "cfg_combine":
+        rows += [({"objective": -1}, b"objective"), ({"objective": 3}, b"objective"), ({"nrep": 0}, b"nrep"), ({"nrep": 3}, b"nrep")]
+    rows += [({"dtype": 7}, b""), ({"dtype": L.FP8}, b""), ({"C": 264, "ld": 264, "ld_rows": 264}, b"256"), ({"ld": 0}, b"")]
+    if unpacked:            # the general kernel takes any C in [2, 256] and any alignment
+        rows += [({"C": 1}, b"[2, 256]"), ({"C": 257, "ld": 264}, b"[2, 256]"), ({"C": 8, "ld": 7}, b"[2, 256]")]
+    else:                   # the vector forms: 8-channel vectors in 16-byte rows
+        rows += [({"C": 12, "ld": 16, "ld_rows": 16}, b"C %"), ({"C": 4}, b"C %"), ({"C": 0}, b""), ({"ld": 12}, b"16-byte rows"),
+                 ({"net": _P0 + 8}, b"16-byte rows"), ({"dtype": L.BF16, "net": _P0 + 8}, b"16-byte rows"),
+                 ({"dtype": L.BF16, "ld": 12, "ld_rows": 16}, b"16-byte rows"),
+                 ({"rows": 7 * _P0 + 8}, b"rows must be 16-byte aligned"), ({"parts": 8 * _P0 + 4}, b"rows must be 16-byte aligned"),
+                 ({"ld_rows": 4}, b"ld_rows >= C"), ({"ld_rows": 10}, b"rows must be 16-byte aligned"),
+                 ({"dtype": L.BF16, "ld_rows": 12}, b"rows must be 16-byte aligned")]
+    if tail:
+        rows += [({"poison_table": None}, b"sentinel table"), ({"n_rows": 0}, b"sentinel table"), ({"n_rows": 60001}, b"sentinel table"),
+                 ({"zero_ptr": None}, b"16-byte aligned and sized"), ({"zero_ptr": 10 * _P0 + 8}, b"16-byte aligned and sized"),
+                 ({"zero_bytes": 0}, b"16-byte aligned and sized"), ({"zero_bytes": 1000}, b"16-byte aligned and sized")]
+    if ms:
+        rows += [({"hist": None}, b"history buffer"), ({"hist": 3 * _P0 + 2}, b"4-byte aligned"),
+                 ({"hist": _STEP_VALID["x"]}, b"must not be the latents"), ({"hist": 11 * _P0, "x_out": 11 * _P0}, b"must not be the latents")]
+    if blend:
+        rows += [({"blend": None}, b"null blend")]
+    if ms or blend:
+        for i in range(4):
+            rows += [({"blend": _BLEND_OK[:i] + (None,) + _BLEND_OK[i + 1:]}, b"null known / eps_k / keep / kb"),
+                     ({"blend": _BLEND_OK[:i] + (_BLEND_OK[i] + 2,) + _BLEND_OK[i + 1:]}, b"4-byte aligned")]
+    return rows
+
+
+@pytest.mark.parametrize("name", list(_STEP_ORDER))
+def test_step_entry_points_refuse_bad_arguments_without_a_gpu(lib, name):
+    fn = getattr(lib, "jen1_" + name)
+    names = (name.encode() + b":", b"step_tail:" if name.startswith("step_tail") else b"cfg step")
+    valid = dict(_STEP_VALID, blend=_BLEND_OK if name.endswith("_blend") else None)
+    rows = _step_refusals(name)
+    if name.endswith("_ms"):                                  # (the blend is optional there: every row with and without it)
+        rows = rows + [(dict(ch, blend=_BLEND_OK), words) for ch, words in rows if "blend" not in ch]
+    for change, words in rows:
+        a = dict(valid, **change)
+        keep = L.BlendArgs(*a["blend"]) if a["blend"] is not None else None
+        a["blend"] = None if keep is None else C.byref(keep)
+        rc = fn(*[a[p] for p in _STEP_ORDER[name].split()], None)
+        msg = lib.jen1_last_error() if rc != 0 else b"(accepted)"
+        assert rc != 0 and words in msg and any(n in msg for n in names), (name, change, msg)
+
 def test_product_path_fails_loudly_without_gpu_or_library():
     from jen1_amd.model import UNetCFG1d
     if not torch.cuda.is_available():
