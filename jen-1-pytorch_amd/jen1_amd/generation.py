@@ -3,13 +3,15 @@
 Host-side mirror of /root/reference/generation.py:16-192 -- same constructor arguments, ``get_model_and_diffusion``,
 ``generate(prompt, seed, steps, batch_size, seconds, use_gdm, task, init_audio, init_audio_sr, inpainting_scope)`` (plus the keyword
 additions ``sampler``, ``preserve_known`` and ``output_sr``), ``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
-passed in instead (they are outside this build):
+passed in instead (their weights are outside this build):
 
   * ``audio_encoder``: the object the reference gets from ``EncodecModel.encodec_model_48khz()``; used exactly as
     generation.py uses it: ``.channels``, ``.encode(audio) -> [(codes, scale)]``, ``.quantizer.decode(codes)``,
     ``.decoder(emb)``  (generation.py:34, :95, :113, :130, :145-150);
   * ``conditioner``: the ``MultiConditioner`` of ``create_multi_conditioner`` (generation.py:29, :121-122),
-    ``conditioner(batch_metadata, device) -> {"prompt": (emb [B,128,1024], mask [B,128])}``;
+    ``conditioner(batch_metadata, device) -> {"prompt": (emb [B,128,1024], mask [B,128])}``.  ``jen1_amd.t5.T5ConditionerHIP`` is one: the
+    reference's ``T5Conditioner`` with the T5 encoder stack and ``proj_out`` on the HIP path (csrc/t5.hip); it takes the caller's tokenizer
+    and the encoder's ``state_dict`` (the checkpoint itself is not part of this build);
   * ``convert_audio``: ``encodec.utils.convert_audio`` (generation.py:95).  Optional: the default is ``jen1_amd.audio.convert_audio``, the
     same channel rule and windowed-sinc resampler as one HIP kernel on ``device`` (csrc/audio.hip).  Audio that already has the model's
     sample rate and channel count is passed through untouched, without loading the library.

@@ -19,13 +19,14 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GELU = 0, 1
 CFG_W64x64, CFG_W128x64, CFG_S16x64, CFG_S16x32, CFG_S16x16 = 0, 1, 2, 3, 4
 CFG_T128x64, CFG_T128x32, CFG_T128x16, CFG_T256x32, CFG_T256x16, CFG_T64x64 = 5, 6, 7, 8, 9, 10
+T5_ACT_GELU_NEW, T5_ACT_RELU, T5_MAX_TOKENS = 0, 1, 128      # include/jen1_t5.h
 
 c_void_p, c_int, c_float, c_int64 = C.c_void_p, C.c_int32, C.c_float, C.c_int64
 
@@ -249,6 +250,14 @@ SYMBOLS = {
     "jen1_abi_version": (c_int, []),
 }
 
+# every symbol include/jen1_t5.h declares (the T5 encoder stack of the text conditioner, csrc/t5.hip)
+T5_SYMBOLS = {
+    "jen1_t5_embed": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "jen1_t5_rmsnorm": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_int, _P]),
+    "jen1_t5_attention": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "jen1_t5_gate": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -262,7 +271,7 @@ def build(verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "jen1_hip.h"), os.path.join(INCLUDE, "jen1_train.h"),
-            os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h")]
+            os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h"), os.path.join(INCLUDE, "jen1_t5.h")]
     hdrs += [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h") and h != "common.h"]
     deps = srcs + hdrs
     if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -311,7 +320,7 @@ def load() -> C.CDLL:
     # pulls in the system runtime instead, and two runtimes in one process fail with "no ROCm-capable device".
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS}.items():
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
