@@ -13,6 +13,8 @@ from jen1_amd.init_fill import fill  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 SEED = 1234
+F32_TOL = 1e-3          # rel_err of a float32 path against the oracle (BASELINE.json; the figure test_gpu_model.py states)
+BF16_TOL = 5e-2         # the same for a bf16 path
 
 
 def golden(name):

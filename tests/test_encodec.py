@@ -164,6 +164,17 @@ def test_hip_decoder_vs_oracle_other_lengths():
         got = dec(torch.from_numpy(emb)).numpy()
         assert got.shape == want.shape == (B, 2, 320 * T)
         assert rel_err(got, want) < 1e-3, (B, T)
+    # one clip in bf16 mode (the ordinary Jen1.generate call): its LSTM is lstm_multi_kernel<bf16> (one sequence does not go to the
+    # matrix cores), or the single-workgroup kernel with the multi-workgroup one switched off
+    dec16 = SEANetDecoderHIP({k: torch.from_numpy(v) for k, v in p.items()}, compute_dtype="bf16")
+    emb = fill_normal("encodec.emb.9", (1, 128, 9), 6)
+    want = EO.seanet_decoder(p, emb)
+    for multi in (True, False):
+        dec16.lstm_multi = multi
+        got = dec16(torch.from_numpy(emb)).numpy()
+        assert got.shape == want.shape == (1, 2, 320 * 9)
+        assert rel_err(got, want) < 5e-2, multi
+        assert not multi or int(dec16.last_lstm_counters[:, 1].sum()) == 0
 
 
 @pytest.mark.gpu
