@@ -153,6 +153,12 @@ typedef struct jen1_deep_hot {
   int32_t n_chunks, Lc;
   float inv_nchunks;
   int32_t pad_hot_;
+  /* edge bias (jen1_conv_args.edge_bias), or NULL = none: [2][M] float32.  With it `bias` is [M], indexed by the GEMM row m instead
+   * of the output channel, and a lane whose GEMM column is the first of its batch element (t = 0) takes edge_bias[m], one whose column
+   * is the last (t = L_out - 1) takes edge_bias[M + m] in its place.  This is the bias of a 1x1 conv folded into the taps of the conv
+   * that follows it: the inner bias must not be counted for a tap that falls on a halo row.  The rows are read and the choice is made
+   * (two compares, selects) with the other epilogue operands, ahead of the dependency wait; the epilogue itself is unchanged. */
+  const float* edge_bias;
 } jen1_deep_hot;
 
 /* JEN1_DEEP_TILE: what a tile unit needs beyond the shared fields of jen1_deep_hot (w / bias / residual / y and its row mapping,
@@ -218,7 +224,9 @@ int jen1_deep_has_chunks(void);
  * mapping, pro_mode (NONE / GN / GN_SILU) with the gn_* fields (statistics pointers are ignored: the consumer computes
  * them), act, m_split / k_split, dtype, B / L_in / L_out.  When `film` is set it must be the FUSED GroupNorm-FiLM table
  * (gamma (scale + 1) at film_off + c, beta (scale + 1) + shift at film_off + film_C + c; rows picked by film_row / film_step
- * as in jen1_conv_args).  nb_max > 0 caps the batch elements per unit. */
+ * as in jen1_conv_args).  nb_max > 0 caps the batch elements per unit.
+ * edge_bias (optional, see jen1_deep_hot.edge_bias): needs bias (then [M]), stride == 1, L_out >= 2, no dual-range split
+ * (m_split == 0) and 16-byte aligned bias / edge_bias pointers; NULL keeps the per-channel bias and the unit's data path as is. */
 int jen1_deep_phase_conv(const jen1_conv_args* a, int nb_max, jen1_deep_phase* out);
 
 int jen1_deep_phase_attention(const void* q, const void* k, const void* v, void* out_t, const int32_t* kv_row, const void* kv_extra,

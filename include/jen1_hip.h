@@ -162,6 +162,10 @@ typedef struct jen1_conv_args {
                                 launch (they start poisoned and are polled, jen1_deep.h): bit 0 x0, bit 1 x1 (or seg[0] when c1 = 0),
                                 following bits the extra segments in source order, bit 8 the residual */
   int32_t reserved_;
+  const float* edge_bias;    /* jen1_deep_phase_conv only (every other entry point rejects it), or NULL: [2][M] float32.  `bias` is then
+                                [M] (one value per GEMM row m, not per output channel) and is replaced by edge_bias[m] in the FIRST GEMM
+                                column of every batch element (t = 0) and by edge_bias[M + m] in the LAST one (t = L_out - 1): the bias of
+                                two linear maps folded into one differs where a tap falls outside the sample (include/jen1_deep.h) */
 } jen1_conv_args;
 
 int jen1_conv_gemm(const jen1_conv_args* args, void* stream);

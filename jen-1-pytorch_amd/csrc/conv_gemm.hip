@@ -858,6 +858,7 @@ extern "C" int64_t jen1_conv_gemm_lds_bytes(const jen1_conv_args* args) {
 
 extern "C" int jen1_conv_gemm(const jen1_conv_args* args, void* stream) {
   JEN1_CHECK(args != nullptr, "conv_gemm: null args");
+  JEN1_CHECK(!args->edge_bias, "conv_gemm: an edge bias is an option of the persistent deep-level kernel only (jen1_deep_phase_conv)");
   if (int rc = validate(*args)) return rc;
   jen1_conv_args a = *args;
   // derived launch constants (kept out of the kernel's serial prologue)

@@ -827,6 +827,16 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
       const int n = nfe * 16 + li;
       const int ebl = (int)(((float)n + 0.5f) * inv_Lout);
       const int t = n - ebl * Lc + q0;
+      if (const float* edgep = HP(edge_bias, const float*)) {
+        // edge bias: all three rows are indexed by the GEMM row m; the lane's column picks one (selects, here in the set-up: the
+        // epilogue adds bias4 as always)
+        const f32x4 mid4 = *reinterpret_cast<const f32x4*>(biasp + m);
+        const f32x4 first4 = *reinterpret_cast<const f32x4*>(edgep + m);
+        const f32x4 last4 = *reinterpret_cast<const f32x4*>(edgep + (size_t)HI(MT) * 16 + m);
+        const bool is_first = t == 0, is_last = t == L_out - 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = is_first ? first4[r] : (is_last ? last4[r] : mid4[r]);
+      }
       const int ty = t * ps_f + ph - HI(ps_off);
       okk = n < nb * Lc && t < L_out && b0 + ebl < B && ty >= 0 && ty < HI(L_y);
       yrow = okk ? (b0 + ebl) * HI(y_brows) + HI(y_row0) + ty : 0;
@@ -2426,6 +2436,13 @@ extern "C" int jen1_deep_phase_conv(const jen1_conv_args* a, int nb_max, jen1_de
   }
   // ---- epilogue ----------------------------------------------------------------------------------------------------------------
   p.h.bias = a->bias; p.h.residual = a->residual; p.h.y = a->y;
+  if (a->edge_bias) {
+    JEN1_CHECK(a->bias, "deep conv: an edge bias replaces the per-row bias in the first / last column: bias ([M]) must be given");
+    JEN1_CHECK(a->stride == 1 && a->L_out >= 2, "deep conv: an edge bias needs stride 1 and at least two GEMM columns per batch element");
+    JEN1_CHECK(a->m_split == 0, "deep conv: an edge bias does not combine with the dual-range split");
+    JEN1_CHECK(((uintptr_t)a->bias & 15) == 0 && ((uintptr_t)a->edge_bias & 15) == 0, "deep conv: bias / edge_bias must be 16-byte aligned");
+    p.h.edge_bias = a->edge_bias;
+  }
   p.h.out_C = a->out_C; p.h.ps_f = a->ps_f < 1 ? 1 : a->ps_f; p.h.ps_off = a->ps_off; p.h.L_y = a->L_y; p.h.y_brows = a->y_brows;
   p.h.y_row0 = a->y_row0; p.h.ld_y = a->ld_y; p.h.ld_res = a->ld_res; p.h.act = a->act; p.h.y_f32 = a->y_f32;
   JEN1_CHECK(a->out_C % 4 == 0 && a->ld_y % 4 == 0 && (!a->residual || a->ld_res % 4 == 0), "deep conv: output channels / pitches must be multiples of 4");
@@ -2605,6 +2622,7 @@ extern "C" int jen1_deep_phase_tile(const jen1_conv_args* a, int tb, int bm, con
   JEN1_CHECK(a && out, "deep tile: null pointer");
   JEN1_CHECK(a->dtype == JEN1_F32 || a->dtype == JEN1_BF16, "deep tile: dtype must be float32 or bf16 (the JEN1_FP8 mode runs the long levels in bf16)");
   JEN1_CHECK(a->x0 && a->w && a->y, "deep tile: null tensor");
+  JEN1_CHECK(!a->edge_bias, "deep tile: an edge bias is an option of the deep GEMM phases only");
   JEN1_CHECK(a->pro_mode == JEN1_PRO_NONE || a->pro_mode == JEN1_PRO_GN || a->pro_mode == JEN1_PRO_GN_SILU, "deep tile: prologue %d is not supported", a->pro_mode);
   JEN1_CHECK(!a->ln_fold && !a->row_scale && !a->out_rowstats && a->act == JEN1_ACT_NONE && a->m_split == 0, "deep tile: LayerNorm / row scale / activation / dual range are not tile options");
   JEN1_CHECK(a->c0 > 0 && a->c0 % 32 == 0 && a->c1 % 32 == 0 && a->M % 16 == 0, "deep tile: channels must be multiples of 32, M of 16");

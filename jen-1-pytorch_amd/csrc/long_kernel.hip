@@ -848,6 +848,7 @@ extern "C" int jen1_long_phase_conv(const jen1_conv_args* a, int G, const float*
   JEN1_CHECK(a && out, "long phase: null pointer");
   JEN1_CHECK(a->dtype == JEN1_F32 || a->dtype == JEN1_BF16, "long phase: dtype must be float32 or bf16 (the JEN1_FP8 mode runs the long levels in bf16)");
   JEN1_CHECK(a->x0 && a->w && a->y, "long phase: null tensor");
+  JEN1_CHECK(!a->edge_bias, "long phase: an edge bias is an option of the deep GEMM phases only");
   JEN1_CHECK(a->pro_mode == JEN1_PRO_NONE || a->pro_mode == JEN1_PRO_GN || a->pro_mode == JEN1_PRO_GN_SILU, "long phase: prologue %d is not supported", a->pro_mode);
   JEN1_CHECK(!a->ln_fold && !a->row_scale && !a->out_rowstats && a->act == JEN1_ACT_NONE && a->m_split == 0 && !a->y_f32,
              "long phase: LayerNorm / row scale / activation / dual range / float32 output are not options of the long levels");

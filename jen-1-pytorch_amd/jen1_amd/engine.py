@@ -33,7 +33,8 @@ import torch
 
 from . import lib as L
 from .config import ResSpec, TransformerSpec, UNetSpec
-from .packing import (conv_weight_to_gemm, convT_weight_to_gemm, fold_layernorm, pack_gemm_weight)
+from .packing import (conv_weight_to_gemm, convT_weight_to_gemm, ff_out_matrix, fold_layernorm, fold_linear_into_upsample,
+                      pack_gemm_weight)
 
 FG = 32  # fine groups per tensor for GroupNorm statistics
 
@@ -77,6 +78,7 @@ class Weights:
         self.w: Dict[str, torch.Tensor] = {}
         self.v: Dict[str, torch.Tensor] = {}
         self._fp8: Dict[int, tuple] = {}
+        self._fold_src: Dict[str, tuple] = {}
         pk = lambda w_tmk: pack_gemm_weight(w_tmk, dtype)
         f32 = lambda t: t.contiguous()
 
@@ -151,6 +153,11 @@ class Weights:
             wt = p[f"{u.name}.upsample.weight"]
             self.w[f"{u.name}.up"] = pk(conv_weight_to_gemm(wt) if u.factor == 1 else convT_weight_to_gemm(wt, u.factor))
             self.v[f"{u.name}.up.bias"] = f32(p[f"{u.name}.upsample.bias"])
+            if u.transformer is not None and u.factor > 1:
+                # float32 sources of the up-path fold (fold_up): the packed copies above are already rounded to the compute dtype
+                tn = u.transformer.name
+                self._fold_src[u.name] = (u.factor, wt, p[f"{u.name}.upsample.bias"], p[f"{tn}.conv1d.conv.weight"], p[f"{tn}.conv1d.conv.bias"],
+                                          p[f"{tn}.blocks.0.feed_forward.2.weight"], p[f"{tn}.blocks.0.feed_forward.2.bias"])
 
         # ---- Transformer1d (blocks.py:497-537), LayerNorm folded into the projections -------------
         kvx_w, kvx_b, self.kvx_off = [], [], {}
@@ -250,6 +257,23 @@ class Weights:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.w.values())
 
+    def fold_up(self, uname: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The transformer's output conv folded into the upsampling conv of up level ``uname`` (UpsampleBlock1d.forward,
+        blocks.py:754-758: on the up path nobody else reads the transformer's result): ONE 2-tap sub-pixel GEMM over [x3 | gelu(f)]
+        with  Wf[k] = U[k] [P | P W_ff2]  (float64, rounded to the compute dtype once).  Returns (packed weight [2][(C + F) / 32]
+        [M / 16][64][8], bias [M] of an interior column, edge bias [2][M] of the first / last GEMM column of a sample:
+        packing.fold_linear_into_upsample).  Built when a plan first folds the site; ``{n}.ffp`` and ``{u}.up`` stay for the
+        launch-per-layer path."""
+        key = f"{uname}.upf"
+        if key not in self.w:
+            f, wt, b_up, wp, bp, w2, b2 = self._fold_src[uname]
+            wm, bm = ff_out_matrix(wp, bp, w2, b2)
+            wf, b_mid, b_first, b_last = fold_linear_into_upsample(wt, b_up, f, wm, bm)
+            self.w[key] = pack_gemm_weight(wf, self.dtype)
+            self.v[f"{key}.bias"] = b_mid.float().contiguous()
+            self.v[f"{key}.edge"] = torch.stack([b_first, b_last], 0).float().contiguous()
+        return self.w[key], self.v[f"{key}.bias"], self.v[f"{key}.edge"]
+
     def fp8(self, w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """JEN1_FP8 form of a packed weight ([..][M/16][64 lanes][8], any leading block dims): OCP e4m3 bytes in the same
         fragment order + one float32 scale per output row m = 16 mt + (lane & 15), chosen so that the row's largest magnitude
@@ -281,6 +305,17 @@ def _group_align(part) -> int:
     first column is a 256-column multiple (the kernel may then use its 256 x 256 tile form), else 128 (the minimum)"""
     n_lo = part[0][2]
     return 256 if all((n0 - n_lo) % 256 == 0 and N % 256 == 0 for _, _, n0, N, _ in part) else 128
+
+
+def parse_fold_up(s: str) -> Optional[frozenset]:
+    """JEN1_FOLD_UP: "" / "1" / "all" -> None (every up site of the persistent launch is folded), "0" -> no site, else a comma list of
+    level indices (a single level is written with a trailing comma when it is 0 or 1: "1,")"""
+    s = s.strip().lower()
+    if s in ("", "1", "all", "on"):
+        return None
+    if s in ("0", "off", "none"):
+        return frozenset()
+    return frozenset(int(v) for v in s.split(",") if v.strip())
 
 
 class DeepIneligible(Exception):
@@ -652,8 +687,9 @@ class OpBuilder:
     def conv(self, ops, *, src0: Act, w: torch.Tensor, bias, out: Act, taps=1, stride=1, pad_left=0, L_out=None,
              src1: Optional[Act] = None, src1_scale=1.0, ps_f=1, ps_off=0, L_y=None, y_row0=0, pro=L.PRO_NONE,
              gn=None, film=None, ln=None, act=L.ACT_NONE, residual: Optional[Act] = None, row_scale=None,
-             y_f32=False, out_C=None, force=None, label="", extra_segs=None, m_split=0, k_split=0, flat_w=False):
-        """extra_segs: [(Act, row_shift)] raw sources appended to the K axis after the (tap, source) pairs of
+             y_f32=False, out_C=None, force=None, label="", extra_segs=None, m_split=0, k_split=0, flat_w=False, edge_bias=None):
+        """edge_bias: [2][M] float32 (persistent deep-level kernel only; ``bias`` is then [M]: jen1_conv_args.edge_bias).
+        extra_segs: [(Act, row_shift)] raw sources appended to the K axis after the (tap, source) pairs of
         src0/src1 (streaming / direct mode only); ``w`` is then the flat packed weight [chunks][M/16][64][8]."""
         eng = self.eng
         a = L.ConvArgs()
@@ -662,6 +698,8 @@ class OpBuilder:
             a.x1, a.c1, a.ld1 = src1.t.data_ptr(), src1.cp, src1.ld
             assert src1.L == src0.L and src1.B == src0.B
         a.w, a.bias = w.data_ptr(), _ptr(bias)
+        a.edge_bias = _ptr(edge_bias)
+        assert edge_bias is None or self._deep_on, f"{label}: an edge bias exists only in the persistent deep-level kernel"
         a.dtype = eng.dt
         a.B, a.L_in = src0.B, src0.L
         a.L_out = L_out if L_out is not None else src0.L
@@ -744,7 +782,7 @@ class OpBuilder:
                 (256 if residual is not None and self.deep.is_live(residual.t) else 0)
             if m_split:
                 a.m_split, a.k_split = m_split, k_split
-            self._keep.append((a, src0, src1, w, w8, bias, out, residual, gn, film, extra_segs))
+            self._keep.append((a, src0, src1, w, w8, bias, edge_bias, out, residual, gn, film, extra_segs))
             # batch elements per unit: fewer per unit = smaller tiles to normalise and stage (the critical path of a phase) on more
             # workgroups, but every batch group streams the layer's weights again -- so only where the weights are small
             nb_cap = eng.deep_nb_max
@@ -1257,6 +1295,8 @@ class Plan(OpBuilder):
             self.pack_rows = None
             self.poison_op, self.poison_args = None, None
             self.taps: Dict[str, Act] = {}
+            self.fold_errors: List[str] = []
+            self.folded_levels: List[int] = []          # up levels whose transformer output conv runs inside the upsampling phase
             self.acts: List[Act] = []
             self.n_launch = 0
             self.deep_level = first if first < n_lv else None
@@ -1281,14 +1321,17 @@ class Plan(OpBuilder):
         assert self._arena_used <= self.arena.numel(), "statistics arena overflow"
         return self.arena[o: o + nfloats]
 
-    def new_act(self, B, L, C, gn=False, rs=False, dtype=None) -> Act:
+    def new_act(self, B, L, C, gn=False, rs=False, dtype=None, listed=True) -> Act:
+        """listed=False keeps the tensor off ``acts``, the creation-ordered list of the activations EVERY execution path of the network
+        forms (the paths are compared through it entry by entry): an intermediate that one path never forms stays off it in all"""
         ld = _ceil_to(C, 32)
         if ld != C:
             t = torch.zeros((B, L, ld), dtype=dtype or self.eng.tdtype, device=self.eng.device)
         else:
             t = self._empty((B, L, ld), dtype)
         a = Act(t, B, L, C, ld, self._stats(B * 64) if gn else None, self._stats(B * L * 2) if rs else None)
-        self.acts.append(a)
+        if listed:
+            self.acts.append(a)
         return a
 
     # ---------------------------------------------------------------- persistent deep-level launch
@@ -1413,8 +1456,11 @@ class Plan(OpBuilder):
                   pro=L.PRO_GN_SILU, gn=gn2, film=film, residual=res)
         return y
 
-    def transformer(self, t: TransformerSpec, x: Act, causal: bool) -> Act:
-        """Transformer1d.forward + TransformerBlock.forward (blocks.py:528-537, :483-489): 10 launches."""
+    def transformer(self, t: TransformerSpec, x: Act, causal: bool, fold_out: bool = False, list_out: bool = True):
+        """Transformer1d.forward + TransformerBlock.forward (blocks.py:528-537, :483-489): 10 launches.
+        fold_out: the caller folds the output conv into its own conv (the up path's upsampling, Weights.fold_up): the ``ffp`` GEMM
+        is not emitted and its operands (x3, gelu(f)) are handed back instead of the result (``transformer_out`` emits it after all).
+        list_out=False: the result stays off ``acts`` (new_act: a site whose result the folded form never writes)."""
         W, ops, eng = self.eng.W, self.ops, self.eng
         n, Cc, H, d = t.name, t.channels, t.heads, t.head_features
         mid = H * d
@@ -1480,7 +1526,16 @@ class Plan(OpBuilder):
             self.conv(ops, src0=a2, w=W.w[f"{n}.o2"], bias=W.v[f"{n}.o2.bias"], out=x3, residual=x2)
             f1 = self.new_act(Bf, Lx, Cf)
             self.conv(ops, src0=x3, w=W.w[f"{n}.ff1"], bias=W.v[f"{n}.ff1.bias"], out=f1, act=L.ACT_GELU)
-        y = self.new_act(Bf, Lx, Cc, gn=True)
+        if fold_out and eng.fuse_ff_out and self.streams(Bf, Lx, Cc) and x3.cp == Cc and f1.cp == f1.C:
+            return x3, f1
+        return self.transformer_out(t, x3, f1, listed=list_out)
+
+    def transformer_out(self, t: TransformerSpec, x3: Act, f1: Act, listed: bool = True) -> Act:
+        """the transformer's tail: FeedForward's second layer, the residual and the output 1x1 conv (blocks.py:446, :488, :536)"""
+        W, ops, eng = self.eng.W, self.ops, self.eng
+        n, Cc = t.name, t.channels
+        Bf, Lx = x3.B, x3.L
+        y = self.new_act(Bf, Lx, Cc, gn=True, listed=listed)
         if eng.fuse_ff_out and self.streams(Bf, Lx, Cc) and x3.cp == Cc and f1.cp == f1.C:
             self.conv(ops, src0=x3, w=W.w[f"{n}.ffp"], bias=W.v[f"{n}.ffp.bias"], out=y, extra_segs=[(f1, 0)])
             return y
@@ -1658,25 +1713,42 @@ class Plan(OpBuilder):
                 sk = skips.pop()
                 assert x.L == sk.L, (x.L, sk.L)      # crop already folded into the producing upsample
                 x = self.resblock(r, x, sk, causal)
-            if u.transformer:
-                x = self.transformer(u.transformer, x, causal)
             f = u.factor
+            level = n_lv - 1 - idx
+            # inside the persistent launch the transformer's output conv and the upsampling are ONE phase (Weights.fold_up): a linear map
+            # behind a linear map with no norm, activation, residual or second reader in between
+            xf = None
+            if u.transformer:
+                fold = self._deep_on and f > 1 and (eng.fold_up is None or level in eng.fold_up)
+                # (the transformer's result of such a site is not an entry of ``acts`` in ANY plan: the folded form never writes it)
+                x = self.transformer(u.transformer, x, causal, fold_out=fold, list_out=f == 1)
+                if isinstance(x, tuple):
+                    xf, x = x, x[0]
             last = idx == len(spec.ups) - 1
             # length the next consumer needs: the skips of the next level (or T at the top)
             # (a next level without blocks or transformer has no skip to crop against: its upsample takes the full f * L)
             L_need = skip0.L if last else (skips_list[-1][-1].L if skips_list[-1] else f * x.L)
             y = self.new_act(Be, L_need, u.c_out, gn=True)
-            if f == 1:
+            res = skip0 if last else None
+            p, diff = f // 2 + f % 2, f * x.L - L_need          # (x3 of a folded site has the transformer result's length)
+            assert diff >= 0
+            if xf is not None:
+                wf_, bf_, ef_ = W.fold_up(u.name)
+                try:
+                    self.conv(ops, src0=xf[0], src1=xf[1], src1_scale=1.0, w=wf_, bias=bf_, edge_bias=ef_, out=y, taps=2, pad_left=1,
+                              L_out=x.L + 1, ps_f=f, ps_off=p + diff // 2, out_C=u.c_out, residual=res, label=f"fold_up{level}")
+                except DeepIneligible as e:
+                    # the folded tile ([x3 | f] with its halo rows) does not fit a unit: the two phases as before
+                    self.fold_errors.append(f"level {level}: {e}")
+                    x, xf = self.transformer_out(u.transformer, xf[0], xf[1], listed=False), None
+            if xf is not None:
+                self.folded_levels.append(level)
+            elif f == 1:
                 assert L_need == x.L
-                self.conv(ops, src0=x, w=W.w[f"{u.name}.up"], bias=W.v[f"{u.name}.up.bias"], out=y, taps=3, pad_left=1,
-                          residual=skip0 if last else None)
+                self.conv(ops, src0=x, w=W.w[f"{u.name}.up"], bias=W.v[f"{u.name}.up.bias"], out=y, taps=3, pad_left=1, residual=res)
             else:
-                p = f // 2 + f % 2
-                diff = f * x.L - L_need
-                assert diff >= 0
                 self.conv(ops, src0=x, w=W.w[f"{u.name}.up"], bias=W.v[f"{u.name}.up.bias"], out=y, taps=2, pad_left=1,
-                          L_out=x.L + 1, ps_f=f, ps_off=p + diff // 2, out_C=u.c_out,
-                          residual=skip0 if last else None)
+                          L_out=x.L + 1, ps_f=f, ps_off=p + diff // 2, out_C=u.c_out, residual=res)
             x = y
             self.taps[f"up{idx}"] = x
             if self.deep_level is not None and n_lv - 1 - idx == self.deep_level:
@@ -1901,6 +1973,10 @@ class Engine:
         # 0 -> 922, 128 / 2 MB -> 927, 128 / 8 MB -> 893, 128 / 16 MB -> 889, 192 / 4 MB -> 918, 256 / 8 MB -> 909, 256 / 32 MB -> 1001
         self.deep_unit_target = int(os.environ.get("JEN1_DEEP_UNIT_TARGET", "128"))
         self.deep_reread_cap = int(float(os.environ.get("JEN1_DEEP_REREAD_MB", "16")) * (1 << 20))
+        # up path of the persistent launch: the transformer's output conv folded into the upsampling conv, one phase instead of two per
+        # site (Weights.fold_up).  JEN1_FOLD_UP: unset / "1" = every site, "0" = none (two phases), a comma list of level indices ("8,7,"
+        # -- the level of downsamples.<i>) = those sites only.  None = all, else the set of folded levels; part of the plan key.
+        self.fold_up = parse_fold_up(os.environ.get("JEN1_FOLD_UP", "1"))
         self.plans: Dict[tuple, Plan] = {}
         self.load_params(params)
 
@@ -1955,7 +2031,7 @@ class Engine:
             deep = slot == 0 or self.deep_all_slots
         deep = bool(deep) and self.use_deep
         det = self.deterministic if deterministic is None else bool(deterministic)
-        key = (B, T, nrep, bool(causal), slot, n_t, deep, det)
+        key = (B, T, nrep, bool(causal), slot, n_t, deep, det, self.fold_up)
         if key not in self.plans:
             self.plans[key] = Plan(self, B, T, nrep, bool(causal), n_t, deep=deep, deterministic=det)
         return self.plans[key]

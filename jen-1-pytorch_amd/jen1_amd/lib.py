@@ -62,7 +62,7 @@ class ConvArgs(C.Structure):
         ("zeros", c_void_p), ("tiles_t", c_int), ("inv_tiles_t", c_float), ("inv_tb", c_float),
         ("film_step", c_void_p), ("ln_u", c_void_p), ("ln_fold", c_int), ("nseg", c_int),
         ("seg", ConvSeg * MAX_SEG), ("m_split", c_int), ("k_split", c_int), ("w_scale", c_void_p),
-        ("live_mask", c_int), ("reserved_", c_int),
+        ("live_mask", c_int), ("reserved_", c_int), ("edge_bias", c_void_p),
     ]
 
 

@@ -54,3 +54,30 @@ def fold_layernorm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
     """Linear(LayerNorm(x)) = (W diag(gamma)) xhat + W beta  (reference blocks.py:427-429):
     returns (W', b') so the kernel's LN prologue only standardises."""
     return w * gamma[None, :], w @ beta
+
+
+def ff_out_matrix(w_proj: torch.Tensor, b_proj: torch.Tensor, w_ff2: torch.Tensor, b_ff2: torch.Tensor):
+    """The transformer's tail  y = P (x + W_ff2 f + b_ff2) + b_P  (reference blocks.py:446, :488, :536) as ONE linear map over
+    the K concat [x | f]: returns (Wm = [P | P W_ff2]  [C][C + F],  b_m = b_P + P b_ff2) in float64.
+    w_proj: the 1x1 conv weight [C][C][1] or [C][C]."""
+    P = (w_proj[:, :, 0] if w_proj.dim() == 3 else w_proj).double()
+    return torch.cat([P, P @ w_ff2.double()], 1), b_proj.double() + P @ b_ff2.double()
+
+
+def fold_linear_into_upsample(w_up: torch.Tensor, b_up: torch.Tensor, f: int, wm: torch.Tensor, b_m: torch.Tensor):
+    """ConvTranspose1d(y) with y = Wm z + b_m (a 1x1 conv over the K concat z) as ONE 2-tap sub-pixel GEMM over z.
+
+    With U[k] the two packed taps of the transposed conv (``convT_weight_to_gemm``: tap 0 <-> y[q-1], tap 1 <-> y[q]) GEMM
+    column q in [0, L] is  U[0] y[q-1] + U[1] y[q] + b_up, and y does not exist outside [0, L): there the staged halo rows of z
+    are zero, so the matrix part  Wf[k] = U[k] Wm  needs no edge treatment -- but b_m must not be counted for a tap that falls
+    outside the sample.  Returns, in float64,
+        Wf      [2][f * C_out][K]    the folded taps,
+        b_mid   [f * C_out]          bias of an interior column:  b_up + (U[0] + U[1]) b_m,
+        b_first [f * C_out]          bias of column q = 0:        b_up + U[1] b_m,
+        b_last  [f * C_out]          bias of column q = L:        b_up + U[0] b_m
+    (row m = r * C_out + co as in ``convT_weight_to_gemm``; the biases are per GEMM row because U differs per phase r)."""
+    U = convT_weight_to_gemm(w_up.double(), f)            # [2][f * C_out][C]
+    wm, b_m = wm.double(), b_m.double()
+    bu = b_up.double().repeat(f)
+    u0b, u1b = U[0] @ b_m, U[1] @ b_m
+    return torch.stack([U[0] @ wm, U[1] @ wm], 0), bu + u0b + u1b, bu + u1b, bu + u0b
