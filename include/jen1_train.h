@@ -199,6 +199,33 @@ int jen1_lstm_layer(const float* gin, const void* whh_t, const void* skip, void*
 int jen1_lstm_layer_multi(const float* gin, const void* whh, const void* skip, void* y, float* hbuf, uint32_t* counters, int B, int T,
                           int H, int ld_y, int dtype, void* stream);
 
+/* --- EncodecModel.encode / .decode around the SEANet halves (encodec model.py; segments of `L` samples every `stride` samples) ---
+ * jen1_codec_segment_scales: scale[b][s] = 1e-8 + sqrt(mean_n (mean_c x)^2) over segment s (the last ones may be short) of
+ *   audio float32 [B][C][N]; scale float32 [B][S].  Fixed summation order.
+ * jen1_codec_segment_cut: the rows the encoder's first convolution reads for the n_sel equal-length segments s0 .. s0 + n_sel - 1:
+ *   rows (dtype) [n_sel * B][L][8], row j * B + b, = audio[b][c][(s0 + j) stride + i] / scale[b][s0 + j] (a float32 division;
+ *   scale == NULL: the plain cut), columns C .. 7 zero.  Here L is the length of THESE segments.
+ * jen1_codec_pad1d: pad1d(mode = "reflect") of encodec modules/conv.py on channel-last rows x (dtype) [rows][L][ld] ->
+ *   y [rows][L + left + right][ld], including its small-input rule: when L <= max(left, right) the input is zero-extended on the
+ *   right by max(left, right) - L + 1 before the reflection and the same count is dropped from the end.  ld a multiple of 8.
+ * jen1_codec_overlap_add: EncodecModel._linear_overlap_add followed by the trim to N_out, gather form (no atomics):
+ *   out[b][c][n] = sum_s w(n - s stride) scale[b][s] y_s[b][n - s stride][c] / sum_s w(n - s stride) over the frames that cover n,
+ *   w(i) = 0.5 - |(i + 1) / (L0 + 1) - 0.5| (L0: the length of the first frame; a shorter frame uses the head of the same triangle).
+ *   segs: DEVICE table of S entries; frame s of batch element b is row (row0 + b) of the channel-last tensor rows (dtype) [..][len][8]
+ *   (the decoder's final rows as it leaves them).  scale float32 [B][S] or NULL, out float32 [B][C][N_out],
+ *   N_out <= stride (S - 1) + L_last; every len must be <= L0 and L_last is the last entry's len. */
+typedef struct jen1_ola_seg {
+  const void* rows;
+  int32_t row0;
+  int32_t len;
+} jen1_ola_seg;
+int jen1_codec_segment_scales(const float* audio, float* scale, int B, int C, int64_t N, int L, int stride, int S, void* stream);
+int jen1_codec_segment_cut(const float* audio, const float* scale, void* rows, int B, int C, int64_t N, int L, int stride, int S, int s0,
+                           int n_sel, int dtype, void* stream);
+int jen1_codec_pad1d(const void* x, void* y, int rows, int L, int ld, int left, int right, int dtype, void* stream);
+int jen1_codec_overlap_add(const jen1_ola_seg* segs, int S, const float* scale, float* out, int B, int C, int ld, int N_out, int stride,
+                           int L0, int L_last, int dtype, void* stream);
+
 /* --- the two ends of a training pass (csrc/train_glue.hip): what the reference writes as ATen elementwise / cat / reduce ops around
  * the network, one launch each ---
  * jen1_train_pack_input: x_t = ca[b] x0 + cb[b] noise (q_sample, gdm.py:232-243), torch.cat([x_t, input_concat_cond], 1)

@@ -288,6 +288,118 @@ __global__ __launch_bounds__(1024) void lstm_multi_mfma_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// EncodecModel.encode / .decode around the SEANet halves: segment scales, segment cut, pad1d and the linear overlap-add
+// ---------------------------------------------------------------------------------------------------------------------
+
+// scale[b][s] = 1e-8 + sqrt(mean_n (mean_c x)^2) over segment s: one workgroup per (s, b); every thread sums its strided share in
+// double, then a tree over LDS in a fixed order (the result does not depend on scheduling)
+__global__ __launch_bounds__(256) void codec_segment_scales_kernel(const float* __restrict__ audio, float* __restrict__ scale, int C,
+                                                                   long long N, int Lseg, int stride, int S) {
+  __shared__ double part[256];
+  const int s = blockIdx.x, b = blockIdx.y;
+  const long long n0 = (long long)s * stride;
+  const long long rest = N - n0;
+  const int len = rest < Lseg ? (int)rest : Lseg;
+  const float* x = audio + (long long)b * C * N + n0;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < len; i += 256) {
+    float m = 0.f;
+    for (int c = 0; c < C; ++c) m += x[(long long)c * N + i];
+    const double md = (double)m / (double)C;
+    acc += md * md;
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) scale[(long long)b * S + s] = (float)(1e-8 + sqrt(part[0] / (double)len));
+}
+
+// rows[(j B + b)][i][0..7] = audio[b][c][(s0 + j) stride + i] / scale[b][s0 + j] (a true float32 division; scale == NULL: the plain
+// cut), columns C..7 zero: the channel-last rows the encoder's first convolution reads
+template <typename T>
+__global__ __launch_bounds__(256) void codec_segment_cut_kernel(const float* __restrict__ audio, const float* __restrict__ scale,
+                                                                T* __restrict__ rows, int B, int C, long long N, int Lsel, int stride, int S,
+                                                                int s0) {
+  const int i = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
+  if (i >= Lsel) return;
+  const int j = row / B, b = row - j * B, s = s0 + j;
+  const float* x = audio + (long long)b * C * N + (long long)s * stride + i;
+  const float sc = scale ? scale[(long long)b * S + s] : 1.0f;
+  float v[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    v[c] = 0.f;
+    if (c < C) {
+      const float a = x[(long long)c * N];
+      v[c] = scale ? a / sc : a;
+    }
+  }
+  store8(rows + ((long long)row * Lsel + i) * 8, v);
+}
+
+// pad1d(mode="reflect") of encodec modules/conv.py on channel-last rows, 16 bytes per thread: y[r][j] = z[reflect(j - left)] with
+// z = x zero-extended on the right to Lz = L + extra (extra = max(left, right) - L + 1 when L <= max(left, right), else 0); the
+// `extra` entries the package drops from the end are never produced
+__global__ __launch_bounds__(256) void codec_pad1d_kernel(const uint4* __restrict__ x, uint4* __restrict__ y, long long total, int L, int units,
+                                                          int left, int right) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int Lp = L + left + right;
+  const int u = (int)(e % units);
+  const long long rj = e / units;
+  const int j = (int)(rj % Lp);
+  const long long r = rj / Lp;
+  const int max_pad = left > right ? left : right;
+  const int Lz = L <= max_pad ? max_pad + 1 : L;
+  int q = j - left;
+  if (q < 0) q = -q;
+  if (q >= Lz) q = 2 * (Lz - 1) - q;
+  y[e] = q < L ? x[(r * L + q) * units + u] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// EncodecModel._linear_overlap_add in gather form: one thread per (b, n) walks the segments that cover n in ascending order (no
+// atomics: bit-identical from run to run), reads the decoder's final rows (8 wide) and writes channel-first float32.  No contraction
+// of the multiply-adds: the sums are the ones a float32 restatement of the formula makes.
+template <typename T>
+__global__ __launch_bounds__(256) void codec_overlap_add_kernel(const jen1_ola_seg* __restrict__ segs, int S, const float* __restrict__ scale,
+                                                                float* __restrict__ out, int C, int N_out, int stride, int L0) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (n >= N_out) return;
+  int s_hi = n / stride;
+  if (s_hi > S - 1) s_hi = S - 1;
+  const int s_lo = n < L0 ? 0 : (n - L0) / stride + 1;          // the first s with n - s stride < L0
+  float num[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) num[c] = 0.f;
+  float den = 0.f;
+  const float span = (float)(L0 + 1);
+  for (int s = s_lo; s <= s_hi; ++s) {
+    const jen1_ola_seg e = segs[s];
+    const int i = n - s * stride;
+    if (i >= e.len) continue;
+    const float t = (float)(i + 1) / span;
+    const float w = 0.5f - fabsf(t - 0.5f);
+    float v[8];
+    load8(reinterpret_cast<const T*>(e.rows) + ((long long)(e.row0 + b) * e.len + i) * 8, v);
+    if (scale) {
+      const float sc = scale[(long long)b * S + s];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) v[c] = v[c] * sc;
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) num[c] = num[c] + w * v[c];
+    den = den + w;
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+    if (c < C) out[((long long)b * C + c) * N_out + n] = den > 0.f ? num[c] / den : 0.f;
+}
+
 }  // namespace
 
 extern "C" int jen1_rvq_decode(const int64_t* codes, const float* tables, float* out, int n_q, int B, int T, int bins, int D, void* stream) {
@@ -339,6 +451,71 @@ extern "C" int jen1_lstm_layer(const float* gin, const void* whh_t, const void* 
   if (dtype == JEN1_F32) { if (rpt == 1) JEN1_LSTM(float, 1); else if (rpt == 2) JEN1_LSTM(float, 2); else JEN1_LSTM(float, 4); }
   else { if (rpt == 1) JEN1_LSTM(bf16_t, 1); else if (rpt == 2) JEN1_LSTM(bf16_t, 2); else JEN1_LSTM(bf16_t, 4); }
 #undef JEN1_LSTM
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_codec_segment_scales(const float* audio, float* scale, int B, int C, int64_t N, int L, int stride, int S, void* stream) {
+  JEN1_CHECK(audio && scale, "jen1_codec_segment_scales: NULL argument");
+  JEN1_CHECK(B >= 1 && B <= 65535 && C >= 1 && N >= 1 && L >= 1 && stride >= 1 && S >= 1, "jen1_codec_segment_scales: bad shape");
+  JEN1_CHECK((int64_t)(S - 1) * stride < N, "jen1_codec_segment_scales: segment %d starts past the %lld samples", S - 1, (long long)N);
+  hipLaunchKernelGGL(codec_segment_scales_kernel, dim3(S, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), audio, scale, C,
+                     (long long)N, L, stride, S);
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_codec_segment_cut(const float* audio, const float* scale, void* rows, int B, int C, int64_t N, int L, int stride, int S,
+                                      int s0, int n_sel, int dtype, void* stream) {
+  JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "jen1_codec_segment_cut: dtype must be JEN1_F32 or JEN1_BF16");
+  JEN1_CHECK(audio && rows, "jen1_codec_segment_cut: NULL argument");
+  JEN1_CHECK(B >= 1 && C >= 1 && C <= 8 && N >= 1 && L >= 1 && stride >= 1 && S >= 1, "jen1_codec_segment_cut: bad shape");
+  JEN1_CHECK(s0 >= 0 && n_sel >= 1 && s0 + n_sel <= S && (int64_t)n_sel * B <= 65535, "jen1_codec_segment_cut: bad segment range %d + %d of %d",
+             s0, n_sel, S);
+  JEN1_CHECK((int64_t)(s0 + n_sel - 1) * stride + L <= N, "jen1_codec_segment_cut: segment %d of length %d ends past the %lld samples",
+             s0 + n_sel - 1, L, (long long)N);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((L + 255) / 256, n_sel * B);
+  if (dtype == JEN1_F32)
+    hipLaunchKernelGGL(codec_segment_cut_kernel<float>, grid, dim3(256), 0, s, audio, scale, reinterpret_cast<float*>(rows), B, C, (long long)N, L,
+                       stride, S, s0);
+  else
+    hipLaunchKernelGGL(codec_segment_cut_kernel<bf16_t>, grid, dim3(256), 0, s, audio, scale, reinterpret_cast<bf16_t*>(rows), B, C, (long long)N,
+                       L, stride, S, s0);
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_codec_pad1d(const void* x, void* y, int rows, int L, int ld, int left, int right, int dtype, void* stream) {
+  JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "jen1_codec_pad1d: dtype must be JEN1_F32 or JEN1_BF16");
+  JEN1_CHECK(x && y, "jen1_codec_pad1d: NULL argument");
+  JEN1_CHECK(rows >= 1 && L >= 1 && ld >= 8 && ld % 8 == 0 && left >= 0 && right >= 0, "jen1_codec_pad1d: bad shape rows=%d L=%d ld=%d (%d, %d)",
+             rows, L, ld, left, right);
+  const int units = ld * (dtype == JEN1_F32 ? 4 : 2) / 16;
+  const long long total = (long long)rows * (L + left + right) * units;
+  JEN1_CHECK(total <= 0x7fffffffLL * 256, "jen1_codec_pad1d: too many elements");
+  hipLaunchKernelGGL(codec_pad1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint4*>(x), reinterpret_cast<uint4*>(y), total, L, units, left, right);
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_codec_overlap_add(const jen1_ola_seg* segs, int S, const float* scale, float* out, int B, int C, int ld, int N_out,
+                                      int stride, int L0, int L_last, int dtype, void* stream) {
+  JEN1_CHECK(dtype == JEN1_F32 || dtype == JEN1_BF16, "jen1_codec_overlap_add: dtype must be JEN1_F32 or JEN1_BF16");
+  JEN1_CHECK(segs && out, "jen1_codec_overlap_add: NULL argument");
+  JEN1_CHECK(S >= 1 && B >= 1 && B <= 65535 && C >= 1 && C <= 8 && ld == 8, "jen1_codec_overlap_add: bad shape S=%d B=%d C=%d ld=%d (ld must be 8)",
+             S, B, C, ld);
+  JEN1_CHECK(stride >= 1 && L0 >= 1 && L_last >= 1 && L_last <= L0 && (S == 1 || stride <= L0),
+             "jen1_codec_overlap_add: bad frames stride=%d L0=%d L_last=%d", stride, L0, L_last);
+  JEN1_CHECK(N_out >= 1 && (int64_t)N_out <= (int64_t)stride * (S - 1) + L_last, "jen1_codec_overlap_add: N_out=%d is more than the frames cover",
+             N_out);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((N_out + 255) / 256, B);
+  if (dtype == JEN1_F32)
+    hipLaunchKernelGGL(codec_overlap_add_kernel<float>, grid, dim3(256), 0, s, segs, S, scale, out, C, N_out, stride, L0);
+  else
+    hipLaunchKernelGGL(codec_overlap_add_kernel<bf16_t>, grid, dim3(256), 0, s, segs, S, scale, out, C, N_out, stride, L0);
   JEN1_HIP(hipGetLastError());
   return 0;
 }

@@ -139,9 +139,18 @@ class _SEANetOps:
                                   None, 0, y.data_ptr(), B, Lx, C, ld, 1, 1e-5, 0, dt, s), "jen1_gn_apply")
         return y
 
-    def _conv(self, x: torch.Tensor, name: str, stride: int = 1) -> torch.Tensor:
+    def _pad1d(self, x: torch.Tensor, left: int, right: int) -> torch.Tensor:
+        """``pad1d(x, (left, right), "reflect")`` of modules/conv.py as an explicit copy (jen1_codec_pad1d), small-input rule included"""
+        B, Lx, ld = x.shape
+        y = torch.empty((B, Lx + left + right, ld), dtype=x.dtype, device=x.device)
+        L.check(self.rt.lib.jen1_codec_pad1d(x.data_ptr(), y.data_ptr(), B, Lx, ld, left, right, self.rt.dt_of(x), self.rt.stream()), "jen1_codec_pad1d")
+        return y
+
+    def _conv(self, x: torch.Tensor, name: str, stride: int = 1, tiny: bool = False) -> torch.Tensor:
         """SConv1d, non-causal: reflect padding of k - stride (split right-first) plus the extra right padding that
-        makes the frame count whole (modules/conv.py get_extra_padding_for_conv1d), conv, GroupNorm(1)"""
+        makes the frame count whole (modules/conv.py get_extra_padding_for_conv1d), conv, GroupNorm(1).
+        An input of no more frames than the padding is outside what the index map of the GEMM can mirror; ``tiny=True`` (what the two
+        networks pass) applies pad1d's small-input rule through a padded copy of those few frames, ``tiny=False`` refuses them."""
         w, b = self.p[f"{name}.conv.weight"], self.p[f"{name}.conv.bias"]
         co, ci, k = w.shape
         Lx = x.shape[1]
@@ -150,9 +159,13 @@ class _SEANetOps:
         Lout = -(-(Lx - k + total) // stride) + 1                  # ceil((L - k + total) / stride) + 1
         right = (Lout - 1) * stride + k - left - Lx                # total // 2 + extra padding
         if Lx <= max(left, right):
-            raise NotImplementedError(f"{name}: {Lx} frames are not more than the reflect padding ({left}, {right}); encodec's "
-                                      "tiny-input case of pad1d is not built")
-        g = ConvGeom("conv", k, stride, left, Lx, Lout, ci, co, reflect=True)
+            if not tiny:
+                raise NotImplementedError(f"{name}: {Lx} frames are not more than the reflect padding ({left}, {right}); pass tiny=True for "
+                                          "the small-input case of encodec's pad1d")
+            x = self._pad1d(x.contiguous(), left, right)
+            g = ConvGeom("conv", k, stride, 0, Lx + left + right, Lout, ci, co)
+        else:
+            g = ConvGeom("conv", k, stride, left, Lx, Lout, ci, co, reflect=True)
         y = _conv_forward(self.rt, x, self.rt.packed(w, "conv", x.dtype), b, g)
         return self._norm(y, name, co)
 
@@ -174,9 +187,14 @@ class _SEANetOps:
         return y
 
     def _resblock(self, x: torch.Tensor, name: str) -> torch.Tensor:
-        h = self._conv(self._elu(x), f"{name}.block.1")
-        h = self._conv(self._elu(h), f"{name}.block.3")
-        return self._conv(x, f"{name}.shortcut") + h
+        h = self._conv(self._elu(x), f"{name}.block.1", tiny=True)
+        h = self._conv(self._elu(h), f"{name}.block.3", tiny=True)
+        return self._conv(x, f"{name}.shortcut", tiny=True) + h
+
+    def lstm_multi_rows(self) -> int:
+        """the most sequences one pass may hold for ``_lstm`` to stay on jen1_lstm_layer_multi (its co-residency bound)"""
+        H = self.whh[0].shape[1]
+        return 8 * (256 // (H // 32))
 
     def _lstm(self, x: torch.Tensor) -> torch.Tensor:
         """SLSTM: y = LSTM(x) + x over the time axis (modules/lstm.py)"""
@@ -227,20 +245,28 @@ class SEANetDecoderHIP(_SEANetOps):
         return cls({k: v for k, v in decoder.state_dict().items()}, ratios, **kw)
 
     # ------------------------------------------------------------------ SEANetDecoder.forward
+    @property
+    def channels(self) -> int:
+        return self.p[f"layers.{self.last}.conv.weight"].shape[0]
+
     @torch.no_grad()
-    def __call__(self, emb: torch.Tensor) -> torch.Tensor:
-        """latents [B, 128, T] (any device) -> audio float32 [B, channels, hop * T] on the same device"""
-        src = emb.device
-        x = emb.to(self.device, torch.float32)
-        h = self._conv(self._to_rows(x), "layers.0")
+    def rows(self, emb: torch.Tensor) -> torch.Tensor:
+        """latents [B, 128, T] on the decoder's device -> the output convolution's rows as it leaves them: channel-last
+        [B, hop * T, pad8(channels)] in the compute dtype (what jen1_codec_overlap_add reads); the caller runs ``_check_lstm``"""
+        h = self._conv(self._to_rows(emb.to(self.device, torch.float32)), "layers.0", tiny=True)
         h = self._lstm(h)
         for conv_idx, ratio, res in self.stages:
             h = self._conv_transpose(self._elu(h), f"layers.{conv_idx}", ratio)
             for r in res:
                 h = self._resblock(h, f"layers.{r}")
-        h = self._conv(self._elu(h), f"layers.{self.last}")
-        ch = self.p[f"layers.{self.last}.conv.weight"].shape[0]
-        out = h[:, :, :ch].to(torch.float32).transpose(1, 2).contiguous().to(src)
+        return self._conv(self._elu(h), f"layers.{self.last}", tiny=True)
+
+    @torch.no_grad()
+    def __call__(self, emb: torch.Tensor) -> torch.Tensor:
+        """latents [B, 128, T] (any device) -> audio float32 [B, channels, hop * T] on the same device"""
+        src = emb.device
+        h = self.rows(emb)
+        out = h[:, :, :self.channels].to(torch.float32).transpose(1, 2).contiguous().to(src)
         self._check_lstm()
         return out
 
@@ -265,25 +291,53 @@ class SEANetEncoderHIP(_SEANetOps):
     def __call__(self, audio: torch.Tensor) -> torch.Tensor:
         """audio [B, channels, L] -> latents float32 [B, 128, ceil(L / 320)] on the same device"""
         src = audio.device
-        h = self._conv(self._to_rows(audio.to(self.device, torch.float32)), "layers.0")
+        out = self.from_rows(self._to_rows(audio.to(self.device, torch.float32))).to(src)
+        self._check_lstm()
+        return out
+
+    @torch.no_grad()
+    def from_rows(self, rows: torch.Tensor) -> torch.Tensor:
+        """the same from the first convolution's input rows [B, L, pad8(channels)] in the compute dtype (jen1_codec_segment_cut writes
+        them) -> latents float32 [B, 128, ceil(L / 320)] on the encoder's device; the caller runs ``_check_lstm``"""
+        h = self._conv(rows, "layers.0", tiny=True)
         idx = 1
         for r in self.ratios:
             for j in range(self.n_res):
                 h = self._resblock(h, f"layers.{idx + j}")
             idx += self.n_res
-            h = self._conv(self._elu(h), f"layers.{idx + 1}", stride=r)
+            h = self._conv(self._elu(h), f"layers.{idx + 1}", stride=r, tiny=True)
             idx += 2
         h = self._lstm(h)
-        h = self._conv(self._elu(h), f"layers.{self.last}")
+        h = self._conv(self._elu(h), f"layers.{self.last}", tiny=True)
         ch = self.p[f"layers.{self.last}.conv.weight"].shape[0]
-        out = h[:, :, :ch].to(torch.float32).transpose(1, 2).contiguous().to(src)
-        self._check_lstm()
-        return out
+        return h[:, :, :ch].to(torch.float32).transpose(1, 2).contiguous()
+
+
+def segment_lengths(n: int, segment_length: int, segment_stride: int) -> List[int]:
+    """the sample counts of the segments ``EncodecModel.encode`` cuts ``n`` samples into (model.py: one per offset 0, stride, ...)"""
+    return [min(segment_length, n - off) for off in range(0, n, segment_stride)]
+
+
+def segment_frame_counts(n: int, segment_length: int, segment_stride: int, hop: int = HOP_48K) -> List[int]:
+    """the latent frames per segment, ceil(samples / hop): 10 s at 48 kHz -> 10 x 150 + 15"""
+    return [-(-m // hop) for m in segment_lengths(n, segment_length, segment_stride)]
+
+
+def _runs(values: Sequence[int]) -> List[tuple]:
+    """(first index, count, value) of every run of equal neighbours"""
+    out: List[tuple] = []
+    for i, v in enumerate(values):
+        if out and out[-1][2] == v:
+            out[-1] = (out[-1][0], out[-1][1] + 1, v)
+        else:
+            out.append((i, 1, v))
+    return out
 
 
 class EncodecHIP:
     """the slice of ``EncodecModel`` generation.py touches: ``.channels``, ``.sample_rate``, ``.quantizer.decode``,
-    ``.decoder``, ``.encode``"""
+    ``.decoder``, ``.encode`` -- and the codec's own way back, which the reference leaves out: ``.decode`` / ``.decode_latents``
+    (per-segment decoder, x scale, linear overlap-add)"""
 
     def __init__(self, decoder: SEANetDecoderHIP, quantizer: ResidualVectorQuantizerHIP, channels: int = 2, sample_rate: int = 48000,
                  encode: Optional[Callable] = None, encoder: Optional["SEANetEncoderHIP"] = None, segment: float = 1.0,
@@ -293,18 +347,27 @@ class EncodecHIP:
         self.decoder_device = decoder.device       # Jen1.generate hands the sampled latents over where they are (no host round trip)
         self.segment_length = int(segment * sample_rate)                                   # encodec model.py segment_length
         self.segment_stride = max(1, int((1 - overlap) * self.segment_length))             # encodec model.py segment_stride
+        # JEN1_ENCODE_BATCHED=0: one encoder pass per segment, scales and cut in torch (the form before the segment kernels; the A/B)
+        self.encode_batched = os.environ.get("JEN1_ENCODE_BATCHED", "1") == "1"
+
+    def segment_frames(self, n_samples: int) -> List[int]:
+        """latent frames per segment for ``n_samples`` of audio: the layout ``encode`` produces and ``decode_latents`` undoes"""
+        return segment_frame_counts(n_samples, self.segment_length, self.segment_stride)
 
     @torch.no_grad()
     def encode(self, audio: torch.Tensor):
         """``EncodecModel.encode`` of the package (model.py): the audio is cut into 1 s segments with 1 % overlap, every
         segment is normalised by the RMS of its mono mix, encoded and quantised with ALL codebooks (the reference never
         sets a target bandwidth) -> ``[(codes [B, n_q, T_seg], scale [B, 1]), ...]``, which is what ``get_emb``
-        concatenates (generation.py:145-150; dataloader.py:106-114)."""
+        concatenates (generation.py:145-150; dataloader.py:106-114).  Segments of equal length share one encoder pass
+        (``_encode_batched``); JEN1_ENCODE_BATCHED=0 keeps one pass per segment."""
         if self._encode is not None:
             return self._encode(audio)
         if self.encoder is None:
             raise NotImplementedError("no encoder: construct EncodecHIP with encoder=SEANetEncoderHIP(...) or encode=<callable>")
         assert audio.dim() == 3 and 0 < audio.shape[1] <= 2
+        if self.encode_batched:
+            return self._encode_batched(audio)
         frames = []
         for offset in range(0, audio.shape[-1], self.segment_stride):
             x = audio[:, :, offset: offset + self.segment_length]
@@ -317,3 +380,108 @@ class EncodecHIP:
             codes = self.quantizer.encode(self.encoder(x), self.n_q).transpose(0, 1)       # [B, n_q, T]
             frames.append((codes, scale))
         return frames
+
+    def segment_scales(self, audio: torch.Tensor) -> torch.Tensor:
+        """audio float32 [B, C, N] on the encoder's device -> the per-segment scale [B, S] (jen1_codec_segment_scales)"""
+        enc = self.encoder
+        B, C, N = audio.shape
+        S = len(segment_lengths(N, self.segment_length, self.segment_stride))
+        scale = torch.empty((B, S), dtype=torch.float32, device=enc.device)
+        L.check(enc.rt.lib.jen1_codec_segment_scales(audio.data_ptr(), scale.data_ptr(), B, C, N, self.segment_length, self.segment_stride, S,
+                                                     enc.rt.stream()), "jen1_codec_segment_scales")
+        return scale
+
+    def segment_rows(self, audio: torch.Tensor, scale: Optional[torch.Tensor], s0: int, n_sel: int, length: int) -> torch.Tensor:
+        """the encoder's input rows [n_sel * B, length, 8] (row j * B + b) of the equal-length segments s0 .. s0 + n_sel - 1, divided by
+        their scales when given (jen1_codec_segment_cut)"""
+        enc = self.encoder
+        B, C, N = audio.shape
+        S = len(segment_lengths(N, self.segment_length, self.segment_stride))
+        rows = torch.empty((n_sel * B, length, pad8(C)), dtype=enc.rt.tdtype, device=enc.device)
+        L.check(enc.rt.lib.jen1_codec_segment_cut(audio.data_ptr(), None if scale is None else scale.data_ptr(), rows.data_ptr(), B, C, N, length,
+                                                  self.segment_stride, S, s0, n_sel, enc.rt.dt_of(rows), enc.rt.stream()), "jen1_codec_segment_cut")
+        return rows
+
+    def _encode_batched(self, audio: torch.Tensor):
+        enc = self.encoder
+        src = audio.device
+        x = audio.to(enc.device, torch.float32).contiguous()
+        B = x.shape[0]
+        scale = self.segment_scales(x) if self.normalize else None
+        per_pass = max(1, enc.lstm_multi_rows() // B)              # more rows would push _lstm off the multi-workgroup kernel
+        frames: List[tuple] = []
+        for s0, count, length in _runs(segment_lengths(x.shape[-1], self.segment_length, self.segment_stride)):
+            for j0 in range(0, count, per_pass):
+                n = min(per_pass, count - j0)
+                emb = enc.from_rows(self.segment_rows(x, scale, s0 + j0, n, length))                    # [n B, 128, T]
+                codes = self.quantizer.encode(emb, self.n_q)                                             # [n_q, n B, T]
+                for j in range(n):
+                    s = s0 + j0 + j
+                    frames.append((codes[:, j * B:(j + 1) * B].transpose(0, 1).to(src), None if scale is None else scale[:, s:s + 1].to(src)))
+        enc._check_lstm()
+        return frames
+
+    # ------------------------------------------------------------------ EncodecModel.decode
+    @torch.no_grad()
+    def decode(self, frames) -> torch.Tensor:
+        """``EncodecModel.decode`` of the package (model.py): ``[(codes [B, n_q, T_s], scale [B, 1] or None), ...]`` -> audio
+        ``[B, channels, stride (S - 1) + 320 T_last]`` on the codes' device: per-frame decoder, x scale, ``_linear_overlap_add``.  One
+        jen1_rvq_decode call looks up the codes of all frames."""
+        assert len(frames) > 0, "no frames"
+        src = frames[0][0].device
+        codes = torch.cat([c.to(self.decoder_device) for c, _ in frames], dim=-1).permute(1, 0, 2)       # [n_q, B, sum T_s]
+        emb = self.quantizer.decode(codes)
+        scales = None
+        if any(s is not None for _, s in frames):
+            B = codes.shape[1]
+            dev = self.decoder_device
+            scales = torch.cat([torch.ones((B, 1), device=dev) if s is None else s.reshape(B, 1).to(dev, torch.float32) for _, s in frames], dim=1)
+        return self.decode_latents(emb, [int(c.shape[-1]) for c, _ in frames], scales).to(src)
+
+    @torch.no_grad()
+    def decode_latents(self, emb: torch.Tensor, segment_frames: Sequence[int], scales: Optional[torch.Tensor] = None,
+                       length: Optional[int] = None) -> torch.Tensor:
+        """the same for continuous latents ``[B, 128, T']`` that hold the segments side by side (what ``get_emb`` builds and the sampler
+        returns): ``segment_frames`` is the frame count of every segment (``segment_frames(n_samples)`` of the encode that defined the
+        layout), ``scales`` ``[B, S]`` or None (unit), ``length`` trims the audio to that many samples.  Segments of equal length go through
+        the decoder together as batch rows (row j B + b), at most as many per pass as keep its LSTM on the multi-workgroup kernel; the
+        overlap-add reads the decoder's final rows in place (jen1_codec_overlap_add)."""
+        dec = self.decoder
+        src = emb.device
+        counts = [int(t) for t in segment_frames]
+        S = len(counts)
+        if emb.dim() != 3 or S == 0 or min(counts) < 1 or sum(counts) != emb.shape[2]:
+            raise ValueError(f"segment_frames {counts} do not add up to the {tuple(emb.shape)} latents")
+        if max(counts) != counts[0]:
+            raise ValueError("the first segment must be the longest (its length defines the overlap-add weights)")
+        B = emb.shape[0]
+        total = self.segment_stride * (S - 1) + HOP_48K * counts[-1]
+        n_out = total if length is None else int(length)
+        if not 1 <= n_out <= total:
+            raise ValueError(f"length={length} is outside what the {S} segments cover ({total} samples)")
+        if any(HOP_48K * t < self.segment_stride for t in counts[:-1]):
+            raise ValueError(f"segment_frames {counts}: a segment before the last is shorter than the stride of {self.segment_stride} samples, "
+                             "which leaves samples no segment covers")
+        if scales is not None and tuple(scales.shape) != (B, S):
+            raise ValueError(f"scales must be [B, S] = {(B, S)}, not {tuple(scales.shape)}")
+        x = emb.to(dec.device, torch.float32)
+        offs = [sum(counts[:s]) for s in range(S)]
+        per_pass = max(1, dec.lstm_multi_rows() // B)
+        by_len: Dict[int, List[int]] = {}
+        for s, t in enumerate(counts):
+            by_len.setdefault(t, []).append(s)
+        table: List[Optional[tuple]] = [None] * S                 # per segment: (the pass's rows, first row, samples)
+        for t, segs in by_len.items():
+            for j0 in range(0, len(segs), per_pass):
+                part = segs[j0:j0 + per_pass]
+                rows = dec.rows(torch.cat([x[:, :, offs[s]:offs[s] + t] for s in part], dim=0))            # [n B, 320 t, 8]
+                for j, s in enumerate(part):
+                    table[s] = (rows, j * B, HOP_48K * t)
+        segs_d = L.ola_seg_table([(r.data_ptr(), r0, n) for r, r0, n in table], dec.device)
+        sc = None if scales is None else scales.to(dec.device, torch.float32).contiguous()
+        out = torch.empty((B, dec.channels, n_out), dtype=torch.float32, device=dec.device)
+        L.check(dec.rt.lib.jen1_codec_overlap_add(segs_d.data_ptr(), S, None if sc is None else sc.data_ptr(), out.data_ptr(), B, dec.channels,
+                                                  table[0][0].shape[-1], n_out, self.segment_stride, HOP_48K * counts[0], HOP_48K * counts[-1],
+                                                  dec.rt.dt_of(table[0][0]), dec.rt.stream()), "jen1_codec_overlap_add")
+        dec._check_lstm()
+        return out.to(src)

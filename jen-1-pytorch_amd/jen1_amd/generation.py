@@ -52,6 +52,22 @@ from .model import UNetCFG1d
 from .tasks import get_conditioning, get_mask
 
 
+def known_segment_scales(scales: torch.Tensor, keep: torch.Tensor, segments: Sequence[Tuple[int, int]]) -> torch.Tensor:
+    """the ``segment_scales="known"`` policy of ``Jen1.generate``: ``scales`` [B, S] are the encoder's per-segment scales of the known
+    audio, ``keep`` the sample mask (1 = kept; [N], or [B, 1, N] as ``get_mask`` returns it, the same for every batch element),
+    ``segments`` the (offset, samples) of every segment.  A segment lying wholly inside the kept region keeps its own scale; every other
+    segment gets the RMS of those scales, ``sqrt(mean(scale^2))`` per batch element, and 1.0 when no segment is wholly kept."""
+    scales = torch.as_tensor(scales, dtype=torch.float32)
+    k = torch.as_tensor(keep).reshape(-1, keep.shape[-1])[0] != 0
+    if scales.dim() != 2 or scales.shape[1] != len(segments):
+        raise ValueError(f"scales {tuple(scales.shape)} do not match the {len(segments)} segments")
+    kept = torch.tensor([bool(n > 0 and k[off:off + n].numel() == n and k[off:off + n].all()) for off, n in segments], device=scales.device)
+    if not bool(kept.any()):
+        return torch.ones_like(scales)
+    fill = scales[:, kept].pow(2).mean(dim=1, keepdim=True).sqrt()
+    return torch.where(kept[None, :], scales, fill.expand_as(scales))
+
+
 class Jen1:
     def __init__(self, ckpt_path: Optional[str], device: str = "cuda", sample_rate: int = 48000,
                  cross_attn_cond_ids: Sequence[str] = ("prompt",), global_cond_ids: Sequence[str] = (),
@@ -151,8 +167,16 @@ class Jen1:
     def generate(self, prompt, seed: int = -1, steps: int = 100, batch_size: int = 1, seconds: int = 30, use_gdm: bool = False,
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
                  inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
-                 preserve_known: bool = False) -> torch.Tensor:
-        """``preserve_known`` (not in the reference): for music_inpaint / music_cont, pin the frames the mask keeps to the latents of
+                 decode: str = "whole", segment_scales: str = "unit", preserve_known: bool = False) -> torch.Tensor:
+        """``decode`` (not in the reference): ``"whole"`` hands all latents to ``audio_encoder.decoder`` in one piece, as generation.py:130
+        does -- the latents hold the encoder's overlapping 1 s segments side by side, so 10 s come back as 1515 x 320 samples with every
+        overlap played twice; ``"segments"`` undoes the encoder's layout with the codec's own decode (``audio_encoder.decode_latents``:
+        per-segment decoder, linear overlap-add) and returns exactly ``seconds * sample_rate`` samples.
+        ``segment_scales`` (not in the reference, nor in the ``encodec`` package; ``decode="segments"`` only): ``"unit"`` decodes every
+        segment at unit RMS, which is what the reference's decoder call amounts to; ``"known"`` gives a segment that lies wholly inside the
+        kept region of the known audio the scale its encoder measured, and every other segment the RMS of those scales
+        (``known_segment_scales``), so kept audio comes back at its own level.
+        ``preserve_known`` (not in the reference): for music_inpaint / music_cont, pin the frames the mask keeps to the latents of
         the given audio (the samplers' ``known`` / ``keep_mask``) instead of regenerating them from the conditioning alone.
         ``sampler="dpmpp2m"`` (not in the reference; ``use_gdm=True`` only): DPM-Solver++(2M) over ``steps`` network evaluations,
         ``GaussianDiffusion.dpm_sample``; None keeps the reference's samplers.
@@ -166,6 +190,16 @@ class Jen1:
             raise ValueError("sampler='dpmpp2m' needs use_gdm=True: there is no multistep solver for the variational diffusion model")
         if preserve_known and task == "text_guided":
             raise ValueError("preserve_known needs known audio: task 'music_inpaint' or 'music_cont'")
+        if decode not in ("whole", "segments"):
+            raise ValueError(f"unknown decode {decode!r}: 'whole' or 'segments'")
+        if segment_scales not in ("unit", "known"):
+            raise ValueError(f"unknown segment_scales {segment_scales!r}: 'unit' or 'known'")
+        if segment_scales == "known" and decode != "segments":
+            raise ValueError("segment_scales='known' needs decode='segments': the whole-latent decoder call has no per-segment scale")
+        if segment_scales == "known" and task == "text_guided":
+            raise ValueError("segment_scales='known' needs known audio: task 'music_inpaint' or 'music_cont'")
+        if decode == "segments" and not hasattr(self.audio_encoder, "decode_latents"):
+            raise ValueError("decode='segments' needs an audio_encoder with decode_latents (jen1_amd.encodec.EncodecHIP)")
         torch.manual_seed(seed if seed != -1 else int(np.random.randint(0, 2 ** 32 - 1)))
         self.batch_size = batch_size
         diffusion, model = self.get_model_and_diffusion(steps, use_gdm)
@@ -174,7 +208,7 @@ class Jen1:
         start_s, end_s, causal = self._task_window(task, seconds, inpainting_scope, prefix)
         keep = self.get_mask(total, start_s, end_s, batch_size)                 # 1 = keep the known audio, 0 = generate
         out = self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
-                           preserve_known=preserve_known, sampler=sampler)
+                           preserve_known=preserve_known, sampler=sampler, decode=decode, segment_scales=segment_scales, length=total)
         if output_sr is not None and int(output_sr) != self.sample_rate:
             from . import audio
             # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
@@ -183,9 +217,15 @@ class Jen1:
 
     @torch.no_grad()
     def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
-                steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None) -> torch.Tensor:
+                steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None, decode: str = "whole",
+                segment_scales: str = "unit", length: Optional[int] = None) -> torch.Tensor:
         B = wav.shape[0]
-        known = self.get_emb(wav.to(self.device)).to(self.device)               # [B, 128, T']
+        keep_samples = keep
+        if decode == "segments":
+            known, seg_frames, enc_scales = self.get_emb_segments(wav.to(self.device))
+            known = known.to(self.device)
+        else:
+            known = self.get_emb(wav.to(self.device)).to(self.device)           # [B, 128, T']
         keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
         cond = self.conditioner([{"prompt": prompt}] * B, self.device)
         cond["masked_input"] = known * keep
@@ -199,6 +239,16 @@ class Jen1:
         z = diffusion.sample(model, tuple(known.shape), cond, causal=causal, init_data=known if seed_with_audio else None, **extra)
         # the reference hands the latents to its CPU decoder (generation.py:129-130); a decoder that lives on a device says so
         # (EncodecHIP.decoder_device) and gets them where they are
+        if decode == "segments":
+            scales = None
+            if segment_scales == "known":
+                if enc_scales is None:
+                    raise ValueError("segment_scales='known': the audio_encoder's encode returned no scales (normalize=False)")
+                ae = self.audio_encoder
+                offs = range(0, wav.shape[-1], ae.segment_stride)
+                scales = known_segment_scales(enc_scales, keep_samples, [(o, min(ae.segment_length, wav.shape[-1] - o)) for o in offs])
+            return self.audio_encoder.decode_latents(z.to(getattr(self.audio_encoder, "decoder_device", "cpu")), seg_frames, scales=scales,
+                                                     length=wav.shape[-1] if length is None else min(length, wav.shape[-1]))
         return self.audio_encoder.decoder(z.to(getattr(self.audio_encoder, "decoder_device", "cpu")))
 
     # generation.py:134-150
@@ -210,6 +260,16 @@ class Jen1:
         codebook vectors (generation.py:145-150)"""
         per_segment = [codes for codes, _scale in self.audio_encoder.encode(audio)]          # each [B, n_q, T_seg]
         return self.audio_encoder.quantizer.decode(torch.cat(per_segment, dim=-1).permute(1, 0, 2))
+
+    def get_emb_segments(self, audio: torch.Tensor):
+        """``get_emb`` together with the layout it came from: (latents [B, 128, T'], the frame count of every segment, the encoder's
+        per-segment scales [B, S] or None) -- what ``decode_latents`` needs to undo the segmentation"""
+        frames = self.audio_encoder.encode(audio)
+        emb = self.audio_encoder.quantizer.decode(torch.cat([codes for codes, _ in frames], dim=-1).permute(1, 0, 2))
+        scales = None
+        if all(s is not None for _, s in frames):
+            scales = torch.cat([s.reshape(-1, 1).to(torch.float32) for _, s in frames], dim=1)
+        return emb, [int(codes.shape[-1]) for codes, _ in frames], scales
 
     # generation.py:152-192
     def get_conditioning(self, cond):

@@ -126,6 +126,11 @@ class KvLayer(C.Structure):
                 ("n0", c_int), ("N", c_int)]
 
 
+class OlaSeg(C.Structure):
+    """mirror of ``jen1_ola_seg`` (include/jen1_train.h): one frame of the overlap-add"""
+    _fields_ = [("rows", c_void_p), ("row0", c_int), ("len", c_int)]
+
+
 # every symbol include/jen1_hip.h and include/jen1_train.h declare: (name, restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -214,6 +219,10 @@ SYMBOLS = {
     "jen1_rvq_decode": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P]),
     "jen1_lstm_layer": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "jen1_lstm_layer_multi": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "jen1_codec_segment_scales": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, c_int, c_int, _P]),
+    "jen1_codec_segment_cut": (c_int, [_P, _P, _P, c_int, c_int, c_int64] + [c_int] * 6 + [_P]),
+    "jen1_codec_pad1d": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
+    "jen1_codec_overlap_add": (c_int, [_P, c_int, _P, _P] + [c_int] * 8 + [_P]),
     # include/jen1_deep.h: the persistent deep-level kernel (phase descriptors are opaque bytes on this side)
     "jen1_deep_phase_size": (c_int, []),
     "jen1_deep_has_chunks": (c_int, []),
@@ -334,6 +343,16 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().jen1_last_error()
         raise Jen1HipError(f"{what}: {msg.decode() if msg else 'unknown error'}")
+
+
+def ola_seg_table(segs, device):
+    """device copy of a ``jen1_ola_seg`` table: ``segs`` = [(rows_ptr, row0, len)]"""
+    import numpy as np
+    import torch
+    arr = (OlaSeg * len(segs))()
+    for i, (rows, row0, n) in enumerate(segs):
+        arr[i].rows, arr[i].row0, arr[i].len = rows, row0, n
+    return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
 
 
 def bgemm_group_table(groups, device):
