@@ -84,7 +84,13 @@ int jen1_train_gemm_pair(const jen1_gemm_args* first, const jen1_gemm_args* seco
 
 /* --- GroupNorm (+FiLM) (+SiLU): ConvBlock1d's prologue, blocks.py:137-143; Transformer1d's GroupNorm, :509 ---
  * sums[B][G][2] float32 = (sum x, sum x^2) over the group (zeroed by the call).  film: [B][film_ld] float32 or bf16
- * (same dtype as x) holding scale at [c] and shift at [C + c], or NULL.  flags bit0: SiLU. */
+ * (same dtype as x) holding scale at [c] and shift at [C + c], or NULL.  flags bit0: SiLU.
+ * Accuracy: the variance is sums[1] / n - (sums[0] / n)^2 from float32 sums.  Measured against float64 on MI355X
+ * (profiles/train_ops_parity.txt): for groups with |mean| <= std / 2 every kernel form keeps outputs and gradients within 4 x the
+ * error of a two-pass float32 computation; with |mean| = std the scalar form exceeded that by 1.5 - 2.5 x (dx; cause not
+ * isolated), with |mean| = 4 - 8 std every form did (up to 4 x, parameter gradients; the figures move between runs with the order
+ * of the float atomics).  Whether the model's activations stay inside that range has not been measured; the whole-model gradient
+ * goldens (tests/test_gpu_train.py) pass at 1e-3. */
 int jen1_gn_sums(const void* x, float* sums, int B, int L, int C, int ld, int groups, int dtype, void* stream);
 int jen1_gn_apply(const void* x, const float* sums, const float* gamma, const float* beta, const void* film, int film_ld,
                   void* y, int B, int L, int C, int ld, int groups, float eps, int flags, int dtype, void* stream);
@@ -143,6 +149,39 @@ int jen1_act_backward(const void* dy, const void* x, void* dx, int64_t n, int mo
  * backward: ds = p * (dp - sum_j dp*p), dp float32 [Z][Nq][ld_s], ds (dtype) [Z][Nq][ld_p]. */
 int jen1_softmax_forward(const float* s, void* p, int rows, int Nq, int Nk, int ld_s, int ld_p, int causal, int dtype, void* stream);
 int jen1_softmax_backward(const void* p, const float* dp, void* ds, int rows, int Nk, int ld_s, int ld_p, int dtype, void* stream);
+
+/* --- which kernel a call of the entry points above runs.  Each of them chooses at run time by shape, padding and pointer alignment
+ * (GroupNorm also by the environment variable JEN1_GN_FUSED: 0 switches the one-launch forms off); these host-only functions are the
+ * very functions the entry points switch on.  They take the pointers and the shape of the call, launch nothing and need no GPU.
+ * -1: a shape the entry point rejects. */
+enum {
+  JEN1_FORM_SCALAR = 0,      /* one element per thread and access: padded rows, odd channel counts, pointers off a 16-byte boundary */
+  JEN1_FORM_VECTOR = 1,      /* 8 channels per thread and access */
+  JEN1_FORM_FUSED256 = 2,    /* GroupNorm: one launch, a 256-thread workgroup per (batch element, group) */
+  JEN1_FORM_FUSED1024 = 3    /* ... of 1024 threads: groups of at least 12 000 elements */
+};
+enum {                       /* jen1_ln_backward(_add) */
+  JEN1_LN_BWD_SCALAR256 = 0,
+  JEN1_LN_BWD_SCALAR512 = 1, /* at least 512 rows */
+  JEN1_LN_BWD_VECTOR256 = 2,
+  JEN1_LN_BWD_VECTOR512 = 3  /* at least 256 rows */
+};
+int jen1_gn_sums_form(const void* x, int B, int L, int C, int ld, int groups);                           /* SCALAR | VECTOR */
+int jen1_gn_apply_form(const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* y, int B, int L,
+                       int C, int ld, int groups);                                                       /* SCALAR | VECTOR */
+/* FUSED256 | FUSED1024, or the form of the jen1_gn_apply of the two calls (the jen1_gn_sums before it: jen1_gn_sums_form).  The
+ * one-launch forms take groups of up to 1024 channels; the tests run them up to 128. */
+int jen1_gn_forward_form(const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* y, int B, int L,
+                         int C, int ld, int groups);
+/* FUSED256 | FUSED1024, or the form of the dx kernel of the three launches (per-channel sums, finish, dx).  A one-launch form whose
+ * dynamic LDS would not fit what its launch may use (groups of 2048 channels) answers with the three launches. */
+int jen1_gn_backward_form(const void* dy, const void* x, const float* gamma, const float* beta, const void* film, int film_ld,
+                          const void* dx, int B, int L, int C, int ld, int groups);
+int jen1_ln_forward_form(const void* x, const float* gamma, const float* beta, const void* y, int rows, int C, int ld);   /* SCALAR | VECTOR */
+int jen1_ln_backward_form(const void* dy, const void* x, const float* gamma, const void* dx, const void* dx_add, int rows, int C,
+                          int ld);                                                                       /* JEN1_LN_BWD_* */
+/* jen1_act_forward(a = x, b = y, c = NULL) and jen1_act_backward(a = dy, b = x, c = dx): SCALAR | VECTOR */
+int jen1_act_form(const void* a, const void* b, const void* c, int64_t n);
 
 /* --- the whole attention core (AttentionBase.forward, math path, blocks.py:355-380) of SHORT sequences in one launch each way: one
  * workgroup per (batch element, head) keeps Q, K, V (and dO) in LDS -- the transformer blocks of JEN-1 sit where a 1500-frame clip

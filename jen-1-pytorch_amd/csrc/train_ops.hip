@@ -1211,7 +1211,108 @@ int gn_fill(GnDev& g, const char* who, const void* x, const float* sums, const f
   return 0;
 }
 
+// ---------------------------------------------------------------- which kernel a call runs (jen1_*_form of include/jen1_train.h): every
+// entry point below switches on the answer of one of these host functions, so the query and the launch cannot disagree
+constexpr long long GN_LONG_GROUP = 12000;       // elements per (batch element, group) from which the 1024-thread form runs
+constexpr size_t lds_cap = 160 * 1024;           // what JEN1_MAX_LDS_ONCE asks for the 1024-thread backward
+constexpr size_t lds_default = 64 * 1024;        // dynamic LDS of a launch without that attribute
+
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool gn_shape_ok(int B, int L, int C, int ld, int groups) { return B >= 1 && L >= 1 && C >= 1 && ld >= C && groups >= 1 && C % groups == 0; }
+
+int gn_sums_form(const void* x, int C, int ld, int groups) {
+  return vec_ok(x, nullptr, nullptr, C, ld, C / groups) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
+}
+
+// the 8-wide apply / dx kernels: p1, p2 are the other tensors of x's layout
+int gn_ew_form(const void* x, const void* p1, const void* p2, const float* gamma, const float* beta, const void* film, int film_ld, int C,
+               int ld, int groups) {
+  const bool film_ok = film == nullptr || ((film_ld & 7) == 0 && al16(film));
+  return film_ok && vec_ok(x, p1, p2, C, ld, C / groups) && al16(gamma) && al16(beta) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
+}
+
+// the one-launch form: vector-aligned rows, a power-of-two number of 8-channel vectors per group, enough (batch element, group) pairs
+// to fill the chip reasonably and a group small enough for one workgroup
+bool gn_fused_ok(const void* x, const void* y, const void* dy, const float* gamma, const float* beta, const void* film, int film_ld, int B, int L,
+                 int C, int ld, int groups, int& lvpg) {
+  const int cpg = C / groups;
+  if (!vec_ok(x, y, dy, C, ld, cpg) || !al16(gamma) || !al16(beta)) return false;
+  if (film != nullptr && ((film_ld & 7) != 0 || !al16(film))) return false;
+  const int vpg = cpg / 8;
+  if ((vpg & (vpg - 1)) != 0 || vpg > NT / 2) return false;      // (2048 channels: the backward's LDS does not fit, and no test runs it)
+  lvpg = 0;
+  while ((1 << lvpg) < vpg) ++lvpg;
+  if (getenv("JEN1_GN_FUSED") && atoi(getenv("JEN1_GN_FUSED")) == 0) return false;
+  return B * groups >= 32 && (long long)L * cpg <= (1 << 17);
+}
+
+int gn_forward_form(const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* y, int B, int L, int C,
+                    int ld, int groups, int& lvpg) {
+  if (gn_fused_ok(x, y, nullptr, gamma, beta, film, film_ld, B, L, C, ld, groups, lvpg))
+    return (long long)L * (C / groups) >= GN_LONG_GROUP ? JEN1_FORM_FUSED1024 : JEN1_FORM_FUSED256;
+  return gn_ew_form(x, y, nullptr, gamma, beta, film, film_ld, C, ld, groups);
+}
+
+// dynamic LDS of gn_bwd_fused_kernel<T, ntb>: [ntb][32] per-thread partials | [cpg][4] | [ntb / 64] | [ntb] chunk sums
+size_t gn_bwd_fused_lds(int ntb, int cpg) { return ((size_t)ntb * 32 + (size_t)cpg * 4 + ntb / 64 + ntb) * sizeof(float); }
+
+int gn_backward_form(const void* dy, const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* dx,
+                     int B, int L, int C, int ld, int groups, int& lvpg) {
+  if (gn_fused_ok(x, dx, dy, gamma, beta, film, film_ld, B, L, C, ld, groups, lvpg)) {
+    const bool big = (long long)L * (C / groups) >= GN_LONG_GROUP;
+    // (groups of 2048 channels: 66 576 bytes with 256 threads, 168 000 with 1024 -- more than the launch may ask for)
+    if (gn_bwd_fused_lds(big ? 1024 : 256, C / groups) <= (big ? lds_cap : lds_default)) return big ? JEN1_FORM_FUSED1024 : JEN1_FORM_FUSED256;
+  }
+  return gn_ew_form(x, dy, dx, gamma, beta, film, film_ld, C, ld, groups);
+}
+
+bool ln_shape_ok(int rows, int C, int ld) { return rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL; }
+
+int ln_forward_form(const void* x, const float* gamma, const float* beta, const void* y, int C, int ld) {
+  return (C & 7) == 0 && (ld & 7) == 0 && C <= 2048 && al16(x) && al16(y) && al16(gamma) && al16(beta) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
+}
+
+// many rows (the text context: 2B x 129): 8 waves per block meet in LDS, so 32 blocks x 2 C atomics finish the column sums
+// (the atomics of hundreds of waves on 2 C addresses were the kernel's time: 26 us at 2 064 x 1 024); 16 waves per block would
+// leave 128 registers per lane and push the per-lane column sums into scratch
+int ln_backward_form(const void* dy, const void* x, const float* gamma, const void* dx, const void* dx_add, int rows, int C, int ld) {
+  const bool lds8 = (size_t)7 * 2 * C * sizeof(float) <= lds_default;       // the column sums of 7 waves fit
+  if ((C & 7) == 0 && (ld & 7) == 0 && C <= 512 * LN_MAXV && al16(dy) && al16(x) && al16(dx) && al16(dx_add) && al16(gamma) && lds8)
+    return rows >= 256 ? JEN1_LN_BWD_VECTOR512 : JEN1_LN_BWD_VECTOR256;     // 8 waves per block when there are rows for them, else 4
+  return rows >= 512 && lds8 ? JEN1_LN_BWD_SCALAR512 : JEN1_LN_BWD_SCALAR256;
+}
+
+int act_form(const void* a, const void* b, const void* c, long long n) {
+  return (n & 7) == 0 && al16(a) && al16(b) && al16(c) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
+}
+
 }  // namespace
+
+extern "C" int jen1_gn_sums_form(const void* x, int B, int L, int C, int ld, int groups) {
+  return gn_shape_ok(B, L, C, ld, groups) ? gn_sums_form(x, C, ld, groups) : -1;
+}
+extern "C" int jen1_gn_apply_form(const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* y, int B,
+                                  int L, int C, int ld, int groups) {
+  return gn_shape_ok(B, L, C, ld, groups) ? gn_ew_form(x, y, nullptr, gamma, beta, film, film_ld, C, ld, groups) : -1;
+}
+extern "C" int jen1_gn_forward_form(const void* x, const float* gamma, const float* beta, const void* film, int film_ld, const void* y, int B,
+                                    int L, int C, int ld, int groups) {
+  int lvpg = 0;
+  return gn_shape_ok(B, L, C, ld, groups) ? gn_forward_form(x, gamma, beta, film, film_ld, y, B, L, C, ld, groups, lvpg) : -1;
+}
+extern "C" int jen1_gn_backward_form(const void* dy, const void* x, const float* gamma, const float* beta, const void* film, int film_ld,
+                                     const void* dx, int B, int L, int C, int ld, int groups) {
+  int lvpg = 0;
+  return gn_shape_ok(B, L, C, ld, groups) ? gn_backward_form(dy, x, gamma, beta, film, film_ld, dx, B, L, C, ld, groups, lvpg) : -1;
+}
+extern "C" int jen1_ln_forward_form(const void* x, const float* gamma, const float* beta, const void* y, int rows, int C, int ld) {
+  return ln_shape_ok(rows, C, ld) ? ln_forward_form(x, gamma, beta, y, C, ld) : -1;
+}
+extern "C" int jen1_ln_backward_form(const void* dy, const void* x, const float* gamma, const void* dx, const void* dx_add, int rows, int C,
+                                     int ld) {
+  return ln_shape_ok(rows, C, ld) ? ln_backward_form(dy, x, gamma, dx, dx_add, rows, C, ld) : -1;
+}
+extern "C" int jen1_act_form(const void* a, const void* b, const void* c, int64_t n) { return n >= 1 ? act_form(a, b, c, n) : -1; }
 
 extern "C" int jen1_gn_sums(const void* x, float* sums, int B, int L, int C, int ld, int groups, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_gn_sums")) return 1;
@@ -1221,7 +1322,7 @@ extern "C" int jen1_gn_sums(const void* x, float* sums, int B, int L, int C, int
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (zero2(sums, 2 * B * groups, nullptr, 0, s)) return 1;
   int CT, rpb, gx, gy;
-  if (vec_ok(x, nullptr, nullptr, C, ld, C / groups)) {
+  if (gn_sums_form(x, C, ld, groups) == JEN1_FORM_VECTOR) {
     red_geom(C / 8, L, CT, rpb, gx, gy);
     DISPATCH(dtype, gn_sums_vec_kernel, dim3(gx, gy, B), x, sums, L, C, groups, C / groups, CT, rpb);
     return 0;
@@ -1231,26 +1332,6 @@ extern "C" int jen1_gn_sums(const void* x, float* sums, int B, int L, int C, int
   return 0;
 }
 
-namespace {
-// the one-launch form: vector-aligned rows, a power-of-two number of 8-channel vectors per group, enough (batch element, group) pairs
-// to fill the chip reasonably and a group small enough for one workgroup
-constexpr long long GN_LONG_GROUP = 12000;       // elements per (batch element, group) from which the 1024-thread form runs
-constexpr size_t lds_cap = 160 * 1024;
-
-bool gn_fused_ok(const void* x, const void* y, const void* dy, const float* gamma, const float* beta, const void* film, int film_ld, int B, int L,
-                 int C, int ld, int groups, int& lvpg) {
-  const int cpg = C / groups;
-  if (!vec_ok(x, y, dy, C, ld, cpg) || ((((uintptr_t)gamma | (uintptr_t)beta) & 15) != 0)) return false;
-  if (film != nullptr && ((film_ld & 7) != 0 || ((uintptr_t)film & 15) != 0)) return false;
-  const int vpg = cpg / 8;
-  if ((vpg & (vpg - 1)) != 0 || vpg > NT) return false;
-  lvpg = 0;
-  while ((1 << lvpg) < vpg) ++lvpg;
-  if (getenv("JEN1_GN_FUSED") && atoi(getenv("JEN1_GN_FUSED")) == 0) return false;
-  return B * groups >= 32 && (long long)L * cpg <= (1 << 17);
-}
-}  // namespace
-
 extern "C" int jen1_gn_forward(const void* x, float* sums, const float* gamma, const float* beta, const void* film, int film_ld, void* y, int B,
                                int L, int C, int ld, int groups, float eps, int flags, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_gn_forward")) return 1;
@@ -1258,13 +1339,14 @@ extern "C" int jen1_gn_forward(const void* x, float* sums, const float* gamma, c
   if (gn_fill(g, "jen1_gn_forward", x, sums, gamma, beta, film, film_ld, B, L, C, ld, groups, eps, flags)) return 1;
   JEN1_CHECK(y != nullptr, "jen1_gn_forward: y is NULL");
   int lvpg = 0;
-  if (!gn_fused_ok(x, y, nullptr, gamma, beta, film, film_ld, B, L, C, ld, groups, lvpg)) {
+  const int form = gn_forward_form(x, gamma, beta, film, film_ld, y, B, L, C, ld, groups, lvpg);
+  if (form != JEN1_FORM_FUSED256 && form != JEN1_FORM_FUSED1024) {
     if (jen1_gn_sums(x, sums, B, L, C, ld, groups, dtype, stream)) return 1;
     return jen1_gn_apply(x, sums, gamma, beta, film, film_ld, y, B, L, C, ld, groups, eps, flags, dtype, stream);
   }
   g.y = y;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if ((long long)L * (C / groups) >= GN_LONG_GROUP) {
+  if (form == JEN1_FORM_FUSED1024) {
     if (dtype == JEN1_F32) hipLaunchKernelGGL((gn_fwd_fused_kernel<float, 1024>), dim3(B * groups), dim3(1024), 0, s, g, sums, lvpg);
     else hipLaunchKernelGGL((gn_fwd_fused_kernel<bf16_t, 1024>), dim3(B * groups), dim3(1024), 0, s, g, sums, lvpg);
   } else {
@@ -1283,8 +1365,7 @@ extern "C" int jen1_gn_apply(const void* x, const float* sums, const float* gamm
   JEN1_CHECK(y != nullptr, "jen1_gn_apply: y is NULL");
   g.y = y;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool film_ok = film == nullptr || ((film_ld & 7) == 0 && ((uintptr_t)film & 15) == 0);
-  if (film_ok && vec_ok(x, y, nullptr, C, ld, C / groups) && (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) {
+  if (gn_ew_form(x, y, nullptr, gamma, beta, film, film_ld, C, ld, groups) == JEN1_FORM_VECTOR) {
     DISPATCH(dtype, gn_apply_vec_kernel, dim3(ew_grid((long long)B * L * C / 8)), g);
     return 0;
   }
@@ -1323,9 +1404,10 @@ extern "C" int jen1_gn_backward_add2(const void* dy, const void* x, const float*
   g.film_bf16 = dtype == JEN1_BF16 ? 1 : 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int lvpg = 0;
-  if (gn_fused_ok(x, dx, dy, gamma, beta, film, film_ld, B, L, C, ld, groups, lvpg)) {
-    if ((long long)L * (C / groups) >= GN_LONG_GROUP) {
-      const size_t lds = ((size_t)1024 * 32 + (size_t)(C / groups) * 4 + 16 + 1024) * sizeof(float);
+  const int form = gn_backward_form(dy, x, gamma, beta, film, film_ld, dx, B, L, C, ld, groups, lvpg);
+  if (form == JEN1_FORM_FUSED256 || form == JEN1_FORM_FUSED1024) {
+    if (form == JEN1_FORM_FUSED1024) {
+      const size_t lds = gn_bwd_fused_lds(1024, C / groups);
       if (dtype == JEN1_F32) {
         JEN1_MAX_LDS_ONCE((gn_bwd_fused_kernel<float, 1024>), (int)lds_cap);
         hipLaunchKernelGGL((gn_bwd_fused_kernel<float, 1024>), dim3(B * groups), dim3(1024), lds, s, g, dx, lvpg);
@@ -1334,7 +1416,7 @@ extern "C" int jen1_gn_backward_add2(const void* dy, const void* x, const float*
         hipLaunchKernelGGL((gn_bwd_fused_kernel<bf16_t, 1024>), dim3(B * groups), dim3(1024), lds, s, g, dx, lvpg);
       }
     } else {
-      const size_t lds = ((size_t)256 * 32 + (size_t)(C / groups) * 4 + 4 + 256) * sizeof(float);
+      const size_t lds = gn_bwd_fused_lds(256, C / groups);
       if (dtype == JEN1_F32) hipLaunchKernelGGL((gn_bwd_fused_kernel<float, 256>), dim3(B * groups), dim3(256), lds, s, g, dx, lvpg);
       else hipLaunchKernelGGL((gn_bwd_fused_kernel<bf16_t, 256>), dim3(B * groups), dim3(256), lds, s, g, dx, lvpg);
     }
@@ -1347,8 +1429,7 @@ extern "C" int jen1_gn_backward_add2(const void* dy, const void* x, const float*
   DISPATCH(dtype, gn_bwd_sums_kernel, dim3(gx, gy, B), g, CT, rpb);
   hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3(B * groups + (C + 63) / 64), dim3(64), 0, s, g);
   JEN1_HIP(hipGetLastError());
-  const bool film_ok = film == nullptr || ((film_ld & 7) == 0 && ((uintptr_t)film & 15) == 0);
-  if (film_ok && vec_ok(x, dy, dx, C, ld, C / groups) && (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) {
+  if (form == JEN1_FORM_VECTOR) {
     DISPATCH(dtype, gn_bwd_dx_vec_kernel, dim3(ew_grid((long long)B * L * C / 8)), g, dx);
     return 0;
   }
@@ -1362,7 +1443,7 @@ extern "C" int jen1_ln_forward(const void* x, const float* gamma, const float* b
   JEN1_CHECK(x && gamma && beta && y && stats, "jen1_ln_forward: NULL argument");
   JEN1_CHECK(rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL, "jen1_ln_forward: bad shape rows=%d C=%d ld=%d (C <= %d)", rows, C, ld, 64 * LN_MAXPL);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if ((C & 7) == 0 && (ld & 7) == 0 && C <= 2048 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) {
+  if (ln_forward_form(x, gamma, beta, y, C, ld) == JEN1_FORM_VECTOR) {
     DISPATCH(dtype, ln_fwd_vec_kernel, dim3((rows + 3) / 4), x, gamma, beta, y, stats, rows, C, ld, eps);
     return 0;
   }
@@ -1382,13 +1463,10 @@ extern "C" int jen1_ln_backward_add(const void* dy, const void* x, const float* 
   JEN1_CHECK(dx != nullptr || dx_add == nullptr, "jen1_ln_backward_add: dx_add without dx");
   JEN1_CHECK(rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL, "jen1_ln_backward: bad shape rows=%d C=%d ld=%d", rows, C, ld);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // many rows (the text context: 2B x 129): 8 waves per block meet in LDS, so 32 blocks x 2 C atomics finish the column sums
-  // (the atomics of hundreds of waves on 2 C addresses were the kernel's time: 26 us at 2 064 x 1 024); 16 waves per block would
-  // leave 128 registers per lane and push the per-lane column sums into scratch
-  if ((C & 7) == 0 && (ld & 7) == 0 && C <= 512 * LN_MAXV && (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dx_add | (uintptr_t)gamma) & 15) == 0 &&
-      (size_t)7 * 2 * C * sizeof(float) <= 64 * 1024) {
-    // 8 waves per block when there are rows for them, else 4; at most 32 blocks: each wave keeps its column sums over many rows
-    const bool big8 = rows >= 256;
+  const int form = ln_backward_form(dy, x, gamma, dx, dx_add, rows, C, ld);
+  if (form == JEN1_LN_BWD_VECTOR512 || form == JEN1_LN_BWD_VECTOR256) {
+    // at most 32 blocks: each wave keeps its column sums over many rows
+    const bool big8 = form == JEN1_LN_BWD_VECTOR512;
     const int wpb = big8 ? 8 : 4;
     int blocks = (rows + wpb - 1) / wpb;
     if (blocks > 32) blocks = 32;
@@ -1403,8 +1481,7 @@ extern "C" int jen1_ln_backward_add(const void* dy, const void* x, const float* 
     JEN1_HIP(hipGetLastError());
     return 0;
   }
-  const bool big = rows >= 512 && (size_t)7 * 2 * C * sizeof(float) <= 64 * 1024;
-  if (big) {
+  if (form == JEN1_LN_BWD_SCALAR512) {
     int blocks = (rows + 31) / 32;
     if (blocks > 32) blocks = 32;
     const size_t lds = (size_t)7 * 2 * C * sizeof(float);
@@ -1458,7 +1535,7 @@ extern "C" int jen1_act_forward(const void* x, void* y, int64_t n, int mode, int
   if (check_dtype(dtype, "jen1_act_forward")) return 1;
   JEN1_CHECK(x && y && n >= 1 && mode >= 0 && mode <= 2, "jen1_act_forward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if ((n & 7) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
+  if (act_form(x, y, nullptr, n) == JEN1_FORM_VECTOR) {
     DISPATCH(dtype, act_fwd_vec_kernel, dim3(ew_grid(n / 8)), x, y, (long long)(n / 8), mode);
     return 0;
   }
@@ -1470,7 +1547,7 @@ extern "C" int jen1_act_backward(const void* dy, const void* x, void* dx, int64_
   if (check_dtype(dtype, "jen1_act_backward")) return 1;
   JEN1_CHECK(dy && x && dx && n >= 1 && mode >= 0 && mode <= 2, "jen1_act_backward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if ((n & 7) == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0) {
+  if (act_form(dy, x, dx, n) == JEN1_FORM_VECTOR) {
     DISPATCH(dtype, act_bwd_vec_kernel, dim3(ew_grid(n / 8)), dy, x, dx, (long long)(n / 8), mode);
     return 0;
   }

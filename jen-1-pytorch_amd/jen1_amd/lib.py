@@ -27,6 +27,8 @@ ACT_NONE, ACT_GELU = 0, 1
 CFG_W64x64, CFG_W128x64, CFG_S16x64, CFG_S16x32, CFG_S16x16 = 0, 1, 2, 3, 4
 CFG_T128x64, CFG_T128x32, CFG_T128x16, CFG_T256x32, CFG_T256x16, CFG_T64x64 = 5, 6, 7, 8, 9, 10
 T5_ACT_GELU_NEW, T5_ACT_RELU, T5_MAX_TOKENS = 0, 1, 128      # include/jen1_t5.h
+FORM_SCALAR, FORM_VECTOR, FORM_FUSED256, FORM_FUSED1024 = 0, 1, 2, 3                 # include/jen1_train.h: the jen1_*_form queries
+LN_BWD_SCALAR256, LN_BWD_SCALAR512, LN_BWD_VECTOR256, LN_BWD_VECTOR512 = 0, 1, 2, 3
 
 c_void_p, c_int, c_float, c_int64 = C.c_void_p, C.c_int32, C.c_float, C.c_int64
 
@@ -213,6 +215,14 @@ SYMBOLS = {
     "jen1_act_backward": (c_int, [_P, _P, _P, c_int64, c_int, c_int, _P]),
     "jen1_softmax_forward": (c_int, [_P, _P] + [c_int] * 7 + [_P]),
     "jen1_softmax_backward": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P]),
+    # which kernel form a call would run (host only, no launch): the enums of include/jen1_train.h
+    "jen1_gn_sums_form": (c_int, [_P] + [c_int] * 5),
+    "jen1_gn_apply_form": (c_int, [_P, _P, _P, _P, c_int, _P] + [c_int] * 5),
+    "jen1_gn_forward_form": (c_int, [_P, _P, _P, _P, c_int, _P] + [c_int] * 5),
+    "jen1_gn_backward_form": (c_int, [_P, _P, _P, _P, _P, c_int, _P] + [c_int] * 5),
+    "jen1_ln_forward_form": (c_int, [_P] * 4 + [c_int] * 3),
+    "jen1_ln_backward_form": (c_int, [_P] * 5 + [c_int] * 3),
+    "jen1_act_form": (c_int, [_P, _P, _P, c_int64]),
     "jen1_colsum": (c_int, [_P, _P] + [c_int] * 4 + [_P]),
     "jen1_convert_clear": (c_int, [_P, _P, c_int64, c_int, _P]),
     "jen1_convert_clear_add": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
