@@ -230,6 +230,18 @@ int jen1_convert_clear_add(float* src, void* dst, const void* res, int64_t n, in
 int jen1_rvq_decode(const int64_t* codes, const float* tables, float* out, int n_q, int B, int T, int bins, int D, void* stream);
 int jen1_lstm_layer(const float* gin, const void* whh_t, const void* skip, void* y, int B, int T, int H, int ld_y, int dtype,
                     void* stream);
+/* jen1_rvq_encode: ResidualVectorQuantization.encode followed by decode (core_vq.py), the whole residual search in one launch.
+ *   Per frame, for q = 0 .. n_q - 1: idx_q = argmax_j (2 r.e_j - e_sq[q][j]) (exact float32 dot products on the f32-input matrix
+ *   instructions; on exact ties the LOWEST index wins), r = r - e_idx (a plain float32 subtract).  The latents are 0 + e_idx0 + e_idx1 +
+ *   ... in float32, bit-identical to jen1_rvq_decode of the codes.  A frame's result does not depend on the launch shape.
+ *   emb float32 [rows][D][T] (what the SEANet encoder returns), tables float32 [n_q][bins][D], e_sq float32 [n_q][bins] = sum_d e^2.
+ *   Input row r is batch row b = r % B_out of segment j = r / B_out (the row order of jen1_codec_segment_cut):
+ *     codes   int64   [n_q][B_out][codes_T]: codes[(q B_out + b) codes_T + codes_t0 + j T + t]
+ *     latents float32 [B_out][D][lat_T]:     latents[(b D + d) lat_T + lat_t0 + j T + t]
+ *   so the equal-length segments of one encoder pass land side by side in time.  Either output may be NULL, not both.
+ *   D == 128; bins a multiple of 64 in [64, 2048]; n_q <= 32; rows % B_out == 0; t0 + (rows / B_out) T <= the output's T. */
+int jen1_rvq_encode(const float* emb, const float* tables, const float* e_sq, int64_t* codes, float* latents, int n_q, int rows, int T,
+                    int bins, int D, int B_out, int64_t codes_T, int64_t codes_t0, int64_t lat_T, int64_t lat_t0, void* stream);
 /* The same layer spread over H / 32 workgroups per group of 8 sequences, the slice of W_hh of every workgroup resident in
  * registers and one grid barrier per step (needs all workgroups co-resident: nothing else may occupy the GPU's CUs).
  * (bf16, H = 512, B > 1: the recurrent product runs on the matrix cores, 16 sequences per group, h split into bf16 high + low.)

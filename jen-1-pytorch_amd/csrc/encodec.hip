@@ -35,6 +35,178 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const long long* __rest
   }
 }
 
+// ---- jen1_rvq_encode: the whole residual search of ResidualVectorQuantization.encode, and its decode, in one launch ----
+// A workgroup of 4 waves owns RVQE_FT = 32 frames for all n_q codebooks (the residual makes the codebooks sequential).  Every wave keeps
+// the residual of those 32 frames in registers as the B operand of v_mfma_f32_32x32x2_f32 (frame on the lane, 64 of the 128 k per lane
+// half), the codebook streams through two LDS buffers in chunks of 128 entries (the next chunk and its |e|^2 travel from L2 through
+// registers into the other buffer while this one is searched) and wave w searches entries 32 w .. 32 w + 31 of the chunk: its 16 LDS
+// fragments first, then 64 MFMAs on one accumulator (issue interval = dependent latency for this shape).  The score 2 r.e - |e|^2 of an
+// entry is lane-local (entries are the rows of the result), so the running (best score, best index) per frame lives in two registers;
+// the lane halves and the 4 waves are combined once per codebook, and the 32 chosen rows are fetched once per workgroup into LDS for
+// the subtract.  The dot product is an f32 fmaf chain in a fixed order of k that depends on nothing but k, so a frame's codes do not
+// depend on the launch shape or on its place in the tile.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int RVQE_FT = 32, RVQE_CH = 128, RVQE_LD = 132, RVQE_WAVES = 4, RVQE_THREADS = 64 * RVQE_WAVES, RVQE_MAXQ = 32, RVQE_D = 128;
+// LDS, in floats: two codebook buffers | the waves' (score, index) candidates | the tile's codes | |e|^2 of the two buffers' entries | the chosen rows
+constexpr int RVQE_OFF_RED = 2 * RVQE_CH * RVQE_LD, RVQE_OFF_CODE = RVQE_OFF_RED + 2 * RVQE_WAVES * RVQE_FT,
+              RVQE_OFF_ESQ = RVQE_OFF_CODE + RVQE_MAXQ * RVQE_FT, RVQE_OFF_ROW = RVQE_OFF_ESQ + 2 * RVQE_CH,
+              RVQE_LDS_BYTES = (RVQE_OFF_ROW + RVQE_FT * RVQE_LD) * 4;
+static_assert(RVQE_LDS_BYTES <= 160 * 1024 && RVQE_OFF_ESQ % 4 == 0 && RVQE_OFF_ROW % 4 == 0 && RVQE_THREADS >= RVQE_CH && RVQE_THREADS == 8 * RVQE_FT,
+              "rvq_encode_kernel: LDS carve");
+
+// on exact ties the LOWEST index wins (torch.argmax on the GEMM's scores returns the first maximum)
+__device__ __forceinline__ bool rvqe_better(float s, int i, float bs, int bi) { return s > bs || (s == bs && i < bi); }
+
+__device__ __forceinline__ void rvqe_fetch(const float* __restrict__ tables, const float* __restrict__ e_sq, int q, int c0, int bins, float4 (&pf)[16],
+                                           float& sq) {
+  const int r = c0 + (int)threadIdx.x;
+  sq = (int)threadIdx.x < RVQE_CH && r < bins ? e_sq[(long long)q * bins + r] : 0.f;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int e = (int)threadIdx.x + RVQE_THREADS * u, row = c0 + (e >> 5), c4 = e & 31;
+    pf[u] = row < bins ? *reinterpret_cast<const float4*>(tables + ((long long)q * bins + row) * RVQE_D + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+__device__ __forceinline__ void rvqe_stage(float* __restrict__ buf, float* __restrict__ esq, const float4 (&pf)[16], float sq) {
+  if ((int)threadIdx.x < RVQE_CH) esq[threadIdx.x] = sq;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int e = (int)threadIdx.x + RVQE_THREADS * u;
+    *reinterpret_cast<float4*>(buf + (e >> 5) * RVQE_LD + (e & 31) * 4) = pf[u];
+  }
+}
+
+__global__ __launch_bounds__(RVQE_THREADS) void rvq_encode_kernel(const float* __restrict__ emb, const float* __restrict__ tables,
+                                                                  const float* __restrict__ e_sq, long long* __restrict__ codes,
+                                                                  float* __restrict__ latents, int n_q, long long F, int T, int bins, int B_out,
+                                                                  long long codes_T, long long codes_t0, long long lat_T, long long lat_t0) {
+  extern __shared__ __attribute__((aligned(16))) float rvqe_lds[];
+  float* red_s = rvqe_lds + RVQE_OFF_RED;                              // [RVQE_WAVES][RVQE_FT]
+  int* red_i = reinterpret_cast<int*>(red_s + RVQE_WAVES * RVQE_FT);   // [RVQE_WAVES][RVQE_FT]
+  int* code_s = reinterpret_cast<int*>(rvqe_lds + RVQE_OFF_CODE);      // [RVQE_MAXQ][RVQE_FT]
+  float* esq_s = rvqe_lds + RVQE_OFF_ESQ;                              // [2][RVQE_CH]
+  float* row_s = rvqe_lds + RVQE_OFF_ROW;                              // [RVQE_FT][RVQE_LD]
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j = lane & 31, h = lane >> 5;
+  const long long f0 = (long long)blockIdx.x * RVQE_FT, f = f0 + j;
+  const bool valid = f < F;
+  const long long row = valid ? f / T : 0;
+  const int t = valid ? (int)(f - row * T) : 0;
+
+  // residual: register 4 s + m holds k = 8 s + 4 h + m (the k the lane's float4 of an entry holds at step s)
+  float res[64];
+#pragma unroll
+  for (int s = 0; s < 16; ++s)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) res[4 * s + m] = valid ? emb[(row * RVQE_D + 8 * s + 4 * h + m) * T + t] : 0.f;
+
+  const int nch = (bins + RVQE_CH - 1) / RVQE_CH;
+  float4 pf[16];
+  float pf_sq;
+  rvqe_fetch(tables, e_sq, 0, 0, bins, pf, pf_sq);
+  rvqe_stage(rvqe_lds, esq_s, pf, pf_sq);
+  int cur = 0;
+  __syncthreads();
+  for (int q = 0; q < n_q; ++q) {
+    float best = -INFINITY;
+    int bidx = 0;
+    for (int c = 0; c < nch; ++c) {
+      const int c0 = c * RVQE_CH;
+      const float* chunk = rvqe_lds + cur * (RVQE_CH * RVQE_LD);
+      const bool more = c + 1 < nch || q + 1 < n_q;                   // block-uniform
+      if (c + 1 < nch) rvqe_fetch(tables, e_sq, q, c0 + RVQE_CH, bins, pf, pf_sq);
+      else if (q + 1 < n_q) rvqe_fetch(tables, e_sq, q + 1, 0, bins, pf, pf_sq);
+      const int ebase = c0 + 32 * w;                                  // wave-uniform
+      if (ebase < bins) {
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        const float* arow = chunk + (32 * w + j) * RVQE_LD + 4 * h;
+        // all 16 fragments of the wave's entries first: a read issued between the dependent MFMAs would only overlap with the last of them
+        float4 a[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) a[s] = *reinterpret_cast<const float4*>(arow + 8 * s);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].x, res[4 * s + 0], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].y, res[4 * s + 1], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].z, res[4 * s + 2], acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s].w, res[4 * s + 3], acc, 0, 0, 0);
+        }
+        // register 4 g + x is entry ebase + 8 g + 4 h + x: ascending with the register, so '>' keeps the lowest index of a tie
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 sq = *reinterpret_cast<const float4*>(esq_s + cur * RVQE_CH + 32 * w + 8 * g + 4 * h);
+          const float sc[4] = {2.f * acc[4 * g + 0] - sq.x, 2.f * acc[4 * g + 1] - sq.y, 2.f * acc[4 * g + 2] - sq.z, 2.f * acc[4 * g + 3] - sq.w};
+#pragma unroll
+          for (int x = 0; x < 4; ++x)
+            if (sc[x] > best) { best = sc[x]; bidx = ebase + 8 * g + 4 * h + x; }
+        }
+      }
+      // the other buffer was last read before the previous barrier
+      if (more) rvqe_stage(rvqe_lds + (cur ^ 1) * (RVQE_CH * RVQE_LD), esq_s + (cur ^ 1) * RVQE_CH, pf, pf_sq);
+      cur ^= 1;
+      __syncthreads();
+    }
+    {
+      const float os = __shfl_xor(best, 32);
+      const int oi = __shfl_xor(bidx, 32);
+      if (rvqe_better(os, oi, best, bidx)) { best = os; bidx = oi; }
+    }
+    if (h == 0) { red_s[w * RVQE_FT + j] = best; red_i[w * RVQE_FT + j] = bidx; }
+    __syncthreads();          // the next write of red_* is behind the barrier of the next codebook's first chunk
+    best = red_s[j];
+    bidx = red_i[j];
+#pragma unroll
+    for (int v = 1; v < RVQE_WAVES; ++v) {
+      const float os = red_s[v * RVQE_FT + j];
+      const int oi = red_i[v * RVQE_FT + j];
+      if (rvqe_better(os, oi, best, bidx)) { best = os; bidx = oi; }
+    }
+    if (w == 0 && h == 0) {
+      code_s[q * RVQE_FT + j] = bidx;
+      if (codes && valid) {
+        const long long r_b = row % B_out, r_j = row / B_out;
+        codes[((long long)q * B_out + r_b) * codes_T + codes_t0 + r_j * T + t] = bidx;
+      }
+    }
+    // the 32 chosen rows through LDS (8 threads per row, 64 bytes each), then r = r - e_idx: a plain float32 subtract
+    {
+      const int fr = tid >> 3, part = (tid & 7) * 16;
+      const int idx_fr = __shfl(bidx, fr);                       // lane j of every wave holds frame j's index
+      const float* src = tables + ((long long)q * bins + idx_fr) * RVQE_D + part;
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(src + 4 * u);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) *reinterpret_cast<float4*>(row_s + fr * RVQE_LD + part + 4 * u) = v[u];
+    }
+    __syncthreads();          // the next write of row_s is behind the barriers of the next codebook's chunks
+    const float* erow = row_s + j * RVQE_LD + 4 * h;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float4 ev = *reinterpret_cast<const float4*>(erow + 8 * s);
+      res[4 * s + 0] -= ev.x;
+      res[4 * s + 1] -= ev.y;
+      res[4 * s + 2] -= ev.z;
+      res[4 * s + 3] -= ev.w;
+    }
+  }
+  if (!latents) return;
+  __syncthreads();
+  // the sum rvq_decode_kernel forms, in its order: 0 + e_idx0 + e_idx1 + ...
+  for (int e = tid; e < RVQE_FT * RVQE_D; e += RVQE_THREADS) {
+    const int tl = e & 31, d = e >> 5;
+    const long long fe = f0 + tl;
+    if (fe >= F) continue;
+    float acc = 0.f;
+    for (int q = 0; q < n_q; ++q) acc += tables[((long long)q * bins + code_s[q * RVQE_FT + tl]) * RVQE_D + d];
+    const long long r = fe / T, r_b = r % B_out, r_j = r / B_out;
+    latents[(r_b * RVQE_D + d) * lat_T + lat_t0 + r_j * T + (fe - r * T)] = acc;
+  }
+}
+
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // One workgroup per sequence; 1024 threads own the 4H gate rows (RPT = 4H / 1024 each).  Per step every thread adds
@@ -407,6 +579,30 @@ extern "C" int jen1_rvq_decode(const int64_t* codes, const float* tables, float*
   JEN1_CHECK(n_q >= 1 && B >= 1 && T >= 1 && bins >= 1 && D >= 1 && B <= 65535, "jen1_rvq_decode: bad shape");
   hipLaunchKernelGGL(rvq_decode_kernel, dim3((T + 63) / 64, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const long long*>(codes), tables, out, n_q, B, T, bins, D);
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_rvq_encode(const float* emb, const float* tables, const float* e_sq, int64_t* codes, float* latents, int n_q, int rows, int T,
+                               int bins, int D, int B_out, int64_t codes_T, int64_t codes_t0, int64_t lat_T, int64_t lat_t0, void* stream) {
+  JEN1_CHECK(emb && tables && e_sq, "jen1_rvq_encode: NULL argument");
+  JEN1_CHECK(codes || latents, "jen1_rvq_encode: codes and latents are both NULL");
+  JEN1_CHECK(D == RVQE_D, "jen1_rvq_encode: D must be %d, not %d", RVQE_D, D);
+  JEN1_CHECK(bins % 64 == 0 && bins >= 64 && bins <= 2048, "jen1_rvq_encode: bins=%d must be a multiple of 64 in [64, 2048]", bins);
+  JEN1_CHECK(n_q >= 1 && n_q <= RVQE_MAXQ && rows >= 1 && T >= 1 && B_out >= 1, "jen1_rvq_encode: bad shape n_q=%d rows=%d T=%d B_out=%d", n_q, rows, T,
+             B_out);
+  JEN1_CHECK(rows % B_out == 0, "jen1_rvq_encode: rows=%d is no multiple of B_out=%d", rows, B_out);
+  const int64_t span = (int64_t)(rows / B_out) * T;
+  JEN1_CHECK(!codes || (codes_t0 >= 0 && codes_t0 + span <= codes_T), "jen1_rvq_encode: codes slot %lld + %lld exceeds codes_T=%lld", (long long)codes_t0,
+             (long long)span, (long long)codes_T);
+  JEN1_CHECK(!latents || (lat_t0 >= 0 && lat_t0 + span <= lat_T), "jen1_rvq_encode: latents slot %lld + %lld exceeds lat_T=%lld", (long long)lat_t0,
+             (long long)span, (long long)lat_T);
+  const int64_t F = (int64_t)rows * T, tiles = (F + RVQE_FT - 1) / RVQE_FT;
+  JEN1_CHECK(tiles <= 0x7fffffffLL, "jen1_rvq_encode: too many frames");
+  JEN1_MAX_LDS_ONCE(rvq_encode_kernel, RVQE_LDS_BYTES);
+  hipLaunchKernelGGL(rvq_encode_kernel, dim3((unsigned)tiles), dim3(RVQE_THREADS), RVQE_LDS_BYTES, reinterpret_cast<hipStream_t>(stream), emb, tables,
+                     e_sq, reinterpret_cast<long long*>(codes), latents, n_q, (long long)F, T, bins, B_out, (long long)codes_T, (long long)codes_t0,
+                     (long long)lat_T, (long long)lat_t0);
   JEN1_HIP(hipGetLastError());
   return 0;
 }

@@ -42,6 +42,7 @@ class ResidualVectorQuantizerHIP:
         self.tables = tables.to(device, torch.float32).contiguous()
         self.device = torch.device(device)
         self._rt = None
+        self.e_sq = (self.tables ** 2).sum(-1).contiguous()                    # [n_q][bins]: |e|^2 of the search score 2 r.e - |e|^2
 
     @classmethod
     def from_state_dict(cls, sd: Dict[str, torch.Tensor], device="cuda") -> "ResidualVectorQuantizerHIP":
@@ -75,6 +76,41 @@ class ResidualVectorQuantizerHIP:
             res = res - self.tables[q][idx]
             out.append(idx.view(B, T))
         return torch.stack(out).to(src)
+
+    @torch.no_grad()
+    def quantize(self, emb: torch.Tensor, n_q: Optional[int] = None, *, codes: bool = True, latents: bool = True):
+        """``encode`` and ``decode`` of the result in ONE launch (jen1_rvq_encode): emb float32 [B, 128, T] -> (codes int64 [n_q, B, T] or
+        None, latents float32 [B, 128, T] or None), both on the quantizer's device.  The latents are bit-identical to ``decode(codes)``.  No
+        host synchronisation: the call can be captured in a graph."""
+        if not (codes or latents):
+            raise ValueError("quantize: nothing asked for (codes=False, latents=False)")
+        B, D, T = emb.shape
+        nq = self.tables.shape[0] if n_q is None else n_q
+        c = torch.empty((nq, B, T), dtype=torch.int64, device=self.device) if codes else None
+        z = torch.empty((B, D, T), dtype=torch.float32, device=self.device) if latents else None
+        self.quantize_into(emb, nq, c, z, B, 0)
+        return c, z
+
+    @torch.no_grad()
+    def quantize_into(self, emb: torch.Tensor, n_q: Optional[int], codes: Optional[torch.Tensor], latents: Optional[torch.Tensor], B_out: int,
+                      t0: int) -> None:
+        """the same into a time slot of preallocated outputs: emb [rows, 128, T] holds rows / B_out segments of B_out batch rows each (row
+        j B_out + b, as ``EncodecHIP.segment_rows`` orders them), which land side by side from frame ``t0`` of codes int64 [n_q, B_out, T']
+        and / or latents float32 [B_out, 128, T'] (contiguous, on the quantizer's device)"""
+        rows, D, T = emb.shape
+        nq = self.tables.shape[0] if n_q is None else n_q
+        assert 1 <= nq <= self.tables.shape[0]
+        bins = self.tables.shape[1]
+        x = emb.to(self.device, torch.float32).contiguous()
+        for o, dt in ((codes, torch.int64), (latents, torch.float32)):
+            assert o is None or (o.is_contiguous() and o.dtype == dt and o.device == x.device), "outputs must be contiguous on the quantizer's device"
+        assert codes is None or tuple(codes.shape[:2]) == (nq, B_out)
+        assert latents is None or tuple(latents.shape[:2]) == (B_out, D)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        L.check(self.lib.jen1_rvq_encode(x.data_ptr(), self.tables.data_ptr(), self.e_sq.data_ptr(), None if codes is None else codes.data_ptr(),
+                                         None if latents is None else latents.data_ptr(), nq, rows, T, bins, D, B_out,
+                                         0 if codes is None else codes.shape[2], t0, 0 if latents is None else latents.shape[2], t0, s),
+                "jen1_rvq_encode")
 
     @torch.no_grad()
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
@@ -420,6 +456,33 @@ class EncodecHIP:
                     frames.append((codes[:, j * B:(j + 1) * B].transpose(0, 1).to(src), None if scale is None else scale[:, s:s + 1].to(src)))
         enc._check_lstm()
         return frames
+
+    @torch.no_grad()
+    def encode_latents(self, audio: torch.Tensor):
+        """``encode`` followed by the quantizer's decode of all segments, without the codes in between: audio [B, C, N] -> (latents
+        float32 [B, 128, T'] with the segments side by side in time, the frame count of every segment, the per-segment scales [B, S] or
+        None), on the audio's device -- what ``Jen1.get_emb_segments`` returns.  The passes are those of ``_encode_batched``; the search of
+        every pass (jen1_rvq_encode) writes its latents straight into their time slot of the result."""
+        if self.encoder is None:
+            raise NotImplementedError("no encoder: construct EncodecHIP with encoder=SEANetEncoderHIP(...)")
+        assert audio.dim() == 3 and 0 < audio.shape[1] <= 2
+        enc = self.encoder
+        src = audio.device
+        x = audio.to(enc.device, torch.float32).contiguous()
+        B = x.shape[0]
+        counts = self.segment_frames(x.shape[-1])
+        offs = [sum(counts[:s]) for s in range(len(counts))]
+        scale = self.segment_scales(x) if self.normalize else None
+        per_pass = max(1, enc.lstm_multi_rows() // B)
+        out = torch.empty((B, 128, sum(counts)), dtype=torch.float32, device=self.quantizer.device)
+        for s0, count, length in _runs(segment_lengths(x.shape[-1], self.segment_length, self.segment_stride)):
+            for j0 in range(0, count, per_pass):
+                n = min(per_pass, count - j0)
+                emb = enc.from_rows(self.segment_rows(x, scale, s0 + j0, n, length))                    # [n B, 128, T]
+                assert emb.shape[2] == counts[s0 + j0]
+                self.quantizer.quantize_into(emb, self.n_q, None, out, B, offs[s0 + j0])
+        enc._check_lstm()
+        return out.to(src), counts, None if scale is None else scale.to(src)
 
     # ------------------------------------------------------------------ EncodecModel.decode
     @torch.no_grad()

@@ -74,10 +74,18 @@ class Jen1:
                  input_concat_ids: Sequence[str] = ("masked_input", "mask"), *, audio_encoder, conditioner: Callable,
                  convert_audio: Optional[Callable] = None, model_config: Optional[dict] = None,
                  diffusion_config: Optional[GDMConfig] = None, compute_dtype: str = "bf16", vdm_config: Optional[VDMConfig] = None,
-                 weights: str = "model"):
-        """``weights="ema"`` (keyword-only, not in the reference): sample from the checkpoint's EMA weights (``checkpoint.load_checkpoint``)"""
+                 weights: str = "model", latents: str = "codes"):
+        """``weights="ema"`` (keyword-only, not in the reference): sample from the checkpoint's EMA weights (``checkpoint.load_checkpoint``).
+        ``latents`` (keyword-only, not in the reference): ``"codes"`` builds the known latents as generation.py:145-150 does, ``encode`` then
+        ``quantizer.decode`` of the concatenated codes; ``"fused"`` asks ``audio_encoder.encode_latents`` for them (jen1_amd.encodec.EncodecHIP:
+        the residual search writes the latents itself)."""
         if weights not in ("model", "ema"):
             raise ValueError(f"weights must be 'model' or 'ema', not {weights!r}")
+        if latents not in ("codes", "fused"):
+            raise ValueError(f"latents must be 'codes' or 'fused', not {latents!r}")
+        if latents == "fused" and not hasattr(audio_encoder, "encode_latents"):
+            raise ValueError("latents='fused' needs an audio_encoder with encode_latents (jen1_amd.encodec.EncodecHIP)")
+        self.latents = latents
         self.ckpt_path, self.device, self.sample_rate, self.weights = ckpt_path, device, sample_rate, weights
         self.conditioner, self.audio_encoder = conditioner, audio_encoder
         self.cross_attn_cond_ids, self.global_cond_ids, self.input_concat_ids = cross_attn_cond_ids, global_cond_ids, input_concat_ids
@@ -258,12 +266,16 @@ class Jen1:
     def get_emb(self, audio: torch.Tensor) -> torch.Tensor:
         """waveform -> continuous latents [B, 128, T']: the codes of every encoded segment side by side in time, summed
         codebook vectors (generation.py:145-150)"""
+        if self.latents == "fused":
+            return self.audio_encoder.encode_latents(audio)[0]
         per_segment = [codes for codes, _scale in self.audio_encoder.encode(audio)]          # each [B, n_q, T_seg]
         return self.audio_encoder.quantizer.decode(torch.cat(per_segment, dim=-1).permute(1, 0, 2))
 
     def get_emb_segments(self, audio: torch.Tensor):
         """``get_emb`` together with the layout it came from: (latents [B, 128, T'], the frame count of every segment, the encoder's
         per-segment scales [B, S] or None) -- what ``decode_latents`` needs to undo the segmentation"""
+        if self.latents == "fused":
+            return self.audio_encoder.encode_latents(audio)
         frames = self.audio_encoder.encode(audio)
         emb = self.audio_encoder.quantizer.decode(torch.cat([codes for codes, _ in frames], dim=-1).permute(1, 0, 2))
         scales = None
@@ -276,3 +288,14 @@ class Jen1:
         """as written in the reference: input-concat entries are read as ``cond[key][0]`` -- the FIRST batch element --
         and expanded over the batch (generation.py:173-180)"""
         return get_conditioning(cond, self.cross_attn_cond_ids, self.global_cond_ids, self.input_concat_ids, batch_size=self.batch_size)
+
+
+# generation.py:194-213
+def save_audio_tensor(audio_tensor: torch.Tensor, file_path: str, sample_rate: int = 48000) -> None:
+    """saves audio ``[C, N]`` (or ``[1, C, N]``: the batch axis is dropped) as a 16-bit PCM ``.wav`` file (``jen1_amd.wav.save`` in the place
+    of ``torchaudio.save``)"""
+    from . import wav
+    audio_tensor = audio_tensor.detach()
+    if audio_tensor.ndim == 3:
+        audio_tensor = audio_tensor.squeeze(0)
+    wav.save(file_path, audio_tensor.to("cpu", torch.float32), sample_rate)

@@ -227,6 +227,7 @@ SYMBOLS = {
     "jen1_convert_clear": (c_int, [_P, _P, c_int64, c_int, _P]),
     "jen1_convert_clear_add": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
     "jen1_rvq_decode": (c_int, [_P, _P, _P] + [c_int] * 5 + [_P]),
+    "jen1_rvq_encode": (c_int, [_P] * 5 + [c_int] * 6 + [c_int64] * 4 + [_P]),
     "jen1_lstm_layer": (c_int, [_P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "jen1_lstm_layer_multi": (c_int, [_P, _P, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "jen1_codec_segment_scales": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, c_int, c_int, _P]),
