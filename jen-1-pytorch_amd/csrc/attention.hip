@@ -10,7 +10,7 @@
 // 64-lane __shfl_xor max / sum reductions.  Padding keys are not masked here -- the
 // reference zeroes their K and V rows instead (blocks.py:431-434), which the K/V
 // producer does through its row_scale epilogue.
-#include "common.h"
+#include "mfma_frag.h"
 
 #ifdef JEN1_PROFILE
 __device__ unsigned long long* g_attn_dbg = nullptr;
@@ -28,14 +28,6 @@ constexpr int QCHUNK = 32;     // queries per workgroup: two 16-row MFMA tiles
 constexpr int FMAX = 2;        // K/V vectors per thread that may carry a deferred LayerNorm finish (self-attention: Nk <= 24)
 constexpr int MAXV = 9;        // 8-element vectors per thread for one K or V tile: ceil(141*128/8/256) = 9
 
-template <typename T> struct AFrag;
-template <> struct AFrag<bf16_t> { typedef bf16x8 type; };
-template <> struct AFrag<float> { typedef f32x8 type; };
-template <> struct AFrag<fp8_t> { typedef long type; };
-__device__ __forceinline__ void amma(f32x4& acc, const long& a, const long& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_frag(long& f, const fp8_t* p) { f = *reinterpret_cast<const long*>(p); }
 // a raw Q / K vector into its LDS tile: a copy when the tile has the tensors' type, a conversion in JEN1_FP8 mode
 __device__ __forceinline__ void stage_vec(bf16_t* dst, const bf16x8& v) { *reinterpret_cast<bf16x8*>(dst) = v; }
 __device__ __forceinline__ void stage_vec(float* dst, const f32x8& v) { *reinterpret_cast<f32x8*>(dst) = v; }
@@ -43,40 +35,6 @@ __device__ __forceinline__ void stage_vec(fp8_t* dst, const bf16x8& v) {
   float x[8];
   vec_to_float(v, x);
   store8(dst, x);
-}
-__device__ __forceinline__ void amma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void amma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_frag(bf16x8& f, const bf16_t* p) { f = *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void lds_frag(f32x8& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-
-// reductions over the 16 lanes of a DPP row without touching LDS: xor 1, xor 2 (quad permutes), then the two mirrors
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));      // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_f<0x4E>(v));      // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_f<0x141>(v));     // row_half_mirror
-  v = fmaxf(v, dpp_f<0x140>(v));     // row_mirror
-  return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  v += dpp_f<0x140>(v);
-  return v;
 }
 
 // One 256-thread workgroup per (batch element, head, 32-query chunk).
@@ -100,7 +58,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ q,
                                                          const float* __restrict__ fin_stats, const float* __restrict__ fin_u,
                                                          const float* __restrict__ fin_b, float fin_inv_c, float fin_eps,
                                                          int fin_q, int fin_kv, float inv_H, int log2_vpr) {
-  typedef typename AFrag<ST>::type Frag;
+  typedef typename Frag8<ST>::type Frag;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool PRECISE = is_f32<T>::value;
   constexpr bool F8 = sizeof(ST) == 1;
@@ -249,7 +207,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ q,
           if (qt < nqt) {
             Frag qa;
             lds_frag(qa, q_s + (qt * 16 + li) * dq + c + lg * 8);
-            amma(acc[qt], qa, kb);
+            mma(acc[qt], qa, kb);
           }
         }
       }
@@ -356,7 +314,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ q,
         Frag pa, vb;
         lds_frag(pa, p_s + (qt * 16 + li) * vt + j + lg * 8);
         lds_frag(vb, kv_s + (ct * 16 + li) * vt + j + lg * 8);
-        amma(acc, pa, vb);
+        mma(acc, pa, vb);
       }
       // lane holds rows 4 lg + r (queries), column li (channel)
 #pragma unroll

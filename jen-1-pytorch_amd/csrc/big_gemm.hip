@@ -23,17 +23,15 @@
 //     from HBM once, the activations (2 - 4 MB) stay in the L2s.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "mfma_frag.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int BM = 128, BN = 128, ROWB = 128;          // tile rows; bytes of one tile row (the K step)
 constexpr int TILE_B = BM * ROWB;                      // 16 KiB per operand tile
-constexpr int RSRC_FLAGS = 0x00020000;
 
 struct BGroup {                 // one column group of the stacked B operand = one output tensor (a layer)
   void* c;                      // output rows: c + row * ldc (+ column n - n0), in the compute dtype or float32

@@ -11,6 +11,8 @@ typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #define JEN1_WAVE 64
 #define JEN1_FINE_GROUPS 32   // GroupNorm statistics are kept per 1/32 of the channel range
@@ -53,12 +55,32 @@ struct f32x8 {
   float v[8];
 };
 
-// sum over the 64 lanes of a wave, every lane gets it: DPP row steps and the two v_permlane swaps of gfx950 -- no LDS crossbar
-// (six ds_bpermute steps of __shfl_xor cost ~0.1 us each on a dependent chain)
+// ---- cross-lane reductions on DPP moves: no LDS crossbar ----------------------------------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
+__device__ __forceinline__ float quad_sum(float v) {        // fixed order: (a+b)+(c+d) in every lane of the quad
+  v += dpp_mov<0xB1>(v);                    // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);                    // quad_perm [2,3,0,1]
+  return v;
+}
+// over the 16 lanes of a DPP row (the 16 positions of an MFMA tile), every lane gets the result
+__device__ __forceinline__ float row16_sum(float v) {
+  v = quad_sum(v);
+  v += dpp_mov<0x141>(v);                   // row_half_mirror
+  v += dpp_mov<0x140>(v);                   // row_mirror
+  return v;
+}
+__device__ __forceinline__ float row16_max(float v) {
+  v = fmaxf(v, dpp_mov<0xB1>(v));
+  v = fmaxf(v, dpp_mov<0x4E>(v));
+  v = fmaxf(v, dpp_mov<0x141>(v));
+  v = fmaxf(v, dpp_mov<0x140>(v));
+  return v;
+}
+// sum over the 64 lanes of a wave, every lane gets it: DPP row steps and the two v_permlane swaps of gfx950 -- no LDS crossbar
+// (six ds_bpermute steps of __shfl_xor cost ~0.1 us each on a dependent chain)
 __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_mov<0xB1>(v);                    // lanes ^ 1
   v += dpp_mov<0x4E>(v);                    // lanes ^ 2

@@ -31,7 +31,7 @@
 //     fine-group sums, LayerNorm row sums) via LDS + global float atomics.
 //   * optional inter-workgroup split-K: partial slabs + agent-scope release / ticket /
 //     acquire, last arriver reduces (cdna_hip_programming.md section 5).
-#include "common.h"
+#include "mfma_frag.h"
 
 // Tuning builds only (-DJEN1_PROFILE): workgroup (0,0,0), thread 0 records the constant-rate 100 MHz
 // s_memrealtime counter at phase boundaries into args.slab (reused as a debug buffer).
@@ -84,50 +84,6 @@ __host__ __device__ inline Layout make_layout(const jen1_conv_args& a, int esize
   return L;
 }
 
-// ---- MFMA wrappers: both dtypes use "lane (i = l&15, g = l>>4) owns K elements 8g..8g+7" ----
-__device__ __forceinline__ void mma32(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma32(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
-
-template <typename T>
-struct FragOf;
-template <>
-struct FragOf<float> {
-  typedef f32x8 type;
-};
-template <>
-struct FragOf<bf16_t> {
-  typedef bf16x8 type;
-};
-
-__device__ __forceinline__ void frag_load(f32x8& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-__device__ __forceinline__ void frag_load(bf16x8& f, const bf16_t* p) { f = *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void frag_zero(f32x8& f) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
-}
-__device__ __forceinline__ void frag_zero(bf16x8& f) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = (bf16_t)0.f;
-}
-__device__ __forceinline__ void frag_to_float(const f32x8& f, float (&o)[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = f.v[j];
-}
-__device__ __forceinline__ void frag_to_float(const bf16x8& f, float (&o)[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (float)f[j];
-}
-
 __device__ __forceinline__ void float_to_frag(f32x8& f, const float (&o)[8]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) f.v[j] = o[j];
@@ -141,7 +97,7 @@ constexpr int VB = 4;   // activation vectors (8 channels each) per thread per s
 
 template <typename T, int MF, int NF, int WM, int WK, int PF>
 __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv_args a) {
-  typedef typename FragOf<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   constexpr int NT = 64 * WM * WK;     // threads per workgroup
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int BM = 16 * MF * WM;
@@ -283,7 +239,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
     for (int mf = 0; mf < MF; ++mf) {
       int mt = mt_base + mf;
       mt = mt < MT ? mt : MT - 1;
-      frag_load(dst[mf], wbase + ((size_t)((size_t)tap * kch_total + kc) * MT + mt) * 512 + lane * 8);
+      lds_frag(dst[mf], wbase + ((size_t)((size_t)tap * kch_total + kc) * MT + mt) * 512 + lane * 8);
     }
   };
   // activation batch: raw vectors (+ FiLM scale/shift vectors) of the staging loop
@@ -306,7 +262,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
       // branch-free (clamped address + select) so the staging loads are counted, not drained
       const T* p = (c < a.c0) ? reinterpret_cast<const T*>(a.x0) + grow * a.ld0 + c
                               : reinterpret_cast<const T*>(a.x1) + grow * a.ld1 + (c - a.c0);
-      frag_load(bt_.x[u], p);
+      lds_frag(bt_.x[u], p);
       if (!ok) frag_zero(bt_.x[u]);
     }
   };
@@ -323,7 +279,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
       const int cl = cv * 8;
       const int c = cst + cl;
       float x[8];
-      frag_to_float(bt_.x[u], x);
+      vec_to_float(bt_.x[u], x);
       const bool ok = (b < a.B) && (tin >= 0) && (tin < a.L_in);   // zero padding is applied AFTER the prologue
       if (ok) {
         if (gn) {
@@ -531,11 +487,11 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
           Frag bfr[NF];
 #pragma unroll
           for (int nf = 0; nf < NF; ++nf)
-            frag_load(bfr[nf], tile + (size_t)(rowbase[nf] + c_tap) * ldsld + kcl * 32 + lg * 8);
+            lds_frag(bfr[nf], tile + (size_t)(rowbase[nf] + c_tap) * ldsld + kcl * 32 + lg * 8);
 #pragma unroll
           for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
-            for (int nf = 0; nf < NF; ++nf) mma32(acc[mf][nf], ring[u][mf], bfr[nf]);
+            for (int nf = 0; nf < NF; ++nf) mma(acc[mf][nf], ring[u][mf], bfr[nf]);
           if (++c_j == nmy) { c_j = 0; ++c_tap; }
         }
       }

@@ -21,32 +21,24 @@
 // raises the error word and releases every other waiter.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#ifdef JEN1_DEEP_EXP_PLAIN        // timing experiment only: plain (L1-cached) loads instead of agent-scope ones in ld_live
+#define JEN1_LIVE_LOAD(p) (*(p))
+#endif
+#include "live_words.h"      // the reserved-word protocol: Raw8 / Raw4, ld_live, raw_bad, st_word, live_poll_again
+#include "mfma_frag.h"
 #include "jen1_deep.h"
 
 namespace {
-
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 constexpr int NT = JEN1_DEEP_THREADS;
 constexpr int NW = NT / 64;
 constexpr int SHARDS = JEN1_DEEP_SHARDS;
 static_assert(SHARDS >= 1 && SHARDS <= 63, "one wave polls the shards and the error word");
 constexpr int SHW = JEN1_DEEP_SHARD_WORDS;
-constexpr unsigned OOB = 0x80000000u;
-constexpr int RSRC_FLAGS = 0x00020000;
 constexpr int QCHUNK = 32;
 #ifndef JEN1_DEEP_ATTN_LIVE_VEC
 #define JEN1_DEEP_ATTN_LIVE_VEC 2     // K / V vectors per thread of a self-attention (produced inside the launch: held across the polled loads)
 #endif
-
-__device__ __forceinline__ gu64* g64(const void* p) { return (gu64*)(u64)p; }
-__device__ __forceinline__ gu32* g32(const void* p) { return (gu32*)(u64)p; }
 
 // ---- JEN1_FP8 mode (BASELINE configs[4]: "fp8 MFMA attention path"; blocks.py:355-380, :402-407, :440-446) -------------
 // Activations stay bf16 in HBM; what the matrix cores read is OCP e4m3 (gfx950's fp8): the packed weights (one float32 scale
@@ -56,56 +48,9 @@ template <typename T> struct Mode { typedef T G; };            // G: element typ
 template <> struct Mode<fp8_t> { typedef bf16_t G; };
 constexpr float P_SCALE = JEN1_FP8_P_SCALE;
 
-// ---- 8-element vectors through agent-scope (sc1) accesses: data another workgroup produced in THIS launch --------
-template <typename T> struct Raw8;
-template <> struct Raw8<bf16_t> { u64 d[2]; };
-template <> struct Raw8<float> { u64 d[4]; };
-
-#ifdef JEN1_DEEP_EXP_PLAIN        // timing experiment only: plain (L1-cached) loads instead of agent-scope ones
-#define JEN1_LIVE_LOAD(p) (*(p))
-#else
-#define JEN1_LIVE_LOAD(p) __hip_atomic_load(p, RLX_AGENT)
-#endif
-__device__ __forceinline__ void ld_live(Raw8<bf16_t>& r, const bf16_t* p) {
-  r.d[0] = JEN1_LIVE_LOAD(g64(p));
-  r.d[1] = JEN1_LIVE_LOAD(g64(p) + 1);
-}
-__device__ __forceinline__ void ld_live(Raw8<float>& r, const float* p) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r.d[i] = JEN1_LIVE_LOAD(g64(p) + i);
-}
-__device__ __forceinline__ void ld_plain(Raw8<bf16_t>& r, const bf16_t* p) {
-  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-  r.d[0] = ((u64)v[1] << 32) | v[0];
-  r.d[1] = ((u64)v[3] << 32) | v[2];
-}
-__device__ __forceinline__ void ld_plain(Raw8<float>& r, const float* p) {
-  const u32x4 a = *reinterpret_cast<const u32x4*>(p);
-  const u32x4 b = *reinterpret_cast<const u32x4*>(p + 4);
-  r.d[0] = ((u64)a[1] << 32) | a[0];
-  r.d[1] = ((u64)a[3] << 32) | a[2];
-  r.d[2] = ((u64)b[1] << 32) | b[0];
-  r.d[3] = ((u64)b[3] << 32) | b[2];
-}
+// ---- what this kernel alone does with live words (Raw8, ld_live, st_word<LOC> and the reserved word: live_words.h) ----------------------
 __device__ __forceinline__ void zero_raw(Raw8<bf16_t>& r) { r.d[0] = r.d[1] = 0; }
 __device__ __forceinline__ void zero_raw(Raw8<float>& r) { r.d[0] = r.d[1] = r.d[2] = r.d[3] = 0; }
-__device__ __forceinline__ void raw_to_float(const Raw8<bf16_t>& r, float (&o)[8]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const unsigned lo = (unsigned)r.d[i], hi = (unsigned)(r.d[i] >> 32);
-    o[4 * i + 0] = __uint_as_float(lo << 16);
-    o[4 * i + 1] = __uint_as_float(lo & 0xffff0000u);
-    o[4 * i + 2] = __uint_as_float(hi << 16);
-    o[4 * i + 3] = __uint_as_float(hi & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void raw_to_float(const Raw8<float>& r, float (&o)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = __uint_as_float((unsigned)r.d[i]);
-    o[2 * i + 1] = __uint_as_float((unsigned)(r.d[i] >> 32));
-  }
-}
 __device__ __forceinline__ void float_to_raw(const float (&x)[8], Raw8<bf16_t>& r) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -127,28 +72,6 @@ __device__ __forceinline__ void stage_raw(fp8_t* dst, const Raw8<bf16_t>& r) {
   raw_to_float(r, x);
   store8(dst, x);
 }
-// The all-ones 8-byte word is RESERVED (it means "not stored yet", see Sync below).  A finite result never encodes as it; four bf16
-// (two float32) NaNs with sign and every mantissa bit set would -- e.g. NaN weights whose payload propagates.  Every live store
-// therefore breaks exactly that pattern (the lowest payload bit of the word's first element is cleared: still a NaN, no longer
-// the sentinel): the consumer sees NaNs, as the reference's consumer would, and no data a producer can compute makes a consumer
-// wait (include/jen1_deep.h "Reserved word").  Three vector instructions per store.
-template <typename G>
-__device__ __forceinline__ void st_word(G* p, int i, unsigned lo, unsigned hi) {
-  lo -= ((lo & hi) == 0xffffffffu) ? 1u : 0u;
-  __hip_atomic_store(g64(p) + i, ((u64)hi << 32) | lo, RLX_AGENT);
-}
-// 4 consecutive output channels of one position, write-through
-__device__ __forceinline__ void st_live4(bf16_t* p, const float (&v)[4]) {
-  bf16x4 a;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) a[i] = (bf16_t)v[i];
-  const u32x2 w = __builtin_bit_cast(u32x2, a);
-  st_word(p, 0, w[0], w[1]);
-}
-__device__ __forceinline__ void st_live4(float* p, const float (&v)[4]) {
-  st_word(p, 0, __float_as_uint(v[0]), __float_as_uint(v[1]));
-  st_word(p, 1, __float_as_uint(v[2]), __float_as_uint(v[3]));
-}
 __device__ __forceinline__ void ld_live4(float (&o)[4], const bf16_t* p) {
   const u64 x = __hip_atomic_load(g64(p), RLX_AGENT);
   const unsigned lo = (unsigned)x, hi = (unsigned)(x >> 32);
@@ -162,90 +85,16 @@ __device__ __forceinline__ void ld_live4(float (&o)[4], const float* p) {
 }
 __device__ __forceinline__ void st_live8(bf16_t* p, const bf16_t* s) {   // 8 elements from LDS, write-through
   const u32x4 v = *reinterpret_cast<const u32x4*>(s);
-  st_word(p, 0, v[0], v[1]);
-  st_word(p, 1, v[2], v[3]);
+  st_word<false>(p, 0, v[0], v[1]);
+  st_word<false>(p, 1, v[2], v[3]);
 }
 __device__ __forceinline__ void st_live8(float* p, const float* s) {
   const u32x4 a = *reinterpret_cast<const u32x4*>(s);
   const u32x4 b = *reinterpret_cast<const u32x4*>(s + 4);
-  st_word(p, 0, a[0], a[1]);
-  st_word(p, 1, a[2], a[3]);
-  st_word(p, 2, b[0], b[1]);
-  st_word(p, 3, b[2], b[3]);
-}
-
-// ---- MFMA fragments ------------------------------------------------------------------------------------------------
-template <typename T> struct DFrag;
-template <> struct DFrag<bf16_t> { typedef bf16x8 type; };
-template <> struct DFrag<float> { typedef f32x8 type; };
-template <> struct DFrag<fp8_t> { typedef long type; };
-__device__ __forceinline__ void dmma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void dmma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
-__device__ __forceinline__ void dmma(f32x4& acc, const long& a, const long& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void dlds(long& f, const fp8_t* p) { f = *reinterpret_cast<const long*>(p); }
-__device__ __forceinline__ void dlds(bf16x8& f, const bf16_t* p) { f = *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void dlds(f32x8& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-// weight fragment through a buffer descriptor (out-of-range offsets return 0 and move no bytes); nt: used once per launch
-__device__ __forceinline__ void wload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  f = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 2));
-}
-__device__ __forceinline__ void wload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 2);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16u, soff, 2);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f.v[j] = __uint_as_float(lo[j]);
-    f.v[4 + j] = __uint_as_float(hi[j]);
-  }
-}
-
-__device__ __forceinline__ void wload(long& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  f = __builtin_bit_cast(long, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 2));
-}
-__device__ __forceinline__ void frag_zero_d(long& f) { f = 0; }
-__device__ __forceinline__ void frag_zero_d(bf16x8& f) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = (bf16_t)0.f;
-}
-__device__ __forceinline__ void frag_zero_d(f32x8& f) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float ddpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float quad_sum(float v) {       // fixed order: (a+b)+(c+d) in every lane of the quad
-  v += ddpp<0xB1>(v);
-  v += ddpp<0x4E>(v);
-  return v;
-}
-__device__ __forceinline__ float row16_sum_d(float v) {
-  v += ddpp<0xB1>(v);
-  v += ddpp<0x4E>(v);
-  v += ddpp<0x141>(v);
-  v += ddpp<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float row16_max_d(float v) {
-  v = fmaxf(v, ddpp<0xB1>(v));
-  v = fmaxf(v, ddpp<0x4E>(v));
-  v = fmaxf(v, ddpp<0x141>(v));
-  v = fmaxf(v, ddpp<0x140>(v));
-  return v;
+  st_word<false>(p, 0, a[0], a[1]);
+  st_word<false>(p, 1, a[2], a[3]);
+  st_word<false>(p, 2, b[0], b[1]);
+  st_word<false>(p, 3, b[2], b[3]);
 }
 
 #ifndef JEN1_DEEP_POLL_SLEEP
@@ -299,15 +148,7 @@ struct Hdr {
   int n_units, rot, kind, before;      // before: units of all earlier phases (the first ticket of this phase)
 };
 
-// ---- synchronisation: the data is its own flag ------------------------------------------------------------------------
-// Every tensor a phase of the launch produces is POISONED before the launch (all bytes 0xFF: jen1_deep_poison, a node of the
-// step's graph well ahead of the launch).  A producer stores its results as 8-byte single-copy-atomic write-through words and does
-// nothing else: no drain, no arrival counter.  A consumer WAVE loads the vectors it needs with agent-scope (L1-bypassing) loads
-// and repeats the loads until none of their 8-byte words is the sentinel: the load that finds the data complete is the load that
-// delivers it.  (A finite activation never encodes as four bf16 / two float32 NaNs with all mantissa bits set.)  Measured on
-// 256 workgroups (tools/microbench/flagchain.hip): 1.2 - 1.35 us per all-to-all stage against 3.05 us for
-// stores -> drain -> counter -> poll -> barrier -> load, the protocol of round 2.  Every spin is bounded: a wave that gives up
-// raises the error word (1 + phase), which releases every other waiter; results are garbage then and the host raises.
+// ---- synchronisation: the data is its own flag (live_words.h) ---------------------------------------------------------------------
 struct Sync {
   unsigned* err;       // error word
   bool dead;           // this wave: a wait timed out somewhere: stop waiting, finish with whatever is there
@@ -336,59 +177,16 @@ __device__ unsigned long long* g_deep_dbg = nullptr;
 #define DK_STAMPN(sy, i) do { } while (0)
 #endif
 
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-constexpr u64 POISON = ~0ull;
 #ifndef JEN1_DEEP_POLL_LIMIT
 #define JEN1_DEEP_POLL_LIMIT (1u << 17)      // failed polls of one wait before the wave gives up (~1.3 us each: ~170 ms; 2^15 = ~40 ms was
                                              // reached now and then by four full-model samplers sharing a GPU that had just been powered up)
 #endif
-__device__ __forceinline__ bool raw_bad(const Raw8<bf16_t>& r) { return (r.d[0] == POISON) | (r.d[1] == POISON); }
-__device__ __forceinline__ bool raw_bad(const Raw8<float>& r) {
-  return (r.d[0] == POISON) | (r.d[1] == POISON) | (r.d[2] == POISON) | (r.d[3] == POISON);
-}
-// 4 consecutive channels (a residual operand) as raw words
-template <typename T> struct Raw4;
-template <> struct Raw4<bf16_t> { u64 d[1]; };
-template <> struct Raw4<float> { u64 d[2]; };
-__device__ __forceinline__ void ld_live4r(Raw4<bf16_t>& r, const bf16_t* p) { r.d[0] = __hip_atomic_load(g64(p), RLX_AGENT); }
-__device__ __forceinline__ void ld_live4r(Raw4<float>& r, const float* p) {
-  r.d[0] = __hip_atomic_load(g64(p), RLX_AGENT);
-  r.d[1] = __hip_atomic_load(g64(p) + 1, RLX_AGENT);
-}
-__device__ __forceinline__ bool raw_bad(const Raw4<bf16_t>& r) { return r.d[0] == POISON; }
-__device__ __forceinline__ bool raw_bad(const Raw4<float>& r) { return (r.d[0] == POISON) | (r.d[1] == POISON); }
-__device__ __forceinline__ void raw4_to_float(const Raw4<bf16_t>& r, float (&o)[4]) {
-  const unsigned lo = (unsigned)r.d[0], hi = (unsigned)(r.d[0] >> 32);
-  o[0] = __uint_as_float(lo << 16); o[1] = __uint_as_float(lo & 0xffff0000u);
-  o[2] = __uint_as_float(hi << 16); o[3] = __uint_as_float(hi & 0xffff0000u);
-}
-__device__ __forceinline__ void raw4_to_float(const Raw4<float>& r, float (&o)[4]) {
-  o[0] = __uint_as_float((unsigned)r.d[0]); o[1] = __uint_as_float((unsigned)(r.d[0] >> 32));
-  o[2] = __uint_as_float((unsigned)r.d[1]); o[3] = __uint_as_float((unsigned)(r.d[1] >> 32));
-}
-
-// behind a round of loads of one wave: `bad` = this lane saw a sentinel word.  Returns true when the wave has to load again.
-// (wave-uniform; the error word is looked at every 64th failed poll)
+// this kernel's switch and limits on the shared poll loop
 __device__ __forceinline__ bool poll_again(Sync& sy, bool bad, unsigned& spins) {
 #ifdef JEN1_DEEP_EXP_NOWAIT      // timing experiment only: results are garbage
   return false;
 #endif
-  if (!__builtin_amdgcn_ballot_w64(bad) || sy.dead) return false;
-  ++spins;
-  if ((spins & 63u) == 0u) {
-    const unsigned ev = __hip_atomic_load(g32(sy.err), RLX_AGENT);
-    if (rfl((int)ev) != 0) { sy.dead = true; return false; }
-  }
-  if (spins > JEN1_DEEP_POLL_LIMIT) {
-    if ((threadIdx.x & 63) == 0) __hip_atomic_store(g32(sy.err), (unsigned)(sy.p + 1), RLX_AGENT);
-    sy.dead = true;
-    return false;
-  }
-#if JEN1_DEEP_POLL_SLEEP > 0
-  __builtin_amdgcn_s_sleep(JEN1_DEEP_POLL_SLEEP);     // (units of 64 clocks) between polls
-#endif
-  return true;
+  return live_poll_again<JEN1_DEEP_POLL_LIMIT, JEN1_DEEP_POLL_SLEEP>(sy, bad, spins);
 }
 
 // ---- scheduling: static ------------------------------------------------------------------------------------------------------------
@@ -572,9 +370,9 @@ __device__ __forceinline__ void gemm_issue(const GemmWave<T>& g, const KCursor& 
   constexpr int ES = sizeof(T);
   constexpr unsigned BLK = 512 * ES;
 #ifdef JEN1_DEEP_EXP_NOW          // timing experiment only: no weight traffic
-  wload(fa, g.rw, OOB, 0);
+  buf_frag<2>(fa, g.rw, OOB, 0);
 #else
-  wload(fa, g.rw, (unsigned)lane * (8u * ES), (unsigned)(c.g * g.MT + g.mt) * BLK);
+  buf_frag<2>(fa, g.rw, (unsigned)lane * (8u * ES), (unsigned)(c.g * g.MT + g.mt) * BLK);
 #endif
 }
 
@@ -597,9 +395,9 @@ __device__ __forceinline__ void gemm_issue_g(const GemmWave<T>& g, int chunk, in
   constexpr int ES = sizeof(T);
   constexpr unsigned BLK = 512 * ES;
 #ifdef JEN1_DEEP_EXP_NOW
-  wload(fa, g.rw, OOB, 0);
+  buf_frag<2>(fa, g.rw, OOB, 0);
 #else
-  wload(fa, g.rw, (unsigned)lane * (8u * ES), (unsigned)(chunk * g.MT + g.mt) * BLK);
+  buf_frag<2>(fa, g.rw, (unsigned)lane * (8u * ES), (unsigned)(chunk * g.MT + g.mt) * BLK);
 #endif
 }
 
@@ -613,7 +411,7 @@ __device__ __forceinline__ void gemm_prefill(const unsigned char* D, int u, int 
 #pragma unroll
   for (int i = 0; i < PF; ++i) {
     if (i < g.total) gemm_issue_g<T>(g, __builtin_amdgcn_readlane(st.g, i), lane, ra[i]);
-    else frag_zero_d(ra[i]);
+    else frag_zero(ra[i]);
   }
 }
 
@@ -624,9 +422,9 @@ __device__ __forceinline__ void k_round(f32x4 (&acc)[4], const Frag (&ra)[PF], c
   for (int i = 0; i < (NS < PF ? NS : PF); ++i) {
     Frag fb[NF];
 #pragma unroll
-    for (int nf = 0; nf < NF; ++nf) dlds(fb[nf], tile + cbase[nf] + soff[i]);
+    for (int nf = 0; nf < NF; ++nf) lds_frag(fb[nf], tile + cbase[nf] + soff[i]);
 #pragma unroll
-    for (int nf = 0; nf < NF; ++nf) dmma(acc[nf], ra[i], fb[nf]);
+    for (int nf = 0; nf < NF; ++nf) mma(acc[nf], ra[i], fb[nf]);
   }
 }
 // a round of `left` chunks (slots beyond them hold zero weights: rounded up to 4 slots)
@@ -651,10 +449,10 @@ __device__ __forceinline__ float xor32_add(float v) {
 }
 // sum and sum of squares over the 2^lS lanes of a lane set (lS wave-uniform, 1..6), the two chains interleaved
 __device__ __forceinline__ void lane_set_sum2(float& s, float& q, int lS) {
-  s += ddpp<0xB1>(s); q += ddpp<0xB1>(q);                         // lanes ^ 1
-  if (lS >= 2) { s += ddpp<0x4E>(s); q += ddpp<0x4E>(q); }        // lanes ^ 2
-  if (lS >= 3) { s += ddpp<0x141>(s); q += ddpp<0x141>(q); }      // row_half_mirror: the other quad of the 8
-  if (lS >= 4) { s += ddpp<0x140>(s); q += ddpp<0x140>(q); }      // row_mirror: the other half of the 16
+  s += dpp_mov<0xB1>(s); q += dpp_mov<0xB1>(q);                         // lanes ^ 1
+  if (lS >= 2) { s += dpp_mov<0x4E>(s); q += dpp_mov<0x4E>(q); }        // lanes ^ 2
+  if (lS >= 3) { s += dpp_mov<0x141>(s); q += dpp_mov<0x141>(q); }      // row_half_mirror: the other quad of the 8
+  if (lS >= 4) { s += dpp_mov<0x140>(s); q += dpp_mov<0x140>(q); }      // row_mirror: the other half of the 16
   if (lS >= 5) { s = xor16_add(s); q = xor16_add(q); }
   if (lS >= 6) { s = xor32_add(s); q = xor32_add(q); }
 }
@@ -1118,7 +916,7 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
             soff[i] = ic.shift * pitch + ic.col;
             if (c0 + PF + i + 1 < total) kc_next(ic, gw.runs, gw.nruns);
           } else {
-            frag_zero_d(ra[i]);
+            frag_zero(ra[i]);
           }
         }
       }
@@ -1134,7 +932,7 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
         gemm_issue_g<T>(gw, __builtin_amdgcn_readlane(stab.g, i), lane, ra[i]);
         soff[i] = __builtin_amdgcn_readlane(stab.off, i);
       } else {
-        frag_zero_d(ra[i]);
+        frag_zero(ra[i]);
       }
     }
   };
@@ -1172,8 +970,8 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] += rres[r];
       const size_t off = (size_t)((unsigned)yrow * (unsigned)HI(ld_y)) + (unsigned)co;
-      if (HI(y_f32)) st_live4(HP(y, float*) + off, v);
-      else st_live4(HP(y, GT*) + off, v);
+      if (HI(y_f32)) st_live4<false>(HP(y, float*) + off, v);
+      else st_live4<false>(HP(y, GT*) + off, v);
     }
   };
   {
@@ -1221,7 +1019,7 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
 template <typename T, typename FPub>
 __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& sy, FPub publish_next, int tid) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef typename DFrag<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   typedef typename Mode<T>::G GT;                      // q / k / v / out in global memory (bf16 in JEN1_FP8 mode)
   constexpr bool PRECISE = is_f32<T>::value;
   constexpr bool F8 = sizeof(T) == 1;
@@ -1450,8 +1248,8 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
           for (int j = 0; j < 8; ++j) { s += f[j]; q2 += f[j] * f[j]; }
         }
       }
-      s = row16_sum_d(s);
-      q2 = row16_sum_d(q2);
+      s = row16_sum(s);
+      q2 = row16_sum(q2);
       if (li == 0) {
         const float mean = s * inv_c;
         float var = q2 * inv_c - mean * mean;
@@ -1488,13 +1286,13 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       for (int c = 0; c < DP; c += 32) {
         Frag kb;
-        dlds(kb, kv_s + (kt * 16 + li) * dq + c + lg * 8);
+        lds_frag(kb, kv_s + (kt * 16 + li) * dq + c + lg * 8);
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
           if (qt < nqt) {
             Frag qa;
-            dlds(qa, q_s + (qt * 16 + li) * dq + c + lg * 8);
-            dmma(acc[qt], qa, kb);
+            lds_frag(qa, q_s + (qt * 16 + li) * dq + c + lg * 8);
+            mma(acc[qt], qa, kb);
           }
         }
       }
@@ -1553,7 +1351,7 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
           e[t] = in ? e[t] : -3.402823466e+38f;
           mx = fmaxf(mx, e[t]);
         }
-        mx = row16_max_d(mx);
+        mx = row16_max(mx);
         float sum = 0.f;
 #pragma unroll
         for (int t = 0; t < 12; ++t) {
@@ -1561,7 +1359,7 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
           e[t] = in ? (PRECISE ? expf(e[t] - mx) : __expf(e[t] - mx)) : 0.f;
           sum += e[t];
         }
-        sum = row16_sum_d(sum);
+        sum = row16_sum(sum);
         const float inv = (PRECISE ? 1.0f / sum : __builtin_amdgcn_rcpf(sum)) * PS;
 #pragma unroll
         for (int t = 0; t < 12; ++t) {
@@ -1581,9 +1379,9 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       for (int j = 0; j < NKP; j += 32) {
         Frag pa, vb;
-        dlds(pa, p_s + (qt * 16 + li) * vt + j + lg * 8);
-        dlds(vb, vt_s + (ct * 16 + li) * vt + ((j + lg * 8) ^ ((((ct * 16 + li) >> 3) & 3) << 3)));
-        dmma(acc, pa, vb);
+        lds_frag(pa, p_s + (qt * 16 + li) * vt + j + lg * 8);
+        lds_frag(vb, vt_s + (ct * 16 + li) * vt + ((j + lg * 8) ^ ((((ct * 16 + li) >> 3) & 3) << 3)));
+        mma(acc, pa, vb);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1716,10 +1514,10 @@ constexpr int TILE_SP = 4;             // statistics partials (8 bytes each) per
 constexpr int TILE_MF = 2;             // 16-row M tiles per wave
 
 template <typename T, typename FPub>
-__device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& sy, typename DFrag<T>::type (&ring)[TileCfg<T>::RING], FPub publish_next,
+__device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& sy, typename Frag8<T>::type (&ring)[TileCfg<T>::RING], FPub publish_next,
                                           int tid) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef typename DFrag<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   constexpr bool PRECISE = is_f32<T>::value;
   constexpr unsigned ES = sizeof(T);
   constexpr unsigned BLK = 512 * ES;
@@ -1768,7 +1566,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
   auto issueA = [&](int slot) __attribute__((always_inline)) {
     const bool in = issuedA < KS;
 #pragma unroll
-    for (int mf = 0; mf < MF; ++mf) wload(ring[slot * MF + mf], rw, in ? voffA[mf] : OOB, in ? soffA : 0u);
+    for (int mf = 0; mf < MF; ++mf) buf_frag<2>(ring[slot * MF + mf], rw, in ? voffA[mf] : OOB, in ? soffA : 0u);
     soffA += stepA;
     ++issuedA;
   };
@@ -2057,11 +1855,11 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
         const T* bp = tile + c_tap * ldsld + c_kc * 32;
         Frag bfr[NFW];
 #pragma unroll
-        for (int nf = 0; nf < NFW; ++nf) dlds(bfr[nf], bp + ldsrow[nf]);
+        for (int nf = 0; nf < NFW; ++nf) lds_frag(bfr[nf], bp + ldsrow[nf]);
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
-          for (int nf = 0; nf < NFW; ++nf) dmma(acc[mf][nf], ring[slot * MF + mf], bfr[nf]);
+          for (int nf = 0; nf < NFW; ++nf) mma(acc[mf][nf], ring[slot * MF + mf], bfr[nf]);
         if (++c_kc == kch && !in_extra) {
           c_kc = 0;
           if (++c_tap == taps && xs) { in_extra = true; c_tap = pad_left; c_kc = kch; }
@@ -2145,8 +1943,8 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
               for (int r = 0; r < 4; ++r) v[r] += r4[r];
             }
             const unsigned off = (unsigned)yrow_[mf][nf] * (unsigned)ld_y + (unsigned)co_[mf];
-            if (y_f32) st_live4(TP(h.y, float*) + off, v);
-            else st_live4(TP(h.y, GT*) + off, v);
+            if (y_f32) st_live4<false>(TP(h.y, float*) + off, v);
+            else st_live4<false>(TP(h.y, GT*) + off, v);
             gs += (v[0] + v[1]) + (v[2] + v[3]);
             gq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
           }
@@ -2155,7 +1953,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
       if (mf == MF - 1) DK_STAMP(sy, 10);
       if (out_part) {
         // the 16 rows of an M tile lie in ONE statistics group (out_cps is a multiple of 16): all 64 lanes, fixed tree
-        gs = row16_sum_d(gs); gq = row16_sum_d(gq);
+        gs = row16_sum(gs); gq = row16_sum(gq);
         auto rl = [](float v, int l) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); };
         const float ts = (rl(gs, 0) + rl(gs, 16)) + (rl(gs, 32) + rl(gs, 48));       // the four rows of the wave, fixed order, no LDS round trips
         const float tq = (rl(gq, 0) + rl(gq, 16)) + (rl(gq, 32) + rl(gq, 48));
@@ -2196,7 +1994,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
         q += mine ? e4[e].y : 0.f;
       }
       const size_t idx = ((size_t)b * (size_t)(tiles_t * mblocks) + (size_t)(tt * mblocks + mblk)) * (size_t)onfg + (size_t)tid;
-      st_word(reinterpret_cast<float*>(out_part) + 2 * idx, 0, __float_as_uint(s), __float_as_uint(q));      // (sum, sumsq) partial: same reserved word
+      st_word<false>(reinterpret_cast<float*>(out_part) + 2 * idx, 0, __float_as_uint(s), __float_as_uint(q));      // (sum, sumsq) partial: same reserved word
     }
   }
   DK_STAMP(sy, 14);
@@ -2214,7 +2012,7 @@ template <typename T, bool TK, int KM>      // TK: units by ticket (any number o
 __global__ __launch_bounds__(NT) void deep_kernel(const unsigned char* __restrict__ blobs, const int4* __restrict__ hdr_g, int n_phases,
                                                   unsigned* sync, unsigned* err) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef typename DFrag<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   constexpr int PF = KM == KM_TILE ? TileCfg<T>::RING : DeepCfg<T>::PF;      // the weight ring of the kernel's units
   const int tid = threadIdx.x;
   const int lane = tid & 63, wk = rfl(tid >> 6);

@@ -451,15 +451,8 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const T* __restrict__ net
 // ---- the same step for C % 8 == 0 (the latent channels of the model: 128): 16-byte row loads, no LDS crossbar -----------------------
 // Half a wave owns a (b, t) row, a lane 8 consecutive channels of it; the row reductions of the std rescale are DPP row steps and one
 // v_permlane16_swap; x_t and the step's noise -- which do not depend on the network output -- are requested before anything else.
-template <int CTRL>
-__device__ __forceinline__ float edpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
 __device__ __forceinline__ float half_wave_sum(float v) {           // over the 32 lanes of a half wave, every lane gets the sum
-  v += edpp<0xB1>(v);                                                // lanes ^ 1
-  v += edpp<0x4E>(v);                                                // lanes ^ 2
-  v += edpp<0x141>(v);                                               // row_half_mirror
-  v += edpp<0x140>(v);                                               // row_mirror
+  v = row16_sum(v);
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);              // lanes ^ 16
 }

@@ -17,30 +17,17 @@
 // loads (write-through, L1-bypassing); every spin is bounded, a time-out raises the error word and releases every waiter.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "live_words.h"      // the reserved-word protocol: Raw8 / Raw4, ld_live, raw_bad, st_word<LOC>, live_poll_again
+#include "mfma_frag.h"
 #include "jen1_long.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 constexpr int NT = JEN1_LONG_THREADS;
 constexpr int NW = NT / 64;
-constexpr unsigned OOB = 0x80000000u;
-constexpr int RSRC_FLAGS = 0x00020000;
-constexpr u64 POISON = ~0ull;
 constexpr int LDS_TOTAL = 160 * 1024;
 constexpr int LDS_MIN = 84 * 1024;          // more than half of a CU's LDS: never two workgroups of this kernel on one CU
 static_assert(sizeof(jen1_long_phase) == JEN1_LONG_DESC_BYTES, "the descriptor is read as two dwords per lane");
-
-__device__ __forceinline__ gu64* g64(const void* p) { return (gu64*)(u64)p; }
-__device__ __forceinline__ gu32* g32(const void* p) { return (gu32*)(u64)p; }
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // ---- the descriptor without LDS round trips: lane i of two registers holds dwords i and 64 + i; a field is a v_readlane ------------
 struct DescRegs {
@@ -69,139 +56,13 @@ __device__ __forceinline__ PT d_ptr(const DescRegs& r) {
 #define LF(f) d_f32<offsetof(jen1_long_phase, f)>(dr)
 #define LP(f, type) d_ptr<offsetof(jen1_long_phase, f), type>(dr)
 
-// ---- 8-element vectors through agent-scope accesses --------------------------------------------------------------------------
-template <typename T> struct Raw8;
-template <> struct Raw8<bf16_t> { u64 d[2]; };
-template <> struct Raw8<float> { u64 d[4]; };
-__device__ __forceinline__ void ld_live(Raw8<bf16_t>& r, const bf16_t* p) {
-  r.d[0] = __hip_atomic_load(g64(p), RLX_AGENT);
-  r.d[1] = __hip_atomic_load(g64(p) + 1, RLX_AGENT);
-}
-__device__ __forceinline__ void ld_live(Raw8<float>& r, const float* p) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r.d[i] = __hip_atomic_load(g64(p) + i, RLX_AGENT);
-}
-__device__ __forceinline__ void ld_plain(Raw8<bf16_t>& r, const bf16_t* p) {
-  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-  r.d[0] = ((u64)v[1] << 32) | v[0];
-  r.d[1] = ((u64)v[3] << 32) | v[2];
-}
-__device__ __forceinline__ void ld_plain(Raw8<float>& r, const float* p) {
-  const u32x4 a = *reinterpret_cast<const u32x4*>(p);
-  const u32x4 b = *reinterpret_cast<const u32x4*>(p + 4);
-  r.d[0] = ((u64)a[1] << 32) | a[0];
-  r.d[1] = ((u64)a[3] << 32) | a[2];
-  r.d[2] = ((u64)b[1] << 32) | b[0];
-  r.d[3] = ((u64)b[3] << 32) | b[2];
-}
-__device__ __forceinline__ bool raw_bad(const Raw8<bf16_t>& r) { return (r.d[0] == POISON) | (r.d[1] == POISON); }
-__device__ __forceinline__ bool raw_bad(const Raw8<float>& r) {
-  return (r.d[0] == POISON) | (r.d[1] == POISON) | (r.d[2] == POISON) | (r.d[3] == POISON);
-}
-__device__ __forceinline__ void raw_to_float(const Raw8<bf16_t>& r, float (&o)[8]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const unsigned lo = (unsigned)r.d[i], hi = (unsigned)(r.d[i] >> 32);
-    o[4 * i + 0] = __uint_as_float(lo << 16);
-    o[4 * i + 1] = __uint_as_float(lo & 0xffff0000u);
-    o[4 * i + 2] = __uint_as_float(hi << 16);
-    o[4 * i + 3] = __uint_as_float(hi & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void raw_to_float(const Raw8<float>& r, float (&o)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = __uint_as_float((unsigned)r.d[i]);
-    o[2 * i + 1] = __uint_as_float((unsigned)(r.d[i] >> 32));
-  }
-}
-// The all-ones 8-byte word is reserved ("not stored yet", include/jen1_deep.h): every live store breaks exactly that pattern
-// LOC: every reader of the word runs on the XCD of the writer (a sample's group of workgroups on one XCD): a PLAIN store -- the line
-// stays in that XCD's L2, where the readers' L1-bypassing polls find it (0.30 us hand-off against 0.47 - 0.60 written through,
-// tools/xcd_handoff_probe.hip; a plain store never arrives on ANOTHER XCD before the kernel ends)
-template <bool LOC, typename G>
-__device__ __forceinline__ void st_word(G* p, int i, unsigned lo, unsigned hi) {
-  lo -= ((lo & hi) == 0xffffffffu) ? 1u : 0u;
-  if constexpr (LOC) *(g64(p) + i) = ((u64)hi << 32) | lo;
-  else __hip_atomic_store(g64(p) + i, ((u64)hi << 32) | lo, RLX_AGENT);
-}
-template <bool LOC>
-__device__ __forceinline__ void st_live4(bf16_t* p, const float (&v)[4]) {
-  bf16x4 a;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) a[i] = (bf16_t)v[i];
-  const u32x2 w = __builtin_bit_cast(u32x2, a);
-  st_word<LOC>(p, 0, w[0], w[1]);
-}
-template <bool LOC>
-__device__ __forceinline__ void st_live4(float* p, const float (&v)[4]) {
-  st_word<LOC>(p, 0, __float_as_uint(v[0]), __float_as_uint(v[1]));
-  st_word<LOC>(p, 1, __float_as_uint(v[2]), __float_as_uint(v[3]));
-}
-template <typename T> struct Raw4;
-template <> struct Raw4<bf16_t> { u64 d[1]; };
-template <> struct Raw4<float> { u64 d[2]; };
-__device__ __forceinline__ void ld_live4r(Raw4<bf16_t>& r, const bf16_t* p) { r.d[0] = __hip_atomic_load(g64(p), RLX_AGENT); }
-__device__ __forceinline__ void ld_live4r(Raw4<float>& r, const float* p) {
-  r.d[0] = __hip_atomic_load(g64(p), RLX_AGENT);
-  r.d[1] = __hip_atomic_load(g64(p) + 1, RLX_AGENT);
-}
-__device__ __forceinline__ bool raw_bad(const Raw4<bf16_t>& r) { return r.d[0] == POISON; }
-__device__ __forceinline__ bool raw_bad(const Raw4<float>& r) { return (r.d[0] == POISON) | (r.d[1] == POISON); }
-__device__ __forceinline__ void raw4_to_float(const Raw4<bf16_t>& r, float (&o)[4]) {
-  const unsigned lo = (unsigned)r.d[0], hi = (unsigned)(r.d[0] >> 32);
-  o[0] = __uint_as_float(lo << 16); o[1] = __uint_as_float(lo & 0xffff0000u);
-  o[2] = __uint_as_float(hi << 16); o[3] = __uint_as_float(hi & 0xffff0000u);
-}
-__device__ __forceinline__ void raw4_to_float(const Raw4<float>& r, float (&o)[4]) {
-  o[0] = __uint_as_float((unsigned)r.d[0]); o[1] = __uint_as_float((unsigned)(r.d[0] >> 32));
-  o[2] = __uint_as_float((unsigned)r.d[1]); o[3] = __uint_as_float((unsigned)(r.d[1] >> 32));
-}
-
-// ---- MFMA fragments ---------------------------------------------------------------------------------------------------------------
-template <typename T> struct LFrag;
-template <> struct LFrag<bf16_t> { typedef bf16x8 type; };
-template <> struct LFrag<float> { typedef f32x8 type; };
-__device__ __forceinline__ void lmma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void lmma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
-__device__ __forceinline__ void llds(bf16x8& f, const bf16_t* p) { f = *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void llds(f32x8& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
 // weight fragment through a buffer descriptor (out-of-range offsets return 0 and move no bytes)
-__device__ __forceinline__ void wload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-#ifdef JEN1_LONG_EXP_NOW         // timing experiment only: every weight request is out of range (no bytes move)
-  voff = OOB;
+template <typename F>
+__device__ __forceinline__ void wload(F& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+#ifdef JEN1_LONG_EXP_NOW         // timing experiment only (bf16): every weight request is out of range (no bytes move)
+  if constexpr (std::is_same<F, bf16x8>::value) voff = OOB;
 #endif
-  f = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ void wload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16u, soff, 0);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f.v[j] = __uint_as_float(lo[j]);
-    f.v[4 + j] = __uint_as_float(hi[j]);
-  }
-}
-template <int CTRL>
-__device__ __forceinline__ float ldpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row16_sum_l(float v) {
-  v += ldpp<0xB1>(v);
-  v += ldpp<0x4E>(v);
-  v += ldpp<0x141>(v);
-  v += ldpp<0x140>(v);
-  return v;
+  buf_frag<0>(f, r, voff, soff);
 }
 __device__ __forceinline__ float rlane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
@@ -242,26 +103,12 @@ __device__ unsigned long long* g_long_dbg = nullptr;
 #else
 #define LK_STAMP(sy, i) do { } while (0)
 #endif
-// behind a round of loads of one wave: `bad` = this lane saw a sentinel word.  True when the wave has to load again.
+// this kernel's switch and limits on the shared poll loop
 __device__ __forceinline__ bool poll_again(LSync& sy, bool bad, unsigned& spins) {
 #ifdef JEN1_LONG_EXP_NOWAIT      // timing experiment only (results are garbage): no dependency waits at all
   return false;
 #endif
-  if (!__builtin_amdgcn_ballot_w64(bad) || sy.dead) return false;
-  ++spins;
-  if ((spins & 63u) == 0u) {
-    const unsigned ev = __hip_atomic_load(g32(sy.err), RLX_AGENT);
-    if (rfl((int)ev) != 0) { sy.dead = true; return false; }
-  }
-  if (spins > JEN1_LONG_POLL_LIMIT) {
-    if ((threadIdx.x & 63) == 0) __hip_atomic_store(g32(sy.err), (unsigned)(sy.p + 1), RLX_AGENT);
-    sy.dead = true;
-    return false;
-  }
-#if JEN1_LONG_POLL_SLEEP > 0
-  __builtin_amdgcn_s_sleep(JEN1_LONG_POLL_SLEEP);
-#endif
-  return true;
+  return live_poll_again<JEN1_LONG_POLL_LIMIT, JEN1_LONG_POLL_SLEEP>(sy, bad, spins);
 }
 
 // the staging vector -> its global address; which of the four sources it comes from by explicit selects
@@ -288,8 +135,8 @@ __device__ __forceinline__ const T* src_vec_ptr(const SrcTab t, int v, bool& lv)
 
 // ---- (0) the unit's weight slice: wave wv owns M tile mblk * 8 + wv; the first RING k-steps -------------------------------------------
 template <typename T>
-__device__ __forceinline__ void ring_fill(const DescRegs& dr, int slot, int lane, int wv, typename LFrag<T>::type (&ringA)[LongCfg<T>::RING / 2],
-                                          typename LFrag<T>::type (&ringB)[LongCfg<T>::RING / 2]) {
+__device__ __forceinline__ void ring_fill(const DescRegs& dr, int slot, int lane, int wv, typename Frag8<T>::type (&ringA)[LongCfg<T>::RING / 2],
+                                          typename Frag8<T>::type (&ringB)[LongCfg<T>::RING / 2]) {
   constexpr int HR = LongCfg<T>::RING / 2;
   constexpr unsigned ES = sizeof(T), BLK = 512 * ES;
   const int MT = LI(MT), KS = LI(KS);
@@ -309,10 +156,10 @@ __device__ __forceinline__ void ring_fill(const DescRegs& dr, int slot, int lane
 // one unit: sample b, slot (= entry index of its partials) of phase dr
 // ======================================================================================================================================
 template <typename T, bool LOC>
-__device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, LSync& sy, typename LFrag<T>::type (&ringA)[LongCfg<T>::RING / 2],
-                                          typename LFrag<T>::type (&ringB)[LongCfg<T>::RING / 2], int tid) {
+__device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, LSync& sy, typename Frag8<T>::type (&ringA)[LongCfg<T>::RING / 2],
+                                          typename Frag8<T>::type (&ringB)[LongCfg<T>::RING / 2], int tid) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  typedef typename LFrag<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   constexpr bool PRECISE = is_f32<T>::value;
   constexpr int RING = LongCfg<T>::RING, MAXVB = LongCfg<T>::MAXVB;
   constexpr unsigned ES = sizeof(T), BLK = 512 * ES;
@@ -641,7 +488,7 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
         auto bload = [&](Frag (&dst)[NFW], int off) __attribute__((always_inline)) {
           const T* bp = tile + off;
 #pragma unroll
-          for (int nf = 0; nf < NFW; ++nf) llds(dst[nf], bp + ldsrow[nf]);
+          for (int nf = 0; nf < NFW; ++nf) lds_frag(dst[nf], bp + ldsrow[nf]);
         };
         // straight-line, no guard per k-step (a conditional LDS read makes the compiler wait for ALL reads in flight at every join): a
         // k-step beyond KS multiplies a ZERO weight fragment (ring slots beyond the slice are out-of-range loads) with the tile's first
@@ -652,7 +499,7 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
         for (int s = 0; s < HR; ++s) {
           if (s + D - 1 < HR) bload(bb[(s + D - 1) % D], koff(ksb + s + D - 1, ((s + D - 1) & 1) != 0));
 #pragma unroll
-          for (int nf = 0; nf < NFW; ++nf) lmma(acc[nf], rg[s], bb[s % D][nf]);
+          for (int nf = 0; nf < NFW; ++nf) mma(acc[nf], rg[s], bb[s % D][nf]);
           __builtin_amdgcn_sched_barrier(0);
         }
       };
@@ -719,7 +566,7 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
     }
     if (out_part) {
       // the wave's 16 channels x its valid positions: all 64 lanes, fixed tree, one word
-      gs = row16_sum_l(gs); gq = row16_sum_l(gq);
+      gs = row16_sum(gs); gq = row16_sum(gq);
       const float ts = (rlane(gs, 0) + rlane(gs, 16)) + (rlane(gs, 32) + rlane(gs, 48));
       const float tq = (rlane(gq, 0) + rlane(gq, 16)) + (rlane(gq, 32) + rlane(gq, 48));
       if (lane == 0) {
@@ -740,7 +587,7 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
 // it can share the GPU with other persistent launches.  No cross-phase prefetch: slower, safe.
 template <typename T, bool TK, bool LOC>
 __global__ __launch_bounds__(NT) void long_kernel(const unsigned char* __restrict__ descs, int n_phases, int Bs, unsigned* err, unsigned* ticket) {
-  typedef typename LFrag<T>::type Frag;
+  typedef typename Frag8<T>::type Frag;
   constexpr int RING = LongCfg<T>::RING;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = rfl(tid >> 6);

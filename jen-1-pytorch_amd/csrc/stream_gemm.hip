@@ -19,7 +19,7 @@
 //     (at T' = 1 that is 2/3 of a k=3 conv) -- exact.
 //   * 16-row M tile per workgroup, the 4 waves split K and reduce through LDS; optional
 //     inter-workgroup split-K with write-through slabs + ticket (cdna_hip_programming.md G16 R1).
-#include "common.h"
+#include "mfma_frag.h"
 
 #ifdef JEN1_PROFILE
 #define SG_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0 && a.dbg) \
@@ -29,9 +29,6 @@
 #endif
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct SegDev {
   const void* x;      // [B][L_in][ld]
@@ -113,38 +110,6 @@ __device__ __forceinline__ EpiArgs load_epi_args() {
 #pragma unroll
   for (int i = 0; i < 4; ++i) raw.d[32 + i] = k2[i];
   return __builtin_bit_cast(EpiArgs, raw);
-}
-
-constexpr unsigned OOB = 0x80000000u;     // per-lane offset beyond every descriptor range: loads return 0
-constexpr int RSRC_FLAGS = 0x00020000;
-
-template <typename T> struct Frag8;
-template <> struct Frag8<bf16_t> { typedef bf16x8 type; };
-template <> struct Frag8<float> { typedef f32x8 type; };
-
-__device__ __forceinline__ void mma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
-
-// one 8-element fragment through a buffer descriptor: address = base + voff + soff
-template <int AUX>
-__device__ __forceinline__ void bload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX);
-  f = __builtin_bit_cast(bf16x8, v);
-}
-template <int AUX>
-__device__ __forceinline__ void bload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16u, soff, AUX);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f.v[j] = __uint_as_float(lo[j]);
-    f.v[4 + j] = __uint_as_float(hi[j]);
-  }
 }
 
 #ifndef JEN1_X_AUX
@@ -278,9 +243,9 @@ __global__ __launch_bounds__(64 * SG_NW) void stream_gemm_kernel(const StreamArg
     }
   }
   auto issue = [&](Frag& fa, Frag(&fb)[NF]) {
-    bload<JEN1_W_AUX>(fa, rw, voffA, soffA);
+    buf_frag<JEN1_W_AUX>(fa, rw, voffA, soffA);
 #pragma unroll
-    for (int nf = 0; nf < NF; ++nf) bload<JEN1_X_AUX>(fb[nf], rx, voff[nf], soffB);
+    for (int nf = 0; nf < NF; ++nf) buf_frag<JEN1_X_AUX>(fb[nf], rx, voff[nf], soffB);
     if (!parked) {
       ++issued;
       cur_g += SG_NW;

@@ -13,7 +13,7 @@
 // product through a 16 x N LDS tile of its own (the accumulator layout has the key on the lane, the A operand wants it along K).
 // Operand fragments are 16 bytes per lane: 8 bf16 = one 16x16x32 step, or 4 floats = four 16x16x4 steps whose K order is the same
 // permutation on both operands.
-#include "common.h"
+#include "mfma_frag.h"
 #include "jen1_t5.h"
 
 namespace {
@@ -27,10 +27,8 @@ template <typename T> struct TaFrag;
 template <> struct TaFrag<bf16_t> { typedef bf16x8 type; };
 template <> struct TaFrag<float> { typedef f32x4 type; };
 
-__device__ __forceinline__ void ta_mma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void ta_mma(f32x4& acc, const f32x4& a, const f32x4& b) {
+using ::mma;      // the bf16 step (mfma_frag.h); this kernel's float32 fragments hold 4 elements, not 8
+__device__ __forceinline__ void mma(f32x4& acc, const f32x4& a, const f32x4& b) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
 }
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(T5_NT) void t5_attn_kernel(const T* __restrict__ qk
           const int k = q * KC + g * EV;
           Frag kf = zero;
           if (k < d) kf = *reinterpret_cast<const Frag*>(Ks + (t * 16 + c16) * KP + k);
-          ta_mma(acc[t], qf[q], kf);
+          mma(acc[t], qf[q], kf);
         }
       }
     }
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(T5_NT) void t5_attn_kernel(const T* __restrict__ qk
     if (ct * 16 < d) {
       f32x4 oa = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int k = g * EV; k < Np; k += KC)
-        ta_mma(oa, *reinterpret_cast<const Frag*>(Ps + c16 * PP + k), *reinterpret_cast<const Frag*>(Vt + (ct * 16 + c16) * VP + k));
+        mma(oa, *reinterpret_cast<const Frag*>(Ps + c16 * PP + k), *reinterpret_cast<const Frag*>(Vt + (ct * 16 + c16) * VP + k));
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = row0 + g * 4 + r;

@@ -17,12 +17,10 @@
 //   * the activation tile (+ conv halo) is staged once in LDS, taps are row-shifted views of it; weights
 //     stream from L2 through a register ring with scalar offsets;
 //   * 4 waves x (16 MF) output rows x (16 NF) positions, v_mfma_f32_16x16x32_bf16 / 16x16x4_f32.
-#include "common.h"
+#include "mfma_frag.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
 
 struct TileHot {                 // 48 dwords: read before the first load is issued
@@ -100,55 +98,9 @@ __device__ __forceinline__ TileEpi load_tile_epi() {
   return __builtin_bit_cast(TileEpi, raw);
 }
 
-constexpr unsigned OOB = 0x80000000u;
-constexpr int RSRC_FLAGS = 0x00020000;
-
-template <typename T> struct Frag8;
-template <> struct Frag8<bf16_t> { typedef bf16x8 type; };
-template <> struct Frag8<float> { typedef f32x8 type; };
-
-__device__ __forceinline__ void mma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
-}
 #ifndef JEN1_TILE_W_AUX
 #define JEN1_TILE_W_AUX 0      // cache policy of the weight ring (2 = nt)
 #endif
-__device__ __forceinline__ void bload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  f = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, JEN1_TILE_W_AUX));
-}
-__device__ __forceinline__ void bload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, JEN1_TILE_W_AUX);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16u, soff, JEN1_TILE_W_AUX);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f.v[j] = __uint_as_float(lo[j]);
-    f.v[4 + j] = __uint_as_float(hi[j]);
-  }
-}
-__device__ __forceinline__ void lds_read(bf16x8& f, const bf16_t* p) { f = *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ void lds_read(f32x8& f, const float* p) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w;
-  f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
-}
-
-// sum over the 16 lanes of a DPP row (the 16 positions of an MFMA tile) without touching LDS
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
-  v += dpp_f<0x141>(v);     // row_half_mirror
-  v += dpp_f<0x140>(v);     // row_mirror
-  return v;
-}
 
 constexpr int VB = 4;          // staging vectors (8 channels) per thread per batch
 
@@ -215,7 +167,7 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
   auto issueA = [&](Frag(&dst)[MF]) {
     const unsigned so = issuedA < KS ? soffA : 0u;
 #pragma unroll
-    for (int mf = 0; mf < MF; ++mf) bload(dst[mf], rw, issuedA < KS ? voffA[mf] : OOB, so);
+    for (int mf = 0; mf < MF; ++mf) buf_frag<JEN1_TILE_W_AUX>(dst[mf], rw, issuedA < KS ? voffA[mf] : OOB, so);
     soffA += stepA;
     ++issuedA;
   };
@@ -413,7 +365,7 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
         const T* bp = tile + c_tap * ldsld + c_kc * 32;
         Frag bfr[NF];
 #pragma unroll
-        for (int nf = 0; nf < NF; ++nf) lds_read(bfr[nf], bp + ldsrow[nf]);
+        for (int nf = 0; nf < NF; ++nf) lds_frag(bfr[nf], bp + ldsrow[nf]);
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf)
 #pragma unroll

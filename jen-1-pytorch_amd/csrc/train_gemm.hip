@@ -8,7 +8,7 @@
 // with the next step's global loads in flight during the MFMAs.  Operands that are contiguous along the output
 // row instead of along K (data gradient's weights, every weight-gradient operand) are transposed on the way into
 // LDS, so the MFMA fragments are always 8 consecutive K values of one row.
-#include "common.h"
+#include "mfma_frag.h"
 #include "jen1_train.h"
 #include <stdlib.h>
 
@@ -237,10 +237,6 @@ __device__ __forceinline__ void mma8(f32x4& acc, const float* a, const float* b)
 // A lane's MFMA fragment (row lane % 16, 8 consecutive k at (lane / 16) * 8) IS 16 contiguous bytes of its row, so the
 // fragments come straight from global memory through buffer descriptors (rows in the padding / beyond M, N, K read as
 // zero through an out-of-range offset): no LDS, no barriers in the K loop, PF steps of loads in flight per wave.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned D_OOB = 0x80000000u;
-constexpr int D_RSRC_FLAGS = 0x00020000;
-
 template <typename T> struct DFrag;
 template <> struct DFrag<bf16_t> { typedef bf16x8 type; static constexpr int PF = 4; };
 template <> struct DFrag<float> { typedef f32x8 type; static constexpr int PF = 2; };
@@ -250,16 +246,9 @@ __device__ __forceinline__ void dload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsig
 }
 __device__ __forceinline__ void dload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff) {
   const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff == D_OOB ? D_OOB : voff + 16u, 0, 0);
+  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff == OOB ? OOB : voff + 16u, 0, 0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) { f.v[j] = __uint_as_float(lo[j]); f.v[4 + j] = __uint_as_float(hi[j]); }
-}
-__device__ __forceinline__ void dmma(f32x4& acc, const bf16x8& a, const bf16x8& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-__device__ __forceinline__ void dmma(f32x4& acc, const f32x8& a, const f32x8& b) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
 }
 
 template <typename T, int PFX = 0>
@@ -268,8 +257,8 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
   typedef typename DFrag<T>::type Frag;
   constexpr int PF = PFX > 0 ? PFX : DFrag<T>::PF;
   constexpr unsigned ES = sizeof(T);
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(abase), 0, 0x7fffffff, D_RSRC_FLAGS);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(bbase), 0, 0x7fffffff, D_RSRC_FLAGS);
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(abase), 0, 0x7fffffff, RSRC_FLAGS);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(bbase), 0, 0x7fffffff, RSRC_FLAGS);
   const int li = lane & 15, kq = (lane >> 4) * 8;
   int a_b[2], a_t[2], a_s[2], a_row[2];
   bool a_ok[2];
@@ -283,7 +272,7 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
     a_t[i] = (g.a.map_axis == 1) ? r - a_b[i] * g.a.map_L : 0;
     a_s[i] = (g.a.map_axis == 1 && a_ok[i]) ? shift_of(g.a, a_b[i]) : 0;
     const int n = n0 + wn * 32 + i * 16 + li;
-    b_off[i] = n < g.N ? (unsigned)((long long)n * g.b.ld_r) * ES : D_OOB;
+    b_off[i] = n < g.N ? (unsigned)((long long)n * g.b.ld_r) * ES : OOB;
   }
   Frag fa[PF][2], fb[PF][2];
   // The byte offsets of this lane's rows are functions of the TAP only: they are computed when the walk enters a tap (one division
@@ -298,8 +287,8 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
     for (int i = 0; i < 2; ++i) {
       long long row = a_row[i];
       if (g.a.map_axis == 1) row = map_from_bt(g.a, a_b[i], a_t[i], tap, a_s[i]);
-      a_base[i] = (a_ok[i] && row >= 0) ? (unsigned)(((long long)tap * g.a.tap_stride + row * g.a.ld_r) * ES) : D_OOB;
-      b_base[i] = b_off[i] != D_OOB ? b_off[i] + (unsigned)((long long)tap * g.b.tap_stride * ES) : D_OOB;
+      a_base[i] = (a_ok[i] && row >= 0) ? (unsigned)(((long long)tap * g.a.tap_stride + row * g.a.ld_r) * ES) : OOB;
+      b_base[i] = b_off[i] != OOB ? b_off[i] + (unsigned)((long long)tap * g.b.tap_stride * ES) : OOB;
     }
   };
   enter_tap(cur_tap);
@@ -309,8 +298,8 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
     const unsigned kb = (unsigned)k * ES;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      dload(xa[i], ra, (live && a_base[i] != D_OOB) ? a_base[i] + kb : D_OOB);
-      dload(xb[i], rb, (live && b_base[i] != D_OOB) ? b_base[i] + kb : D_OOB);
+      dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB);
+      dload(xb[i], rb, (live && b_base[i] != OOB) ? b_base[i] + kb : OOB);
     }
     ++s_next;
     if (++kidx >= ksteps) { kidx = 0; enter_tap(++cur_tap); }
@@ -324,7 +313,7 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) dmma(acc[mi][ni], fa[u][mi], fb[u][ni]);
+          for (int ni = 0; ni < 2; ++ni) mma(acc[mi][ni], fa[u][mi], fb[u][ni]);
       }
       issue(fa[u], fb[u]);
     }
@@ -615,8 +604,8 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
   const int total = ksteps * g.taps;
   const int per = (total + g.splitk - 1) / g.splitk;
   const int s_begin = split * per, s_end = min(total, s_begin + per);
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(abase), 0, 0x7fffffff, D_RSRC_FLAGS);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(bbase), 0, 0x7fffffff, D_RSRC_FLAGS);
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(abase), 0, 0x7fffffff, RSRC_FLAGS);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(bbase), 0, 0x7fffffff, RSRC_FLAGS);
   const int li = lane & 15, kq = (lane >> 4) * 8;
   int a_b[2], a_t[2], a_s[2], a_row[2];
   bool a_ok[2];
@@ -630,7 +619,7 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
     a_s[i] = (g.a.map_axis == 1 && a_ok[i]) ? shift_of(g.a, a_b[i]) : 0;
   }
   const int nb = n0 + li;
-  const unsigned b_off = nb < g.N ? (unsigned)((long long)nb * g.b.ld_r) * ES : D_OOB;
+  const unsigned b_off = nb < g.N ? (unsigned)((long long)nb * g.b.ld_r) * ES : OOB;
   float bias_v = 0.f;
   if (g.bias != nullptr && wave == 0 && split == 0) bias_v = nb < g.N ? g.bias[nb] : 0.f;
   f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -645,9 +634,9 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
     for (int i = 0; i < 2; ++i) {
       long long row = a_row[i];
       if (g.a.map_axis == 1) row = map_from_bt(g.a, a_b[i], a_t[i], tap, a_s[i]);
-      a_base[i] = (a_ok[i] && row >= 0) ? (unsigned)(((long long)tap * g.a.tap_stride + row * g.a.ld_r) * ES) : D_OOB;
+      a_base[i] = (a_ok[i] && row >= 0) ? (unsigned)(((long long)tap * g.a.tap_stride + row * g.a.ld_r) * ES) : OOB;
     }
-    b_base = b_off != D_OOB ? b_off + (unsigned)((long long)tap * g.b.tap_stride * ES) : D_OOB;
+    b_base = b_off != OOB ? b_off + (unsigned)((long long)tap * g.b.tap_stride * ES) : OOB;
   };
   enter_tap(cur_tap);
   auto issue = [&](Frag (&xa)[2], Frag& xb) {
@@ -655,8 +644,8 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
     const bool live = s_next < s_end && k < g.K;
     const unsigned kb = (unsigned)k * ES;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) dload(xa[i], ra, (live && a_base[i] != D_OOB) ? a_base[i] + kb : D_OOB);
-    dload(xb, rb, (live && b_base != D_OOB) ? b_base + kb : D_OOB);
+    for (int i = 0; i < 2; ++i) dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB);
+    dload(xb, rb, (live && b_base != OOB) ? b_base + kb : OOB);
     s_next += NW;
     kidx += NW;
     if (kidx >= ksteps) {
@@ -670,8 +659,8 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       if (c + u * NW < s_end) {
-        dmma(acc[0], fa[u][0], fb[u]);
-        dmma(acc[1], fa[u][1], fb[u]);
+        mma(acc[0], fa[u][0], fb[u]);
+        mma(acc[1], fa[u][1], fb[u]);
       }
       issue(fa[u], fb[u]);
     }
