@@ -281,6 +281,31 @@ int jen1_linear_f32(const float* x, const float* w, const float* bias, float* y,
                     int out_features, int act, void* stream);
 
 /*
+ * Global conditioning (csrc/global_cond.hip).
+ *
+ * jen1_features_into_mapping: tf[r][:] += GELU(w feat[r % B] + bias), float32 (model.py:91-98 ``to_features`` = Linear(F, mf) + GELU,
+ * summed with ``to_time(t)`` in get_mapping, model.py:204-223).  feat [B][F], w [mf][F], tf [rows][mf] with rows a multiple of B: B in
+ * the general forward, S * B in a sampler's mapping table (row s B + b = schedule entry s of batch element b).
+ *
+ * jen1_film_select: film_cur[0 .. B) = film[step B .. step B + B), the same for film2 (NULL together: one table), step = step_idx[0]
+ * read on the device and clamped to [0, n_steps).  Tables of film_ld floats per row, film_ld a multiple of 4, 16-byte aligned: one
+ * float4 per thread, no atomics.  The head of a sampler step whose FiLM rows differ per batch element.
+ *
+ * jen1_cond_embed: the Int / Number conditioners of jen1/conditioners.py:118-170 for n values x[n] (float32), out [n][D] float32.
+ *   kind 0 (IntConditioner):    out[i] = table[(int) clamp(x[i], min_val, max_val)], table [rows_or_half][D] (the reference indexes with
+ *                               the clamped value itself; the row is also kept inside the table)
+ *   kind 1 (NumberConditioner): xn = (clamp(x[i]) - min_val) / range with range = (float)(max_val - min_val) formed in double by the
+ *                               caller, as the reference forms it in Python (kind 0 ignores it), f = [xn, sin(2 pi xn freq), cos(2 pi xn freq)],
+ *                               out[i] = table f + bias with table = the Linear's weight [D][2 rows_or_half + 1], freq [rows_or_half]
+ */
+int jen1_features_into_mapping(const float* feat, const float* w, const float* bias, float* tf, int rows, int B, int F, int mf,
+                               void* stream);
+int jen1_film_select(const float* film, const float* film2, float* film_cur, float* film2_cur, const int32_t* step_idx, int B,
+                     int film_ld, int n_steps, void* stream);
+int jen1_cond_embed(const float* x, int kind, const float* table, const float* freq, const float* bias, float* out, int n, int D,
+                    int rows_or_half, float min_val, float max_val, float range, void* stream);
+
+/*
  * CFG combine + std-rescale (model.py:362-369) fused with model_predictions and the
  * DDIM update (gdm.py:128-131, :212-222).
  *   net: channel-last [nrep*B][T][ld] denoiser output (nrep = 2: cond rows then uncond rows)

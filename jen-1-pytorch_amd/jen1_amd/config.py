@@ -237,7 +237,7 @@ class UNetSpec:
         # in the reference config): fail loudly instead of silently diverging.
         for flag in ("use_snake", "use_stft", "use_stft_context", "use_nearest_upsample"):
             assert not g(flag, False), f"{flag}=True is outside the JEN-1 hot path (SURVEY.md section 2)"
-        assert self.context_features is None, "global_cond / context_features is unused on the JEN-1 path"
+        assert self.context_features is None or int(self.context_features) >= 1, "context_features must be a positive width"
         assert self.patch_size == 1, "patch_size != 1 is unused on the JEN-1 path"
         assert self.use_context_time, "use_context_time=False is unused on the JEN-1 path"
         assert self.kmul % 2 == 0, "Kernel multiplier must be even"   # blocks.py:58
@@ -310,6 +310,8 @@ class UNetSpec:
         lin("to_mapping.2", mf, mf)
         S.append(("to_time.0.0.weights", (half,)))
         lin("to_time.0.1", mf, self.channels + 1)
+        if self.context_features is not None:        # model.py:91-98: registered directly after to_time
+            lin("to_features.0", mf, int(self.context_features))
 
         def res(r: ResSpec):
             S.extend(res_param_shapes(r.name, r.c_in, r.c_out, mf))

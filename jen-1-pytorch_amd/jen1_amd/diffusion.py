@@ -42,6 +42,31 @@ def _tail_eligible(poison_args) -> bool:
             and int(zero_bytes) > 0 and int(zero_bytes) % 16 == 0)
 
 
+# a sampler on global conditioning keeps its FiLM tables per (schedule entry, batch element): 2 * S * B * film_ld * 4 bytes.  Beyond this
+# budget (bytes; env JEN1_FILM_TABLE_BUDGET) the fused stepper is refused and the literal loop -- the general forward per step -- runs
+FILM_TABLE_BUDGET = 1 << 30
+
+
+def has_global_cond(model, conditioning) -> bool:
+    """whether a sampling run of ``model`` reads ``conditioning["global_cond"]`` (a model without ``context_features`` ignores it)"""
+    spec = getattr(model, "spec", None)
+    return (spec is not None and spec.context_features is not None and conditioning is not None
+            and conditioning.get("global_cond") is not None)
+
+
+def film_table_bytes(model, batch: int, steps: int) -> int:
+    """bytes of the two per-sample FiLM tables of a ``steps``-entry schedule at this batch"""
+    film_ld = sum(2 * r.c_out for r in model.spec.res_blocks())
+    return 2 * int(steps) * int(batch) * film_ld * 4
+
+
+def film_tables_fit(model, conditioning, batch: int, steps: int) -> bool:
+    if not has_global_cond(model, conditioning):
+        return True
+    budget = int(os.environ.get("JEN1_FILM_TABLE_BUDGET", FILM_TABLE_BUDGET))
+    return film_table_bytes(model, batch, steps) <= budget
+
+
 def get_beta_schedule(schedule_name: str, num_diffusion_timesteps: int):
     """-> (betas, None)  (reference noise_schedule.py:7-31)."""
     n = num_diffusion_timesteps
@@ -263,9 +288,11 @@ class GaussianDiffusion(torch.nn.Module):
         p0, q0 = torch.tensor(level(t0), dtype=torch.float32).tolist()
         return kb.to(self.device), (p0, q0)
 
-    def _fused_ok(self, model) -> bool:
-        """the fused stepper covers UNetCFG1d with the CFG pair batched (or no CFG at all)"""
-        return isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+    def _fused_ok(self, model, conditioning=None, batch: int = 0, steps: int = 0) -> bool:
+        """the fused stepper covers UNetCFG1d with the CFG pair batched (or no CFG at all); with global conditioning, as long as the
+        per-sample FiLM tables of the schedule stay inside ``FILM_TABLE_BUDGET``"""
+        return (isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+                and film_tables_fit(model, conditioning, batch, steps))
 
     def _fused_loop(self, st: "DDIMStepper", shape, return_all_timesteps, init_data, init_noise, step_noises, dropout_rows,
                     known=None, keep=None, known_noise=None):
@@ -304,15 +331,16 @@ class GaussianDiffusion(torch.nn.Module):
     def ddim_sample(self, model, shape, conditioning, return_all_timesteps=False, causal=False, init_data=None, *,
                     init_noise=None, step_noises: Optional[Sequence[torch.Tensor]] = None,
                     dropout_rows: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True,
-                    known=None, keep_mask=None, known_noise=None):
+                    known=None, keep_mask=None, known_noise=None, fused: bool = True):
         """gdm.py:181-225.  The keyword-only extras inject the RNG draws (parity tests);
-        by default they come from torch's device generator like the reference's.
+        by default they come from torch's device generator like the reference's.  ``fused=False`` runs the literal loop
+        (as in ``p_sample_loop``).
 
         ``known`` [B, C, T] + ``keep_mask`` [B, 1, T] (1 = keep, 0 = generate; not in the reference): the kept frames are pinned to
         the known latents -- blended in at the noise level of every step (``blend_table``) and exactly at the end -- instead of being
         regenerated; ``known_noise`` is the fixed noise of the known region (default: the start draw)."""
         known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
-        if not self._fused_ok(model):
+        if not (fused and self._fused_ok(model, conditioning, shape[0], self.sampling_timesteps)):
             return self._ddim_generic(model, shape, conditioning, return_all_timesteps, causal, init_data,
                                       init_noise, step_noises, dropout_rows, known, keep_mask, known_noise)
         st = self.stepper(model, shape, conditioning, causal=causal, use_graph=use_graph, blend=known is not None)
@@ -332,7 +360,7 @@ class GaussianDiffusion(torch.nn.Module):
         key = (id(model), id(model.engine()), tuple(shape), bool(causal), bool(use_graph), n_streams, plan_slot, mode,
                float(self.embedding_scale), bool(self.batch_cfg), bool(self.scale_cfg), getattr(self, "sampling_timesteps", None),
                float(getattr(self, "ddim_sampling_eta", 0.0)), bool(model.deterministic), bool(model.engine().use_tile_phases),
-               bool(blend), int(order) if mode == "dpmpp" else None)
+               bool(blend), int(order) if mode == "dpmpp" else None, has_global_cond(model, conditioning))
         st = cache.get(key)
         if st is not None and st.model is model and st.eng is model.engine():
             st.rebind(conditioning)
@@ -389,7 +417,7 @@ class GaussianDiffusion(torch.nn.Module):
         if order not in (1, 2):
             raise ValueError(f"dpm_sample: order must be 1 or 2, not {order!r}")
         known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
-        if not (self._fused_ok(model) and _step_pack_enabled(model)):
+        if not (self._fused_ok(model, conditioning, shape[0], self.sampling_timesteps) and _step_pack_enabled(model)):
             return self._dpm_generic(model, shape, conditioning, return_all_timesteps, causal, init_data, init_noise, dropout_rows,
                                      order, known, keep_mask, known_noise)
         st = self.stepper(model, shape, conditioning, causal=causal, use_graph=use_graph, mode="dpmpp", blend=known is not None,
@@ -454,7 +482,7 @@ class GaussianDiffusion(torch.nn.Module):
         ``fused=False`` (or any other callable) runs the literal loop below.  ``known`` / ``keep_mask`` / ``known_noise``: as in
         ``ddim_sample``."""
         known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
-        if fused and self._fused_ok(model):
+        if fused and self._fused_ok(model, conditioning, shape[0], self.num_timesteps):
             st = self.stepper(model, shape, conditioning, causal=False, use_graph=use_graph, mode="ddpm",   # causal is not forwarded (gdm.py:145)
                               blend=known is not None)
             return self._fused_loop(st, shape, return_all_timesteps, init_data, init_noise, step_noises, dropout_rows,
@@ -605,6 +633,9 @@ class DDIMStepper:
         cfg = gd.embedding_scale != 1.0
         assert not (cfg and not gd.batch_cfg), "the fused stepper needs batch_cfg=True when embedding_scale != 1"
         self.nrep = 2 if cfg else 1
+        # global conditioning: the mapping differs per batch element, the plan keeps per-sample tables (engine.Plan(per_sample=True))
+        self.per_sample = has_global_cond(model, conditioning)
+        assert self.per_sample or model.spec.context_features is None, "context_features exists but no features provided"   # model.py:216
         if n_streams is None:
             n_streams = int(os.environ.get("JEN1_STREAMS", "1"))
         n_streams = max(1, min(n_streams, B))
@@ -636,7 +667,7 @@ class DDIMStepper:
             slot = used.get(nb, 0)
             used[nb] = slot + 1
             # plan_slot: independent samplers of the same shape that run concurrently (serving) own separate buffers
-            plan = eng.plan(nb, T, self.nrep, bool(causal), slot=slot + 1000 * plan_slot, n_t=S)
+            plan = eng.plan(nb, T, self.nrep, bool(causal), slot=slot + 1000 * plan_slot, n_t=S, per_sample=self.per_sample)
             sl = slice(b0, b0 + nb)
             self._bind(plan, sl, conditioning)
             self._fill_times(plan, s0)                # FiLM / time-token K/V tables for all S timesteps
@@ -768,7 +799,11 @@ class DDIMStepper:
         emb = conditioning["cross_attn_cond"][sl]
         msk = None if conditioning["cross_attn_masks"] is None else conditioning["cross_attn_masks"][sl]
         cc = conditioning["input_concat_cond"]
-        self.model._prepare(plan, plan.x_in, None, emb, msk, [None if cc is None else cc[sl]], None)
+        feat = None
+        if self.per_sample:
+            assert conditioning.get("global_cond") is not None, "context_features exists but no features provided"
+            feat = conditioning["global_cond"][sl]
+        self.model._prepare(plan, plan.x_in, None, emb, msk, [None if cc is None else cc[sl]], None, features=feat)
         plan._cond_refs = (emb, msk)                  # the K/V cache key holds weakrefs: keep the slices alive
 
     def _fill_times(self, plan, stream=None) -> None:
@@ -794,7 +829,9 @@ class DDIMStepper:
         self._cond = conditioning
         for p in self.parts:
             self._bind(p.plan, p.sl, conditioning)
-            if getattr(p.plan, "_stepper_token", None) is not self._token:
+            # (per-sample tables hold mapping(t_s, features_b): features are per trajectory, so they are filled again for every
+            # conditioning -- tables kept from the last run would condition this one on the last run's features)
+            if self.per_sample or getattr(p.plan, "_stepper_token", None) is not self._token:
                 self._fill_times(p.plan)
         self._pack_dirty = True                    # (the concat context is part of the packed rows)
 

@@ -94,6 +94,9 @@ class Weights:
         for k in ("to_time.0.0.weights", "to_time.0.1.weight", "to_time.0.1.bias", "to_mapping.0.weight",
                   "to_mapping.0.bias", "to_mapping.2.weight", "to_mapping.2.bias"):
             self.v[k] = f32(p[k])
+        if spec.context_features is not None:          # global conditioning (model.py:91-98), float32 like the rest of the mapping
+            for k in ("to_features.0.weight", "to_features.0.bias"):
+                self.v[k] = f32(p[k])
         if spec.use_xattn_time:
             for k in ("to_time_embedding.0.0.weights", "to_time_embedding.0.1.weight", "to_time_embedding.0.1.bias"):
                 self.v[k] = f32(p[k])
@@ -1253,11 +1256,17 @@ class Plan(OpBuilder):
     """Pre-allocated buffers + prepared launches for one (B, T, nrep, causal) shape."""
 
     def __init__(self, eng: "Engine", B: int, T: int, nrep: int, causal: bool, n_t: Optional[int] = None, deep: bool = True,
-                 deterministic: bool = False):
+                 deterministic: bool = False, per_sample: bool = False):
         """n_t = None: one timestep per batch element (the general forward).  n_t = S: *table mode* of a
         sampler -- the timestep-only work (time MLP, FiLM GEMM, time-token K/V GEMM) is evaluated once for
         all S schedule entries (``run_time``) and every kernel of the step indexes the tables through the
         device-side counter ``step_idx``, so a captured step replays with no host-side update.
+
+        per_sample (table mode of a model with ``context_features``): the mapping depends on the batch element's ``features`` too, so
+        the mapping tables (tf, m1, mapping, film, film2) have S * B rows -- row s B + b = mapping(t_s, features_b) -- and every FiLM
+        consumer is built as in the general forward (no ``film_step``, row ``film_row[b]``) on CURRENT tables of B rows that a
+        selection launch at the head of the step (``jen1_film_select``, kind "film_select") copies out of the S * B ones.  The
+        time-token K/V table does not depend on features and keeps its S rows.
 
         deep: run the levels with few positions as ONE persistent launch (DeepProgram).  The first level of that launch
         is the shallowest one whose every layer fits (``deep_level``); levels above it keep one launch per layer.
@@ -1270,6 +1279,9 @@ class Plan(OpBuilder):
         self.Beff = B * nrep
         self.table_mode = n_t is not None
         self.n_t = n_t if n_t is not None else B
+        self.has_features = eng.spec.context_features is not None
+        self.per_sample = bool(per_sample) and self.table_mode and self.has_features
+        assert not (self.table_mode and self.has_features and not self.per_sample), "context_features exists but no features provided"
         lens = eng.spec.level_lengths(T)
         n_lv = len(eng.spec.downs)
         first = n_lv
@@ -1428,7 +1440,7 @@ class Plan(OpBuilder):
                   gn=(r.groups, r.c_in, W.v[f"{n}.gn1.g"], W.v[f"{n}.gn1.b"], 1e-5))
         y = self.new_act(src0.B, src0.L, r.c_out, gn=gn)
         gn2 = (r.groups, r.c_out, W.v[f"{n}.gn2.g"], W.v[f"{n}.gn2.b"], 1e-5)
-        film = (self.film, self.film_row, W.film_off[n], r.c_out, self.step_idx if self.table_mode else None)
+        film = (self.film, self.film_row, W.film_off[n], r.c_out, self.step_idx if (self.table_mode and not self.per_sample) else None)
         srcs_raw = [src0] + ([src1] if src1 is not None else [])
         # (a source with padded channels -- the 257-channel network input -- rides along only in the sample-resident launches: their extra
         # segments read the padded pitch, the padding columns meet zero weights)
@@ -1611,27 +1623,49 @@ class Plan(OpBuilder):
         # (timestep-only work: ``time_ops``; one row per batch element, or per schedule entry in table mode)
         tops = self.time_ops
         mf, half = spec.mapping_features, spec.channels // 2
-        tf = torch.empty((NT_, mf), dtype=f32, device=dev)
-        m1 = torch.empty((NT_, mf), dtype=f32, device=dev)
-        self.mapping = torch.empty((NT_, mf), dtype=f32, device=dev)
+        # rows of the mapping tables: one per timestep, or (per_sample) one per (schedule entry, batch element), s-major
+        NM = NT_ * B if self.per_sample else NT_
+        tf = torch.empty((NM, mf), dtype=f32, device=dev)
+        m1 = torch.empty((NM, mf), dtype=f32, device=dev)
+        self.mapping = torch.empty((NM, mf), dtype=f32, device=dev)
         self._keep += [tf, m1]          # referenced by raw pointer below
         v = W.v
-        a = (v["to_time.0.0.weights"].data_ptr(), v["to_time.0.1.weight"].data_ptr(), v["to_time.0.1.bias"].data_ptr(), tf.data_ptr(), NT_, half, mf)
-        tops.append(lambda s, a=a: self._time_features(a, s))
-        a = (tf.data_ptr(), v["to_mapping.0.weight"].data_ptr(), v["to_mapping.0.bias"].data_ptr(), m1.data_ptr(), NT_, mf, mf, L.ACT_GELU)
+        if self.per_sample:             # the schedule entry of every table row (set_times)
+            self.t_map = torch.zeros((NM,), dtype=torch.int64, device=dev)
+            self.t_map_f = torch.zeros((NM,), dtype=torch.float32, device=dev)
+        a = (v["to_time.0.0.weights"].data_ptr(), v["to_time.0.1.weight"].data_ptr(), v["to_time.0.1.bias"].data_ptr(), tf.data_ptr(), NM, half, mf)
+        tops.append(lambda s, a=a: self._time_features(a, s, mapping_rows=True))
+        self.feat_in = None
+        if self.has_features:
+            # model.py:218-222: the mapping's input is to_time(t) + to_features(features); both CFG halves read row b (film_row)
+            Fc = int(spec.context_features)
+            self.feat_in = torch.zeros((B, Fc), dtype=f32, device=dev)
+            a = (self.feat_in.data_ptr(), v["to_features.0.weight"].data_ptr(), v["to_features.0.bias"].data_ptr(), tf.data_ptr(), NM, B, Fc, mf)
+            fop = lambda s, a=a: L.check(lib.jen1_features_into_mapping(*a, s), "jen1_features_into_mapping")
+            fop.kind, fop.label = "features", f"to_features into {NM} mapping rows"
+            tops.append(fop)
+        a = (tf.data_ptr(), v["to_mapping.0.weight"].data_ptr(), v["to_mapping.0.bias"].data_ptr(), m1.data_ptr(), NM, mf, mf, L.ACT_GELU)
         tops.append(lambda s, a=a: L.check(lib.jen1_linear_f32(*a, s), "jen1_linear_f32"))
-        a = (m1.data_ptr(), v["to_mapping.2.weight"].data_ptr(), v["to_mapping.2.bias"].data_ptr(), self.mapping.data_ptr(), NT_, mf, mf, L.ACT_GELU)
+        a = (m1.data_ptr(), v["to_mapping.2.weight"].data_ptr(), v["to_mapping.2.bias"].data_ptr(), self.mapping.data_ptr(), NM, mf, mf, L.ACT_GELU)
         tops.append(lambda s, a=a: L.check(lib.jen1_linear_f32(*a, s), "jen1_linear_f32"))
-        map_t = Act(self._empty((1, NT_, mf)), 1, NT_, mf, mf)
+        map_t = Act(self._empty((1, NM, mf)), 1, NM, mf, mf)
         self._add_cast(tops, self.mapping, map_t.t)
-        self.film = torch.empty((NT_, W.film_ld), dtype=f32, device=dev)
-        film_act = Act(self.film.view(1, NT_, W.film_ld), 1, NT_, W.film_ld, W.film_ld)
+        film_tab = torch.empty((NM, W.film_ld), dtype=f32, device=dev)
+        film_act = Act(film_tab.view(1, NM, W.film_ld), 1, NM, W.film_ld, W.film_ld)
         self.conv(tops, src0=map_t, w=W.w["film"], bias=W.v["film.bias"], out=film_act, pro=L.PRO_SILU, y_f32=True)
         # fused GroupNorm-FiLM table of the persistent kernel: y = xhat * gamma (scale + 1) + beta (scale + 1) + shift
         # (blocks.py:141-143); timestep-only work like the FiLM GEMM itself
-        self.film2 = torch.empty_like(self.film)
-        if self.deep_level is not None or self.tile_lens:
-            film, film2, fa, fb, fp = self.film, self.film2, W.film2_a, W.film2_b, W.film2_partner
+        film2_tab = torch.empty_like(film_tab)
+        # ``film`` / ``film2``: what the FiLM consumers read -- the tables themselves, or (per_sample) the current step's B rows
+        self.film_tab, self.film2_tab = film_tab, film2_tab
+        if self.per_sample:
+            self.film = self.film_cur = torch.zeros((B, W.film_ld), dtype=f32, device=dev)
+            self.film2 = self.film2_cur = torch.zeros((B, W.film_ld), dtype=f32, device=dev)
+        else:
+            self.film, self.film2 = film_tab, film2_tab
+        has_film2 = self.deep_level is not None or bool(self.tile_lens)
+        if has_film2:
+            film, film2, fa, fb, fp = film_tab, film2_tab, W.film2_a, W.film2_b, W.film2_partner
             tmp_a, tmp_b = torch.empty_like(film), torch.empty_like(film)
 
             def film2_op(s, film=film, film2=film2, fa=fa, fb=fb, fp=fp, tmp_a=tmp_a, tmp_b=tmp_b, dev=dev):
@@ -1644,6 +1678,14 @@ class Plan(OpBuilder):
                     torch.mul(film, fb, out=tmp_b)
                     torch.add(tmp_a, tmp_b, out=film2)
             tops.append(film2_op)
+        if self.per_sample:
+            # head of every step, inside the captured graph: rows [step B, step B + B) of the tables -> the current tables
+            a = (film_tab.data_ptr(), film2_tab.data_ptr() if has_film2 else None, self.film_cur.data_ptr(),
+                 self.film2_cur.data_ptr() if has_film2 else None, self.step_idx.data_ptr(), B, W.film_ld, NT_)
+            sel = lambda s, a=a: L.check(lib.jen1_film_select(*a, s), "jen1_film_select")
+            sel.kind, sel.label = "film_select", f"film_select: {B} x {W.film_ld} floats of {'two tables' if has_film2 else 'one table'}"
+            sel.bytes = (2 if has_film2 else 1) * 2 * B * W.film_ld * 4
+            ops.append(sel)
 
         # ---- 3. time token of the text context -> its K/V row for every cross-attention ------------
         self.kv_ctx: Dict[str, torch.Tensor] = {}
@@ -1823,12 +1865,14 @@ class Plan(OpBuilder):
         self.finalize_workspace()
         self.n_launch = len(self.ops) + (0 if self.table_mode else len(self.time_ops))
 
-    def _time_features(self, a, s):
+    def _time_features(self, a, s, mapping_rows: bool = False):
+        """mapping_rows: the launch fills a mapping table, whose rows are (schedule entry, batch element) pairs in a per_sample plan"""
         lib = self.eng.lib
+        rows = mapping_rows and self.per_sample
         if self.t_float:
-            L.check(lib.jen1_time_features_f32(self.t_in_f.data_ptr(), *a, s), "jen1_time_features_f32")
+            L.check(lib.jen1_time_features_f32((self.t_map_f if rows else self.t_in_f).data_ptr(), *a, s), "jen1_time_features_f32")
         else:
-            L.check(lib.jen1_time_features(self.t_in.data_ptr(), *a, s), "jen1_time_features")
+            L.check(lib.jen1_time_features((self.t_map if rows else self.t_in).data_ptr(), *a, s), "jen1_time_features")
 
     def set_times(self, time: torch.Tensor):
         """raw int64 timesteps (GaussianDiffusion) or continuous float times (VDM) of the next ``run`` / ``run_time``"""
@@ -1838,6 +1882,17 @@ class Plan(OpBuilder):
         else:
             self.t_in.copy_(time.to(torch.int64))
             self.t_float = False
+        if self.per_sample:
+            self.t_map_f.copy_(self.t_in_f.repeat_interleave(self.B))
+            self.t_map.copy_(self.t_in.repeat_interleave(self.B))
+
+    def set_features(self, features: Optional[torch.Tensor]):
+        """the global conditioning [B, context_features] of the next ``run`` / ``run_time`` (model.py:216-217: required)"""
+        assert features is not None, "context_features exists but no features provided"
+        if tuple(features.shape) != tuple(self.feat_in.shape):
+            raise ValueError(f"features of shape {tuple(features.shape)}: this plan was built for {tuple(self.feat_in.shape)} "
+                             "(batch, context_features)")
+        self.feat_in.copy_(features.to(torch.float32))
 
     def run_time(self, stream: Optional[int] = None):
         """timestep-only work (time MLP -> FiLM table, time token -> K/V rows) for every entry of t_in"""
@@ -2019,11 +2074,12 @@ class Engine:
         torch.cuda.synchronize(dev)
 
     def plan(self, B: int, T: int, nrep: int, causal: bool, slot: int = 0, n_t: Optional[int] = None,
-             deep: Optional[bool] = None, deterministic: Optional[bool] = None) -> Plan:
+             deep: Optional[bool] = None, deterministic: Optional[bool] = None, per_sample: bool = False) -> Plan:
         """``slot`` distinguishes plans of the same shape that must own separate buffers because
         they run concurrently on different streams (sub-batches of one sampler step); ``n_t`` selects
         the sampler's table mode (see Plan).  ``deep``: use the persistent deep-level launch (default: yes).
-        ``deterministic``: fixed-order statistics (see Plan; default: ``self.deterministic``, env JEN1_DETERMINISTIC)."""
+        ``deterministic``: fixed-order statistics (see Plan; default: ``self.deterministic``, env JEN1_DETERMINISTIC).
+        ``per_sample`` (with ``n_t``, a model with ``context_features``): mapping tables per (schedule entry, batch element), see Plan."""
         if deep is None:
             # concurrent samplers (slot > 0) keep one launch per layer by default: persistent launches are safe to share the GPU
             # (tickets) but each one wants every CU, while independent launch-per-layer chains overlap -- 4 batches in flight:
@@ -2031,7 +2087,8 @@ class Engine:
             deep = slot == 0 or self.deep_all_slots
         deep = bool(deep) and self.use_deep
         det = self.deterministic if deterministic is None else bool(deterministic)
-        key = (B, T, nrep, bool(causal), slot, n_t, deep, det, self.fold_up)
+        per_sample = bool(per_sample) and n_t is not None and self.spec.context_features is not None
+        key = (B, T, nrep, bool(causal), slot, n_t, deep, det, self.fold_up) + ((True,) if per_sample else ())
         if key not in self.plans:
-            self.plans[key] = Plan(self, B, T, nrep, bool(causal), n_t, deep=deep, deterministic=det)
+            self.plans[key] = Plan(self, B, T, nrep, bool(causal), n_t, deep=deep, deterministic=det, per_sample=per_sample)
         return self.plans[key]

@@ -172,11 +172,28 @@ class Jen1:
             wav = torch.cat([wav, wav.new_zeros((wav.shape[0], wav.shape[1], missing))], dim=2)
         return wav, False, prefix
 
+    @staticmethod
+    def _metadata_rows(prompt, batch_size: int, conditions):
+        """the conditioner's metadata rows: None without ``conditions`` (the call stays ``[{"prompt": prompt}] * B``), else one dict per
+        batch row with the entries of ``conditions`` merged in"""
+        if conditions is None:
+            return None
+        if isinstance(conditions, dict):
+            conditions = [conditions] * batch_size
+        conditions = list(conditions)
+        if len(conditions) != batch_size or not all(isinstance(c, dict) for c in conditions):
+            raise ValueError(f"conditions must be a dict or a list of batch_size = {batch_size} dicts")
+        return [{"prompt": prompt, **c} for c in conditions]
+
     def generate(self, prompt, seed: int = -1, steps: int = 100, batch_size: int = 1, seconds: int = 30, use_gdm: bool = False,
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
                  inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
-                 decode: str = "whole", segment_scales: str = "unit", preserve_known: bool = False) -> torch.Tensor:
-        """``decode`` (not in the reference): ``"whole"`` hands all latents to ``audio_encoder.decoder`` in one piece, as generation.py:130
+                 decode: str = "whole", segment_scales: str = "unit", conditions=None, preserve_known: bool = False) -> torch.Tensor:
+        """``conditions`` (not in the reference, whose ``generate`` can only pass a prompt): further metadata for the conditioner --
+        a dict (the same for every row) or a list of ``batch_size`` dicts -- merged into the ``{"prompt": prompt}`` rows before the
+        conditioner is called (``jen1_amd.conditioners.MultiConditionerHIP``: tempo, key, seconds_start, ...); the entries named by
+        ``global_cond_ids`` reach the denoiser as ``features``.  None keeps the call as it was.
+        ``decode`` (not in the reference): ``"whole"`` hands all latents to ``audio_encoder.decoder`` in one piece, as generation.py:130
         does -- the latents hold the encoder's overlapping 1 s segments side by side, so 10 s come back as 1515 x 320 samples with every
         overlap played twice; ``"segments"`` undoes the encoder's layout with the codec's own decode (``audio_encoder.decode_latents``:
         per-segment decoder, linear overlap-add) and returns exactly ``seconds * sample_rate`` samples.
@@ -208,6 +225,7 @@ class Jen1:
             raise ValueError("segment_scales='known' needs known audio: task 'music_inpaint' or 'music_cont'")
         if decode == "segments" and not hasattr(self.audio_encoder, "decode_latents"):
             raise ValueError("decode='segments' needs an audio_encoder with decode_latents (jen1_amd.encodec.EncodecHIP)")
+        rows = self._metadata_rows(prompt, batch_size, conditions)
         torch.manual_seed(seed if seed != -1 else int(np.random.randint(0, 2 ** 32 - 1)))
         self.batch_size = batch_size
         diffusion, model = self.get_model_and_diffusion(steps, use_gdm)
@@ -216,7 +234,8 @@ class Jen1:
         start_s, end_s, causal = self._task_window(task, seconds, inpainting_scope, prefix)
         keep = self.get_mask(total, start_s, end_s, batch_size)                 # 1 = keep the known audio, 0 = generate
         out = self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
-                           preserve_known=preserve_known, sampler=sampler, decode=decode, segment_scales=segment_scales, length=total)
+                           preserve_known=preserve_known, sampler=sampler, decode=decode, segment_scales=segment_scales, length=total,
+                           metadata=rows)
         if output_sr is not None and int(output_sr) != self.sample_rate:
             from . import audio
             # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
@@ -226,7 +245,7 @@ class Jen1:
     @torch.no_grad()
     def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
                 steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None, decode: str = "whole",
-                segment_scales: str = "unit", length: Optional[int] = None) -> torch.Tensor:
+                segment_scales: str = "unit", length: Optional[int] = None, metadata=None) -> torch.Tensor:
         B = wav.shape[0]
         keep_samples = keep
         if decode == "segments":
@@ -235,7 +254,10 @@ class Jen1:
         else:
             known = self.get_emb(wav.to(self.device)).to(self.device)           # [B, 128, T']
         keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
-        cond = self.conditioner([{"prompt": prompt}] * B, self.device)
+        cond = self.conditioner([{"prompt": prompt}] * B if metadata is None else metadata, self.device)
+        for k in self.global_cond_ids:
+            if k not in cond:
+                raise KeyError(f"global_cond_ids names {k!r}, which the conditioner did not return (it returned {sorted(cond)})")
         cond["masked_input"] = known * keep
         cond["mask"] = keep
         cond = self.get_conditioning(cond)

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -152,6 +152,9 @@ SYMBOLS = {
     "jen1_time_features": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "jen1_time_features_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "jen1_linear_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "jen1_features_into_mapping": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "jen1_film_select": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "jen1_cond_embed": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P]),
     "jen1_cfg_ddim_step": (c_int, [_P] * 8 + [c_int] * 5 + [c_float, c_int, c_float, c_int, c_int, c_int, _P]),
     "jen1_step_advance": (c_int, [_P, _P]),
     "jen1_cfg_ddim_step_adv": (c_int, [_P] * 9 + [c_int] * 5 + [c_float, c_int, c_float, c_int, c_int, c_int, _P]),

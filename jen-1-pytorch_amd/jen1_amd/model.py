@@ -176,10 +176,12 @@ class UNetCFG1d(nn.Module):
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._device).cuda_stream
 
-    def _prepare(self, plan: Plan, x, time, embedding, embedding_mask, channels_list, drop_rows, uncond_only=False):
+    def _prepare(self, plan: Plan, x, time, embedding, embedding_mask, channels_list, drop_rows, uncond_only=False, features=None):
         plan.x_in.copy_(x.to(torch.float32))
         if not plan.table_mode:
             plan.set_times(time)
+        if plan.has_features:
+            plan.set_features(features)            # (the general forward reads them per call; a sampler's tables once per trajectory)
         if self.spec.ctx_ch0:
             assert channels_list is not None and channels_list[0] is not None, "Missing context"   # model.py:189
             ch = channels_list[0]
@@ -253,7 +255,12 @@ class UNetCFG1d(nn.Module):
         float32 [B, out_channels, T] tensor.  ``dropout_rows`` (bool[B]) optionally injects
         the CFG-dropout draw that the reference takes from ``rand_bool`` (model.py:325).
         The call goes through the dispatcher as ``torch.ops.jen1.unet_cfg_forward`` (jen1_amd/ops.py)."""
-        assert features is None, "context_features is unused on the JEN-1 path"
+        if self.spec.context_features is None:
+            features = None                            # the reference ignores them without ``context_features`` (model.py:213-217)
+        else:
+            assert features is not None, "context_features exists but no features provided"      # model.py:216
+            assert features.dim() == 2 and features.shape[1] == int(self.spec.context_features), \
+                f"features of shape {tuple(features.shape)}: expected [batch, {int(self.spec.context_features)}]"
         from . import ops as _ops  # noqa: F401  (registers torch.ops.jen1.*)
         if self._handle is None:
             self._handle = _ops.register_model(self)
@@ -263,14 +270,15 @@ class UNetCFG1d(nn.Module):
             ctx = channels_list[0]
         return torch.ops.jen1.unet_cfg_forward(self._handle, x, time, embedding, embedding_mask, ctx, float(embedding_scale),
                                                float(embedding_mask_proba), bool(batch_cfg), bool(scale_cfg), float(scale_phi), bool(causal),
-                                               dropout_rows)
+                                               dropout_rows, features)
 
     @torch.no_grad()
     def _forward_impl(self, x: torch.Tensor, time: torch.Tensor, *, embedding: torch.Tensor,
                       embedding_mask: Optional[torch.Tensor] = None, embedding_scale: float = 1.0,
                       embedding_mask_proba: float = 0.0, batch_cfg: bool = False, scale_cfg: bool = False,
                       scale_phi: float = 0.7, channels_list: Optional[Sequence[torch.Tensor]] = None,
-                      causal: Optional[bool] = False, dropout_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      causal: Optional[bool] = False, dropout_rows: Optional[torch.Tensor] = None,
+                      features: Optional[torch.Tensor] = None) -> torch.Tensor:
         """what ``torch.ops.jen1.unet_cfg_forward`` runs: plans + launches on the engine"""
         eng = self.engine()
         lib = eng.lib
@@ -291,14 +299,14 @@ class UNetCFG1d(nn.Module):
         if embedding_scale != 1.0:
             if batch_cfg:
                 plan = eng.plan(B, T, 2, causal)
-                self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop)
+                self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop, features=features)
                 plan.run(s)
                 net = plan.net_out
                 self._check_deep(plan)
             else:
                 plan = eng.plan(B, T, 1, causal)
                 both = torch.empty((2 * B, T, plan.net_out.ld), dtype=eng.tdtype, device=self._device)
-                self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop)
+                self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop, features=features)
                 plan.run(s)
                 both[:B].copy_(plan.net_out.t)
                 plan.set_rows(None, uncond_only=True)
@@ -310,7 +318,7 @@ class UNetCFG1d(nn.Module):
                                          1 if scale_cfg else 0, float(scale_phi), eng.dt, s), "jen1_cfg_combine")
             return out
         plan = eng.plan(B, T, 1, causal)
-        self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop)
+        self._prepare(plan, x, time, embedding, embedding_mask, channels_list, drop, features=features)
         plan.run(s)
         L.check(lib.jen1_unpack_output(plan.net_out.t.data_ptr(), out.data_ptr(), B, Co, T, plan.net_out.ld, eng.dt, s),
                 "jen1_unpack_output")

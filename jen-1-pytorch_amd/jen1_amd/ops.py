@@ -67,16 +67,18 @@ def _dt(t: torch.Tensor) -> int:
 @custom_op("jen1::unet_cfg_forward", mutates_args=())
 def unet_cfg_forward(handle: int, x: torch.Tensor, time: torch.Tensor, embedding: torch.Tensor, embedding_mask: Optional[torch.Tensor],
                      context: Optional[torch.Tensor], embedding_scale: float, embedding_mask_proba: float, batch_cfg: bool, scale_cfg: bool,
-                     scale_phi: float, causal: bool, dropout_rows: Optional[torch.Tensor]) -> torch.Tensor:
+                     scale_phi: float, causal: bool, dropout_rows: Optional[torch.Tensor],
+                     features: Optional[torch.Tensor] = None) -> torch.Tensor:
     m = _model(handle)
     return m._forward_impl(x, time, embedding=embedding, embedding_mask=embedding_mask, embedding_scale=embedding_scale,
                            embedding_mask_proba=embedding_mask_proba, batch_cfg=batch_cfg, scale_cfg=scale_cfg, scale_phi=scale_phi,
-                           channels_list=None if context is None else [context], causal=causal, dropout_rows=dropout_rows)
+                           channels_list=None if context is None else [context], causal=causal, dropout_rows=dropout_rows,
+                           features=features)
 
 
 @unet_cfg_forward.register_fake
 def _(handle, x, time, embedding, embedding_mask, context, embedding_scale, embedding_mask_proba, batch_cfg, scale_cfg, scale_phi, causal,
-      dropout_rows):
+      dropout_rows, features=None):
     m = _model(handle)
     return x.new_empty((x.shape[0], m.spec.out_channels, x.shape[2]), dtype=torch.float32)
 

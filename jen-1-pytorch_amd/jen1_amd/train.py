@@ -1621,10 +1621,19 @@ class TrainGraph:
             fp = torch.cat([f, fp[:, f.shape[1]:]], dim=-1)
         return linear(self.rt, fp, self.p[f"{prefix}.1.weight"], self.p[f"{prefix}.1.bias"])
 
-    def mapping(self, t: torch.Tensor) -> torch.Tensor:
-        """UNet1d.get_mapping (model.py:204-223, :75-89), float32"""
-        rt, p = self.rt, self.p
+    def mapping(self, t: torch.Tensor, features: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """UNet1d.get_mapping (model.py:204-223, :75-89), float32.  With ``context_features`` the mapping's input is the sum of
+        to_time(t) and to_features(features) (model.py:218-222); ``features`` [B, F] carries no gradient of its own (its producers are
+        outside the optimiser, like the text conditioner's projection)"""
+        rt, p, sp = self.rt, self.p, self.spec
         m = gelu(rt, self._time_features("to_time.0", t))
+        if sp.context_features is not None:
+            assert features is not None, "context_features exists but no features provided"       # model.py:216
+            f = features.detach().to(torch.float32)
+            assert f.dim() == 2 and f.shape[1] == int(sp.context_features), f"features of shape {tuple(f.shape)}"
+            if pad8(f.shape[1]) != f.shape[1]:
+                f = torch.nn.functional.pad(f, (0, pad8(f.shape[1]) - f.shape[1]))
+            m = m + gelu(rt, linear(rt, f.contiguous(), p["to_features.0.weight"], p["to_features.0.bias"]))
         m = gelu(rt, linear(rt, m, p["to_mapping.0.weight"], p["to_mapping.0.bias"]))
         return gelu(rt, linear(rt, m, p["to_mapping.2.weight"], p["to_mapping.2.bias"]))
 
@@ -1774,18 +1783,20 @@ class TrainGraph:
         return dict(zip(names, pairs))
 
     # ------------------------------------------------------------------ UNet1d.forward
-    def unet(self, x: torch.Tensor, t: torch.Tensor, embedding: torch.Tensor, embedding_mask, ctx_channels, causal: bool) -> torch.Tensor:
+    def unet(self, x: torch.Tensor, t: torch.Tensor, embedding: torch.Tensor, embedding_mask, ctx_channels, causal: bool,
+             features: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B, C, T] float32 (+ ctx_channels [B, 129, T]) -> [B, out_channels, T] float32"""
         sp = self.spec
         if ctx_channels is not None:
             x = torch.cat([x, ctx_channels.to(x.dtype)], dim=1)
-        h = self.unet_rows(self._to_rows(x), t, embedding, embedding_mask, causal)
+        h = self.unet_rows(self._to_rows(x), t, embedding, embedding_mask, causal, features)
         return h[:, :, :sp.out_channels].to(torch.float32).transpose(1, 2)
 
-    def unet_rows(self, h: torch.Tensor, t: torch.Tensor, embedding: torch.Tensor, embedding_mask, causal) -> torch.Tensor:
+    def unet_rows(self, h: torch.Tensor, t: torch.Tensor, embedding: torch.Tensor, embedding_mask, causal,
+                  features: Optional[torch.Tensor] = None) -> torch.Tensor:
         """the same on channel-last rows: h [B, T, pad8(C_in + C_ctx)] in the compute dtype -> [B, T, pad8(out_channels)]"""
         rt, p, sp = self.rt, self.p, self.spec
-        mp = self.mapping(t)
+        mp = self.mapping(t, features)
         smap = silu(rt, mp).to(rt.tdtype)
         films = self.films(smap)
         h = self.res_block(sp.to_in, h, smap, False, films)          # Patcher / Unpatcher are never causal (blocks.py:256-259)
@@ -1863,8 +1874,11 @@ class TrainGraph:
                 scale_phi: float = 0.7, features=None, channels_list: Optional[Sequence[torch.Tensor]] = None,
                 causal: Optional[bool] = False, dropout_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Same contract as the reference forward (model.py:299-376), differentiable."""
-        assert features is None, "context_features is unused on the JEN-1 path"
         rt, p, sp = self.rt, self.p, self.spec
+        if sp.context_features is None:
+            features = None                        # ignored without ``context_features``, as in the reference (model.py:213-217)
+        else:
+            assert features is not None, "context_features exists but no features provided"
         self.rt.abandon_weight_grads()
         # a bool, or one flag per clip (tensor [B]): a pass that holds causal and non-causal clips side by side (CausalRows)
         rows = CausalRows(causal) if torch.is_tensor(causal) else None
@@ -1896,18 +1910,19 @@ class TrainGraph:
             if batch_cfg:
                 out_all = self.unet(torch.cat([x, x], 0), torch.cat([time, time], 0), torch.cat([emb, fixed], 0).contiguous(),
                                     None if mask is None else torch.cat([mask, mask], 0),
-                                    None if ctx is None else torch.cat([ctx, ctx], 0), causal2)
+                                    None if ctx is None else torch.cat([ctx, ctx], 0), causal2,
+                                    None if features is None else torch.cat([features, features], 0))       # model.py:339-342
                 out, out_masked = out_all[:B], out_all[B:]
             else:
-                out = self.unet(x, time, emb.contiguous(), mask, ctx, causal)
-                out_masked = self.unet(x, time, fixed.contiguous(), mask, ctx, causal)
+                out = self.unet(x, time, emb.contiguous(), mask, ctx, causal, features)
+                out_masked = self.unet(x, time, fixed.contiguous(), mask, ctx, causal, features)
             out_cfg = out_masked + (out - out_masked) * embedding_scale
             if scale_cfg:
                 out_std = out.std(dim=1, keepdim=True)
                 out_cfg_std = out_cfg.std(dim=1, keepdim=True)
                 return scale_phi * (out_cfg * (out_std / out_cfg_std)) + (1 - scale_phi) * out_cfg
             return out_cfg
-        return self.unet(x, time, emb.contiguous(), mask, ctx, causal)
+        return self.unet(x, time, emb.contiguous(), mask, ctx, causal, features)
 
     def diffusion_loss(self, gd, x_start: torch.Tensor, t: torch.Tensor, conditioning, noise: torch.Tensor, causal, dropout_rows=None):
         """``_diffusion_loss`` off the legacy default stream (see ``_off_default_stream``): ``training_loosses`` enters here directly, not
@@ -1921,8 +1936,10 @@ class TrainGraph:
         back) -- per-sample losses [B].  None when the settings need the literal path (an unbatched CFG pair)."""
         rt, p, sp = self.rt, self.p, self.spec
         cfg = gd.embedding_scale != 1.0
-        if not rt.fused_glue or (cfg and not gd.batch_cfg) or conditioning.get("global_cond") is not None or sp.out_channels > 256:
+        if not rt.fused_glue or (cfg and not gd.batch_cfg) or sp.out_channels > 256:
             return None
+        feat = conditioning.get("global_cond") if sp.context_features is not None else None
+        assert sp.context_features is None or feat is not None, "context_features exists but no features provided"    # model.py:216
         self.rt.abandon_weight_grads()
         rows_c = CausalRows(causal) if torch.is_tensor(causal) else None
         causal = rows_c if rows_c is not None else bool(causal)
@@ -1980,7 +1997,9 @@ class TrainGraph:
             if nrep == 2:
                 mask = torch.cat([mask, mask], 0)
         t2 = torch.cat([t, t], 0) if nrep == 2 else t
-        out = self.unet_rows(h, t2, ctx_rows, mask, causal)
+        if feat is not None and nrep == 2:
+            feat = torch.cat([feat, feat], 0)                              # model.py:339-342
+        out = self.unet_rows(h, t2, ctx_rows, mask, causal, feat)
         return CfgLossFn.apply(out.contiguous(), tgt, rt, B, sp.out_channels, nrep, float(gd.embedding_scale), bool(gd.scale_cfg), 0.7,
                                getattr(gd, "loss_type", "l2") == "l1")
 
@@ -2034,7 +2053,7 @@ class GraphedLossStep:
         self.exchange = None
 
     def _body(self, static, causal):
-        cond = {"cross_attn_cond": static["emb"], "cross_attn_masks": static["mask"], "global_cond": None,
+        cond = {"cross_attn_cond": static["emb"], "cross_attn_masks": static["mask"], "global_cond": static["features"],
                 "input_concat_cond": static["concat"]}
         if static["causal"] is not None:
             causal = static["causal"]          # one flag per clip, read by the replayed kernels: refreshed before every replay
@@ -2054,6 +2073,7 @@ class GraphedLossStep:
                   "causal": causal.to(torch.int32).clone() if torch.is_tensor(causal) else None,
                   "mask": None if conditioning["cross_attn_masks"] is None else conditioning["cross_attn_masks"].clone(),
                   "concat": None if conditioning["input_concat_cond"] is None else conditioning["input_concat_cond"].clone(),
+                  "features": None if conditioning.get("global_cond") is None else conditioning["global_cond"].to(torch.float32).clone(),
                   "w": None if weights is None else weights.to(torch.float32).clone()}
         keep = [None if p.grad is None else p.grad.clone() for p in params]       # the warm-up run must not leak into the gradients
         saved_ex, self.graph.exchange = self.graph.exchange, None                 # (no collectives in the warm-up run)
@@ -2089,11 +2109,10 @@ class GraphedLossStep:
                  sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """replay (capture on first use) forward + backward of one pass; returns the loss, or with ``sample_weights`` [B] the
         per-sample losses [B] of the pass whose objective is their weighted sum"""
-        assert conditioning.get("global_cond") is None
         ex = self.exchange if (self.exchange is not None and self.exchange.active and self.exchange.capturable) else None
         per_clip = torch.is_tensor(causal)
         key = (tuple(x0.shape), "per clip" if per_clip else bool(causal), conditioning["cross_attn_masks"] is None, conditioning["input_concat_cond"] is None,
-               sample_weights is None, ex is not None)
+               sample_weights is None, ex is not None, conditioning.get("global_cond") is not None)
         hit = self._captured.get(key)
         first = hit is None
         if first:
@@ -2112,6 +2131,8 @@ class GraphedLossStep:
             static["mask"].copy_(conditioning["cross_attn_masks"])
         if static["concat"] is not None:
             static["concat"].copy_(conditioning["input_concat_cond"])
+        if static["features"] is not None:
+            static["features"].copy_(conditioning["global_cond"])
         self.graph.rt.refresh_all()
         g.replay()
         if ex is not None:

@@ -33,7 +33,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from .diffusion import DDIMStepper, _check_model_errors, blend_known, check_known
+from .diffusion import DDIMStepper, _check_model_errors, blend_known, check_known, film_tables_fit, has_global_cond
 from .model import _STEPPER_CACHES, UNetCFG1d
 
 
@@ -104,7 +104,8 @@ class VDM(torch.nn.Module):
             audio = audio + init_data
         self.steps = torch.linspace(1., 0., step + 1, device=self.device)
         self.get_alpha_sigma(self.steps)
-        fused = fused and isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+        fused = (fused and isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+                 and film_tables_fit(model, conditioning, shape[0], step))          # (diffusion.FILM_TABLE_BUDGET)
         audios = [audio]
         if fused:
             self._steps = step
@@ -112,7 +113,8 @@ class VDM(torch.nn.Module):
             cache = self.__dict__.setdefault("_steppers", {})
             _STEPPER_CACHES.add(self)            # (an engine invalidation drops this model's steppers: model._drop_steppers_of)
             key = (id(model), id(model.engine()), tuple(shape), bool(causal), bool(use_graph), int(step), float(self.embedding_scale),
-                   bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic), known is not None)
+                   bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic), known is not None,
+                   has_global_cond(model, conditioning))
             st = cache.get(key)
             if st is not None and st.model is model and st.eng is model.engine():
                 st.rebind(conditioning)
