@@ -26,7 +26,7 @@ import math
 import weakref
 import os
 import time
-from dataclasses import dataclass
+from collections import namedtuple
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -342,6 +342,7 @@ class DeepProgram:
         self.kinds: List[str] = []
         self.lib = eng.lib
         self.psize = self.lib.jen1_deep_phase_size()
+        self.dsize = self.psize                          # bytes of one recorded descriptor
         self.bufs: List[C.Array] = []
         self.labels: List[str] = []
         self.outs: List[Optional["Act"]] = []
@@ -409,18 +410,24 @@ class DeepProgram:
         launch poisoned and are polled by their consumers (include/jen1_deep.h)"""
         return t is not None and t.untyped_storage().data_ptr() in self._produced
 
-    def _new(self):
-        return (C.c_char * self.psize)()
+    ineligible = DeepIneligible     # what a layer that does not fit raises
 
-    def _add(self, buf, rc, label, out, kind="gemm"):
+    def _new(self):
+        return (C.c_char * self.dsize)()
+
+    def _add(self, buf, rc, label, out, kind="gemm", part=None):
+        """the recorder of every phase: the descriptor ``buf`` the library filled (rc != 0: it refused), the phase's kind, its output and the
+        statistics partials it writes beside it (both start every launch poisoned)"""
         if rc != 0:
             msg = self.lib.jen1_last_error()
-            raise DeepIneligible(f"{label}: {msg.decode() if msg else 'does not fit'}")
+            raise self.ineligible(f"{label}: {msg.decode() if msg else 'does not fit'}")
         self.bufs.append(buf)
         self.labels.append(label)
         self.outs.append(out)
         self.kinds.append(kind)
         self._note_output(out)
+        if part is not None:
+            self._produced.setdefault(part.untyped_storage().data_ptr(), part)
 
     def add_conv(self, a: "L.ConvArgs", label: str, out, nb_max: int = 0):
         buf = self._new()
@@ -433,10 +440,8 @@ class DeepProgram:
         p = [(0, 0, 0) if e is None else (e[0], e[1], e[2]) for e in st]
         live = sum(1 << k for k, e in enumerate(st) if e is not None and e[3])
         rc = self.lib.jen1_deep_phase_tile(C.byref(a), tb, bm, p[0][0] or None, p[0][1], p[0][2], p[1][0] or None, p[1][1], p[1][2], live,
-                                           None if out_part is None else out_part.data_ptr(), out_nfg, C.cast(buf, C.c_void_p))
-        self._add(buf, rc, label, out, kind="tile")
-        if out_part is not None:
-            self._produced.setdefault(out_part.untyped_storage().data_ptr(), out_part)
+                                           _ptr(out_part), out_nfg, C.cast(buf, C.c_void_p))
+        self._add(buf, rc, label, out, kind="tile", part=out_part)
 
     def add_attention(self, args, label: str, out):
         buf = self._new()
@@ -457,9 +462,7 @@ class DeepProgram:
         """link the phases, build the device image (per-phase blobs + headers) and move it to the device; ``sync``: int32 view
         of a zeroed-per-step area of sync_words()"""
         n = len(self.bufs)
-        host = (C.c_char * (self.psize * n))()
-        for i, b in enumerate(self.bufs):
-            C.memmove(C.addressof(host) + i * self.psize, b, self.psize)
+        host = (C.c_char * (self.dsize * n)).from_buffer_copy(self._host_image())
         bb = self.lib.jen1_deep_blob_bytes()
         blobs = (C.c_char * (bb * n))()
         hdrs = (C.c_char * (16 * n))()
@@ -467,17 +470,30 @@ class DeepProgram:
         if self.lds <= 0 or self.nwg < 1:
             msg = self.lib.jen1_last_error()
             raise DeepIneligible(f"jen1_deep_link: {msg.decode() if msg else 'failed'}")
-        self.dev = torch.frombuffer(bytearray(bytes(blobs)), dtype=torch.uint8).to(self.eng.device)
-        self.hdr = torch.frombuffer(bytearray(bytes(hdrs)), dtype=torch.uint8).to(self.eng.device)
+        self.dev = self._to_device(blobs)
+        self.hdr = self._to_device(hdrs)
+        self._finish(sync)
+
+    def _host_image(self) -> bytes:
+        """the recorded descriptors, one behind the other"""
+        return b"".join(bytes(b) for b in self.bufs)
+
+    def _to_device(self, image) -> torch.Tensor:
+        return torch.frombuffer(bytearray(bytes(image)), dtype=torch.uint8).to(self.eng.device)
+
+    def _finish(self, sync: torch.Tensor, chunk: Optional[int] = None):
+        """what every program needs behind its device image: the synchronisation area, the error word, the poison table (one row per
+        storage, or per ``chunk`` bytes of it) and, for the plan's leader, the claim on the static schedule"""
         self.sync = sync
         # the error word lives outside the per-step zeroed area: the first time-out of any replay stays visible (error())
         self.err = self._err_shared if self._err_shared is not None else torch.zeros((16,), dtype=torch.int32, device=self.eng.device)
-        # every tensor a phase writes starts each launch as the sentinel (jen1_deep_poison): {pointer, bytes} per storage
+        # every tensor a phase writes starts each launch as the sentinel (jen1_deep_poison): {pointer, bytes} per row
         ent = []
         for ptr, t in self._produced.items():
             nb = t.untyped_storage().nbytes()
             assert ptr % 16 == 0 and nb % 16 == 0, (ptr, nb)
-            ent += [ptr, nb]
+            for o in (range(0, nb, chunk) if chunk else (0,)):
+                ent += [ptr + o, min(chunk or nb, nb - o)]
         if self.leader is self:
             self.claim_static()
         self.poison_tab = torch.tensor(ent, dtype=torch.int64).view(-1, 2).to(self.eng.device)
@@ -526,6 +542,7 @@ class LongProgram(DeepProgram):
     sample).  Shares the plan's leader (static schedule claim, error word) with the deep program(s)."""
 
     POISON_CHUNK = 1 << 18          # a poisoned tensor is cut into table rows of this many bytes (8 workgroups per row)
+    ineligible = LongIneligible
 
     def __init__(self, eng, Bs: int, leader: Optional["DeepProgram"] = None, err: Optional[torch.Tensor] = None):
         super().__init__(eng, leader=leader, err=err)
@@ -544,46 +561,20 @@ class LongProgram(DeepProgram):
 
     def add_long(self, a: "L.ConvArgs", st, st_live: int, out_part, label: str, out):
         """st: per normalised source None or (pointer, entries, mblocks, nsub) -- entries = 0: fine-group totals"""
-        buf = (C.c_char * self.dsize)()
+        buf = self._new()
         st = list(st) + [None] * (2 - len(st))
         q = [(None, 0, 1, 8) if e is None else e for e in st]
         rc = self.lib.jen1_long_phase_conv(C.byref(a), self.G, q[0][0], q[0][1], q[0][2], q[0][3], q[1][0], q[1][1], q[1][2], q[1][3], st_live,
-                                           None if out_part is None else out_part.data_ptr(), C.cast(buf, C.c_void_p))
-        if rc != 0:
-            msg = self.lib.jen1_last_error()
-            raise LongIneligible(f"{label}: {msg.decode() if msg else 'does not fit'}")
-        self.bufs.append(buf)
-        self.labels.append(label)
-        self.outs.append(out)
-        self.kinds.append("long")
-        self._note_output(out)
-        if out_part is not None:
-            self._produced.setdefault(out_part.untyped_storage().data_ptr(), out_part)
+                                           _ptr(out_part), C.cast(buf, C.c_void_p))
+        self._add(buf, rc, label, out, kind="long", part=out_part)
 
     def sync_words(self) -> int:
         return 64                   # word 0: the ticket counter of the ticket form (zero when the launch starts)
 
     def finalize(self, sync: torch.Tensor):
-        n = len(self.bufs)
-        host = (C.c_char * (self.dsize * n))()
-        lds = 0
-        for i, b in enumerate(self.bufs):
-            C.memmove(C.addressof(host) + i * self.dsize, b, self.dsize)
-            lds = max(lds, int(self.lib.jen1_long_phase_lds(C.cast(b, C.c_void_p))))
-        self.lds = lds
-        self.dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.eng.device)
-        self.sync = sync
-        self.err = self._err_shared if self._err_shared is not None else torch.zeros((16,), dtype=torch.int32, device=self.eng.device)
-        ent = []
-        for ptr, t in self._produced.items():
-            nb = t.untyped_storage().nbytes()
-            assert ptr % 16 == 0 and nb % 16 == 0, (ptr, nb)
-            for o in range(0, nb, self.POISON_CHUNK):
-                ent += [ptr + o, min(self.POISON_CHUNK, nb - o)]
-        if self.leader is self:
-            self.claim_static()
-        self.poison_tab = torch.tensor(ent, dtype=torch.int64).view(-1, 2).to(self.eng.device)
-        self.poison_bytes = int(sum(ent[1::2]))
+        self.lds = max([0] + [int(self.lib.jen1_long_phase_lds(C.cast(b, C.c_void_p))) for b in self.bufs])
+        self.dev = self._to_device(self._host_image())
+        self._finish(sync, chunk=self.POISON_CHUNK)
         self.local = self.xcd_local()
 
     def xcd_local(self) -> bool:
@@ -608,6 +599,47 @@ class LongProgram(DeepProgram):
         loc = static and self.local
         L.check(self.lib.jen1_long_run(self.dev.data_ptr(), n, self.Bs, self.err.data_ptr(), None if (static and not loc) else self.sync.data_ptr(),
                                        self.nwg, self.lds, self.eng.dt, 1 if loc else 0, stream), "jen1_long_run")
+
+
+class Launch:
+    """One entry of a plan's ``ops``: ``fn(stream)`` enqueues it; the rest is what bench.py, the samplers, the tests and the tools read
+    back (all of it assignable).  A plain callable is as legal an entry: readers use ``getattr(op, "kind", "")``."""
+
+    def __init__(self, fn: Callable[[int], None], kind: str = "", label: str = "", prog=None, w_bytes=0, act_bytes=0, flops=0, bytes=0):
+        self.fn, self.kind, self.label, self.prog = fn, kind, label, prog
+        self.w_bytes, self.act_bytes, self.flops, self.bytes = w_bytes, act_bytes, flops, bytes      # algorithmic traffic / work
+
+    def __call__(self, stream: int) -> None:
+        self.fn(stream)
+
+
+def conv_traffic(taps: int, c_real: int, c_extra: int, M: int, B: int, L_in: int, L_out: int, L_y: int, out_C: int, *,
+                 w_es: int, act_es: int, out_es: int, scale_bytes: int = 0) -> Tuple[int, int, int]:
+    """algorithmic traffic / work of one convolution, however it runs (weights once + conv input + output):
+    (weight bytes, activation bytes, FLOPs).  c_real: unpadded channels of the one or two conv sources (read under every tap), c_extra:
+    of the raw extra K segments; w_es / act_es / out_es: bytes per weight, input and output element (fp8 weights: 1, a float32 output:
+    4); scale_bytes: what rides with the weights (fp8: one float32 scale per output row)"""
+    k = taps * c_real + c_extra
+    return k * M * w_es + scale_bytes, B * L_in * (c_real + c_extra) * act_es + B * L_y * out_C * out_es, 2 * k * M * B * L_out
+
+
+def _extras_fit_tile(extra_segs, padded_ok: bool = False) -> bool:
+    """at most two raw extra K segments at row shift 0 in whole 32-channel chunks (a 1x1 shortcut riding on the block's second conv):
+    what the tile kernel, the tile phases and the long phases take.  padded_ok (the long phases alone): a source whose channels are
+    padded (``cp != C``) may ride along"""
+    return len(extra_segs) <= 2 and all(sh == 0 and (padded_ok or e.cp == e.C) and e.cp % 32 == 0 for e, sh in extra_segs)
+
+
+class ConvRequest(namedtuple("ConvRequest", "ops src0 src1 w bias edge_bias out pro gn film ln act residual row_scale y_f32 extra_segs m_split k_split "
+                                            "flat_w taps out_C force label")):
+    """the Python-side operands of one ``OpBuilder.conv`` call (``ops``: where a launch goes; ``extra_segs``: a list, possibly empty): what
+    its back ends read beside the filled ``jen1_conv_args``, and what keeps the tensors behind the raw pointers alive"""
+    __slots__ = ()
+    # the sources a GroupNorm prologue normalises (empty: no GroupNorm)
+    normed = property(lambda self: [s for s in (self.src0, self.src1) if s is not None] if self.pro in (L.PRO_GN, L.PRO_GN_SILU) else [])
+    # all sources in the kernels' order: x0, x1 (when present), then the extra segments
+    sources = property(lambda self: [s for s in (self.src0, self.src1) if s is not None] + [e for e, _ in self.extra_segs])
+    k_extra = property(lambda self: sum(e.cp for e, _ in self.extra_segs))      # padded channels of the extra segments
 
 
 class KernelCtx:
@@ -673,17 +705,19 @@ class OpBuilder:
     def run(self, stream: Optional[int] = None, pack: bool = True, poison: bool = True):
         """pack=False leaves out the ops that write the network input (kind "pack"), poison=False the head-of-step sentinel / arena
         reset node (kind "deep_poison"): the fused sampler's previous step did both (jen1_cfg_ddim_step_pack / jen1_step_tail)"""
+        skip = (() if pack else ("pack",)) + (() if poison else ("deep_poison",))
+        self._run_ops(self.ops if not skip else [op for op in self.ops if getattr(op, "kind", "") not in skip], stream,
+                      trace=bool(os.environ.get("JEN1_DEBUG_SYNC")))
+
+    def _run_ops(self, ops, stream: Optional[int], trace: bool = False):
+        """enqueue ``ops`` on ``stream`` (default: torch's current one); trace (JEN1_DEBUG_SYNC): name and synchronise each"""
         if stream is None:
             stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-        skip = (() if pack else ("pack",)) + (() if poison else ("deep_poison",))
-        ops = self.ops if not skip else [op for op in self.ops if getattr(op, "kind", "") not in skip]
-        if os.environ.get("JEN1_DEBUG_SYNC"):
-            for i, op in enumerate(ops):
-                print(f"[jen1] op {i}: {getattr(op, 'label', '?')}", flush=True)
-                op(stream)
-                torch.cuda.synchronize(self.eng.device)
-            return
-        for op in ops:
+        for i, op in enumerate(ops if trace else ()):
+            print(f"[jen1] op {i}: {getattr(op, 'label', '') or '?'}", flush=True)
+            op(stream)
+            torch.cuda.synchronize(self.eng.device)
+        for op in (() if trace else ops):
             op(stream)
 
     # ---------------------------------------------------------------- the fused conv / linear op
@@ -693,41 +727,57 @@ class OpBuilder:
              y_f32=False, out_C=None, force=None, label="", extra_segs=None, m_split=0, k_split=0, flat_w=False, edge_bias=None):
         """edge_bias: [2][M] float32 (persistent deep-level kernel only; ``bias`` is then [M]: jen1_conv_args.edge_bias).
         extra_segs: [(Act, row_shift)] raw sources appended to the K axis after the (tap, source) pairs of
-        src0/src1 (streaming / direct mode only); ``w`` is then the flat packed weight [chunks][M/16][64][8]."""
-        eng = self.eng
+        src0/src1 (streaming / direct mode only); ``w`` is then the flat packed weight [chunks][M/16][64][8].
+        Returns ``out``, or None when a wide-tile launch declines the extra segments (the caller uses separate launches)."""
+        rq = ConvRequest(ops, src0, src1, w, bias, edge_bias, out, pro, gn, film, ln, act, residual, row_scale, y_f32, extra_segs or [],
+                         m_split, k_split, flat_w, taps, out_C if out_C is not None else out.C, force, label)
+        a = self._conv_args(rq, stride, pad_left, L_out, src1_scale, ps_f, ps_off, L_y, y_row0)
+        if self._long_on:
+            return self._conv_long(a, rq)
+        if self._deep_on:
+            return self._conv_deep(a, rq)
+        if src0.L in self.tile_lens and not self.det:
+            # a long level inside the persistent launch: a tile phase (jen1_deep_phase_tile); a layer that does not fit runs as a launch
+            try:
+                return self._conv_tile(L.ConvArgs.from_buffer_copy(a), rq)
+            except DeepIneligible as e:
+                self.tile_errors.append(str(e))
+        return self._conv_launch(a, rq)
+
+    def _conv_args(self, rq: ConvRequest, stride, pad_left, L_out, src1_scale, ps_f, ps_off, L_y, y_row0) -> "L.ConvArgs":
+        """the fields of ``jen1_conv_args`` that do not depend on how the layer runs"""
+        src0, src1, w, out, pro, taps, label = rq.src0, rq.src1, rq.w, rq.out, rq.pro, rq.taps, rq.label
         a = L.ConvArgs()
         a.x0, a.c0, a.ld0 = src0.t.data_ptr(), src0.cp, src0.ld
         if src1 is not None:
             a.x1, a.c1, a.ld1 = src1.t.data_ptr(), src1.cp, src1.ld
             assert src1.L == src0.L and src1.B == src0.B
-        a.w, a.bias = w.data_ptr(), _ptr(bias)
-        a.edge_bias = _ptr(edge_bias)
-        assert edge_bias is None or self._deep_on, f"{label}: an edge bias exists only in the persistent deep-level kernel"
-        a.dtype = eng.dt
+        a.w, a.bias = w.data_ptr(), _ptr(rq.bias)
+        a.edge_bias = _ptr(rq.edge_bias)
+        assert rq.edge_bias is None or self._deep_on, f"{label}: an edge bias exists only in the persistent deep-level kernel"
+        a.dtype = self.eng.dt
         a.B, a.L_in = src0.B, src0.L
         a.L_out = L_out if L_out is not None else src0.L
         a.taps, a.stride, a.pad_left = taps, stride, pad_left
-        out_C = out_C if out_C is not None else out.C
-        a.out_C, a.ps_f, a.ps_off = out_C, ps_f, ps_off
-        a.M = out_C * ps_f
-        if extra_segs or flat_w:
-            k_extra = sum(e.cp for e, _ in extra_segs) if extra_segs else 0
-            assert w.dim() == 4 and w.shape[1] * 16 == a.M and w.shape[0] * 32 == taps * (a.c0 + a.c1) + k_extra, \
-                (tuple(w.shape), taps, a.M, a.c0, a.c1, k_extra)
+        a.out_C, a.ps_f, a.ps_off = rq.out_C, ps_f, ps_off
+        a.M = rq.out_C * ps_f
+        if rq.extra_segs or rq.flat_w:
+            assert w.dim() == 4 and w.shape[1] * 16 == a.M and w.shape[0] * 32 == taps * (a.c0 + a.c1) + rq.k_extra, \
+                (tuple(w.shape), taps, a.M, a.c0, a.c1, rq.k_extra)
         else:
             assert w.shape[0] == taps and w.shape[2] * 16 == a.M and w.shape[1] * 32 == a.c0 + a.c1, \
                 (tuple(w.shape), taps, a.M, a.c0, a.c1)
         a.y, a.ld_y = out.t.data_ptr(), out.ld
         a.L_y = L_y if L_y is not None else (out.L - y_row0)
         a.y_brows, a.y_row0 = out.L, y_row0
-        a.y_f32 = 1 if y_f32 else 0
-        if residual is not None:
-            a.residual, a.ld_res = residual.t.data_ptr(), residual.ld
-            assert residual.L == out.L and residual.B == out.B and y_row0 == 0
+        a.y_f32 = 1 if rq.y_f32 else 0
+        if rq.residual is not None:
+            a.residual, a.ld_res = rq.residual.t.data_ptr(), rq.residual.ld
+            assert rq.residual.L == out.L and rq.residual.B == out.B and y_row0 == 0
         a.pro_mode = pro
         a.src1_scale = float(src1_scale)
-        if pro in (L.PRO_GN, L.PRO_GN_SILU):
-            groups, creal, gamma, beta, eps = gn
+        if rq.normed:
+            groups, creal, gamma, beta, eps = rq.gn
             a.gn_groups = groups
             a.gn_cpg = creal // groups if groups > 1 else max(creal, a.c0 + a.c1)
             a.gn_count = (creal // groups) * src0.L
@@ -737,100 +787,114 @@ class OpBuilder:
             a.gn_stats0 = src0.gn.data_ptr()
             if src1 is not None:
                 a.gn_stats1 = src1.gn.data_ptr()
-            if film is not None:
-                ftab, frow, foff, fC = film[:4]
+            if rq.film is not None:
+                ftab, frow, foff, fC = rq.film[:4]
                 a.film, a.film_row = ftab.data_ptr(), _ptr(frow)
                 a.film_off, a.film_C, a.film_ld = foff, fC, ftab.shape[-1]
-                a.film_step = _ptr(film[4]) if len(film) > 4 else None
-        ln_u = None
+                a.film_step = _ptr(rq.film[4]) if len(rq.film) > 4 else None
         if pro == L.PRO_LN:
-            lnC, g_, b_ = ln[:3]
-            ln_u = ln[3] if len(ln) > 3 else None
+            lnC, g_, b_ = rq.ln[:3]
             a.ln_rowstats, a.ln_C, a.ln_eps = src0.rs.data_ptr(), lnC, 1e-5
             a.ln_gamma, a.ln_beta = _ptr(g_), _ptr(b_)
-        a.act = act
-        a.row_scale = _ptr(row_scale)
-        if out.gn is not None and not y_f32:
+        a.act = rq.act
+        a.row_scale = _ptr(rq.row_scale)
+        if out.gn is not None and not rq.y_f32:
             a.out_gn_stats, a.out_cpf = out.gn.data_ptr(), out.ld // FG
         if out.rs is not None:
             a.out_rowstats = out.rs.data_ptr()
-        if self._long_on:
-            return self._conv_long(a, src0=src0, src1=src1, w=w, bias=bias, out=out, pro=pro, gn=gn, film=film, act=act, residual=residual,
-                                   row_scale=row_scale, y_f32=y_f32, extra_segs=extra_segs, m_split=m_split, label=label, taps=taps, out_C=out_C)
-        if self._deep_on:
-            # persistent deep-level kernel: one phase descriptor instead of a launch (norm_apply + streaming GEMM); the consumer
-            # computes the GroupNorm statistics itself, FiLM comes from the fused GroupNorm-FiLM table
-            if pro == L.PRO_LN or y_f32 or row_scale is not None:
-                raise DeepIneligible(f"{label}: prologue / epilogue option outside the persistent kernel")
-            if out.ld != out.C:
-                raise DeepIneligible(f"{label}: {out.C} output channels are not a multiple of 32 (padding columns would stay poisoned)")
-            a.out_gn_stats = a.out_rowstats = None
-            w8 = None
-            if eng.deep_dt == L.FP8:
-                # JEN1_FP8: e4m3 weights + per-row scales feed the fp8 matrix-core path of the unit; activations stay bf16 in HBM
-                w8 = eng.W.fp8(w)
-                a.dtype, a.w, a.w_scale = L.FP8, w8[0].data_ptr(), w8[1].data_ptr()
-            if pro in (L.PRO_GN, L.PRO_GN_SILU) and film is not None:
-                a.film = self.film2.data_ptr()
-            a.nseg = 0
-            if extra_segs:
-                for i, (e, sh) in enumerate(extra_segs):
-                    assert e.B == a.B and e.L == a.L_in and e.t.dtype == eng.tdtype and e.cp == e.C
-                    a.seg[i].x, a.seg[i].ld, a.seg[i].shift, a.seg[i].kch = e.t.data_ptr(), e.ld, sh, e.cp // 32
-                a.nseg = len(extra_segs)
-            # operands produced by earlier phases of the launch are polled (they start poisoned); source order as in
-            # jen1_deep_phase_conv: x0, x1 (when present), then the extra segments
-            srcs_ = [src0] + ([src1] if src1 is not None else []) + [e for e, _ in (extra_segs or [])]
-            a.live_mask = sum(1 << i for i, s_ in enumerate(srcs_) if self.deep.is_live(s_.t)) | \
-                (256 if residual is not None and self.deep.is_live(residual.t) else 0)
-            if m_split:
-                a.m_split, a.k_split = m_split, k_split
-            self._keep.append((a, src0, src1, w, w8, bias, edge_bias, out, residual, gn, film, extra_segs))
-            # batch elements per unit: fewer per unit = smaller tiles to normalise and stage (the critical path of a phase) on more
-            # workgroups, but every batch group streams the layer's weights again -- so only where the weights are small
-            nb_cap = eng.deep_nb_max
-            if eng.deep_unit_target > 0:
-                wbytes_ = (taps * (a.c0 + a.c1) + sum(e.cp for e, _ in (extra_segs or []))) * a.M * (1 if w8 is not None else (4 if eng.dt == L.F32 else 2))
-                nb_ = 1
-                while nb_ < a.B and ((a.M // 16) * -(-a.B // nb_) > eng.deep_unit_target or -(-a.B // nb_) * wbytes_ > eng.deep_reread_cap):
-                    nb_ *= 2
-                nb_cap = nb_ if nb_cap == 0 else min(nb_cap, nb_)
-            self.deep.add_conv(a, f"conv[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} M={a.M}", out,
-                               nb_max=nb_cap)
-            es_ = 4 if eng.dt == L.F32 else 2
-            c_real_ = src0.C + (src1.C if src1 is not None else 0)
-            c_extra_ = sum(e.C for e, _ in extra_segs) if extra_segs else 0
-            self.deep.w_bytes += (taps * c_real_ + c_extra_) * a.M * (1 if w8 is not None else es_) + (4 * a.M if w8 is not None else 0)
-            self.deep.act_bytes += a.B * a.L_in * (c_real_ + c_extra_) * es_ + a.B * a.L_y * out_C * es_
-            self.deep.flops += 2 * (taps * c_real_ + c_extra_) * a.M * a.B * a.L_out
-            out.gn_valid = False
-            return out
-        if src0.L in self.tile_lens and not self.det:
-            # a long level inside the persistent launch: a tile phase (jen1_deep_phase_tile); a layer that does not fit runs as a launch
-            try:
-                return self._conv_tile(L.ConvArgs.from_buffer_copy(a), src0=src0, src1=src1, w=w, bias=bias, out=out, pro=pro, gn=gn, film=film, ln=ln, act=act,
-                                       residual=residual, row_scale=row_scale, y_f32=y_f32, extra_segs=extra_segs, m_split=m_split,
-                                       flat_w=flat_w, label=label, taps=taps, out_C=out_C)
-            except DeepIneligible as e:
-                self.tile_errors.append(str(e))
+        return a
+
+    # ---------------------------------------------------------------- what the back ends of conv share
+    def _fill_segs(self, a: "L.ConvArgs", extra_segs, first: int = 0, shifts: bool = False, padded_ok: bool = True):
+        """the raw extra K segments into ``a.seg[first:]``.  shifts: a segment keeps its row shift (the streaming kernels; the tile and
+        long forms take shift 0 only); padded_ok=False: a segment's channels are whole (no padding columns)"""
+        for i, (e, sh) in enumerate(extra_segs):
+            assert e.B == a.B and e.L == a.L_in and e.t.dtype == self.eng.tdtype and (padded_ok or e.cp == e.C)
+            s = a.seg[first + i]
+            s.x, s.ld, s.shift, s.kch = e.t.data_ptr(), e.ld, sh if shifts else 0, e.cp // 32
+        a.nseg = first + len(extra_segs)
+
+    @staticmethod
+    def _live_mask(prog: DeepProgram, rq: ConvRequest) -> int:
+        """operands produced by earlier phases of the launch are polled (they start poisoned): bits in source order x0, x1 (when present),
+        then the extra segments; bit 8: the residual"""
+        return sum(1 << i for i, s_ in enumerate(rq.sources) if prog.is_live(s_.t)) | \
+            (256 if rq.residual is not None and prog.is_live(rq.residual.t) else 0)
+
+    def _film2(self, a: "L.ConvArgs", rq: ConvRequest):
+        """the phases apply FiLM from the fused GroupNorm-FiLM table"""
+        if rq.normed and rq.film is not None:
+            a.film = self.film2.data_ptr()
+
+    def _traffic(self, a: "L.ConvArgs", rq: ConvRequest, prog: Optional[DeepProgram] = None, w_es: Optional[int] = None, scale_bytes: int = 0):
+        """``conv_traffic`` of this layer (w_es: bytes per weight element when not the compute dtype's); added to ``prog``'s when it is a phase"""
+        es = 4 if self.eng.dt == L.F32 else 2
+        c_real = rq.src0.C + (rq.src1.C if rq.src1 is not None else 0)
+        t = conv_traffic(rq.taps, c_real, sum(e.C for e, _ in rq.extra_segs), a.M, a.B, a.L_in, a.L_out, a.L_y, rq.out_C,
+                         w_es=w_es or es, act_es=es, out_es=4 if rq.y_f32 else es, scale_bytes=scale_bytes)
+        if prog is not None:
+            prog.w_bytes, prog.act_bytes, prog.flops = prog.w_bytes + t[0], prog.act_bytes + t[1], prog.flops + t[2]
+        return t
+
+    # ---------------------------------------------------------------- GEMM phases of the persistent deep-level launch
+    def _conv_deep(self, a: "L.ConvArgs", rq: ConvRequest):
+        """one phase descriptor instead of a launch (norm_apply + streaming GEMM); the consumer computes the GroupNorm statistics itself,
+        FiLM comes from the fused GroupNorm-FiLM table"""
+        eng, out, label = self.eng, rq.out, rq.label
+        if rq.pro == L.PRO_LN or rq.y_f32 or rq.row_scale is not None:
+            raise DeepIneligible(f"{label}: prologue / epilogue option outside the persistent kernel")
+        if out.ld != out.C:
+            raise DeepIneligible(f"{label}: {out.C} output channels are not a multiple of 32 (padding columns would stay poisoned)")
+        a.out_gn_stats = a.out_rowstats = None
+        w8 = None
+        if eng.deep_dt == L.FP8:
+            # JEN1_FP8: e4m3 weights + per-row scales feed the fp8 matrix-core path of the unit; activations stay bf16 in HBM
+            w8 = eng.W.fp8(rq.w)
+            a.dtype, a.w, a.w_scale = L.FP8, w8[0].data_ptr(), w8[1].data_ptr()
+        self._film2(a, rq)
+        self._fill_segs(a, rq.extra_segs, shifts=True, padded_ok=False)
+        a.live_mask = self._live_mask(self.deep, rq)
+        if rq.m_split:
+            a.m_split, a.k_split = rq.m_split, rq.k_split
+        self._keep.append((a, rq, w8))
+        self.deep.add_conv(a, f"conv[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} M={a.M}", out,
+                           nb_max=self._deep_nb_cap(a, rq, 1 if w8 is not None else (4 if eng.dt == L.F32 else 2)))
+        self._traffic(a, rq, self.deep, w_es=1 if w8 is not None else None, scale_bytes=4 * a.M if w8 is not None else 0)
+        out.gn_valid = False
+        return out
+
+    def _deep_nb_cap(self, a: "L.ConvArgs", rq: ConvRequest, w_es: int) -> int:
+        """batch elements per unit of a GEMM phase (0: as many as fit): fewer per unit = smaller tiles to normalise and stage (the critical
+        path of a phase) on more workgroups, but every batch group streams the layer's weights again -- so only where the weights are small"""
+        eng = self.eng
+        nb_cap = eng.deep_nb_max
+        if eng.deep_unit_target > 0:
+            wbytes = (rq.taps * (a.c0 + a.c1) + rq.k_extra) * a.M * w_es
+            nb = 1
+            while nb < a.B and ((a.M // 16) * -(-a.B // nb) > eng.deep_unit_target or -(-a.B // nb) * wbytes > eng.deep_reread_cap):
+                nb *= 2
+            nb_cap = nb if nb_cap == 0 else min(nb_cap, nb)
+        return nb_cap
+
+    # ---------------------------------------------------------------- one launch per layer
+    def _conv_launch(self, a: "L.ConvArgs", rq: ConvRequest):
+        eng, lib, ops = self.eng, self.eng.lib, rq.ops
+        src0, src1, out, pro, label, force, extra_segs = rq.src0, rq.src1, rq.out, rq.pro, rq.label, rq.force, rq.extra_segs
         if self._prog is not None:
             # a launch behind phases of the open program: the program ends here; what this launch normalises gets its totals first
-            need = [s_ for s_ in (src0, src1) if s_ is not None and pro in (L.PRO_GN, L.PRO_GN_SILU) and not s_.gn_valid]
-            self._prog_close(need)
-        if pro in (L.PRO_GN, L.PRO_GN_SILU):
+            self._prog_close([s_ for s_ in rq.normed if not s_.gn_valid])
+        if rq.normed:
             assert src0.gn_valid and (src1 is None or src1.gn_valid), f"{label}: GroupNorm totals of a tensor produced inside a persistent launch were never written"
-        # the tile kernel takes up to two raw extra K segments at row shift 0 (a 1x1 shortcut riding on the block's second conv)
-        extras_tile = not extra_segs or (len(extra_segs) <= 2 and all(sh == 0 and e.cp == e.C and e.cp % 32 == 0 for e, sh in extra_segs))
         det_gn = det_rs = False
         if self.det:
             det_gn, det_rs = bool(a.out_gn_stats), bool(a.out_rowstats)
             a.out_gn_stats = a.out_rowstats = None
-        tile_ok = (pro in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU, L.PRO_SILU) and act == L.ACT_NONE and row_scale is None and (out.rs is None or det_rs)
-                   and extras_tile and not m_split and (pro not in (L.PRO_GN, L.PRO_GN_SILU) or gn[0] > 1 or src1 is None)
-                   and (pro not in (L.PRO_GN, L.PRO_GN_SILU) or gn[0] == 1 or
+        # the tile kernel takes up to two raw extra K segments at row shift 0 (a 1x1 shortcut riding on the block's second conv)
+        tile_ok = (pro in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU, L.PRO_SILU) and rq.act == L.ACT_NONE and rq.row_scale is None and (out.rs is None or det_rs)
+                   and _extras_fit_tile(extra_segs) and not rq.m_split and (not rq.normed or rq.gn[0] > 1 or src1 is None)
+                   and (not rq.normed or rq.gn[0] == 1 or
                         (a.gn_cpg % (a.c0 // FG) == 0 and (a.c1 == 0 or a.gn_cpg % (a.c1 // FG) == 0))))
-        self._choose_tiles(a, force, k_extra=(sum(e.cp for e, _ in extra_segs) // 32 if extra_segs else 0), tile_ok=tile_ok)
-        lib = eng.lib
+        self._choose_tiles(a, force, k_extra=rq.k_extra // 32, tile_ok=tile_ok)
         streaming = a.cfg in (L.CFG_S16x64, L.CFG_S16x32, L.CFG_S16x16)
         tiled = a.cfg in self.TILE_CFGS
         if extra_segs and tiled and not eng.fuse_shortcut_tiles:
@@ -838,18 +902,15 @@ class OpBuilder:
         if extra_segs and not streaming and not tiled:
             return None           # (a wide W* tile: the caller falls back to separate launches)
         if extra_segs and tiled:
-            for i, (e, sh) in enumerate(extra_segs):
-                assert e.B == a.B and e.L == a.L_in and e.t.dtype == eng.tdtype
-                a.seg[i].x, a.seg[i].ld, a.seg[i].shift, a.seg[i].kch = e.t.data_ptr(), e.ld, 0, e.cp // 32
-            a.nseg = len(extra_segs)
+            self._fill_segs(a, extra_segs)
+        ln_u = rq.ln[3] if pro == L.PRO_LN and len(rq.ln) > 3 else None
         want_direct = streaming and (force is None or force.get("direct", True))
-        if want_direct and pro == L.PRO_LN and ln_u is not None and a.ln_gamma is None and taps == 1 and stride == 1 \
+        if want_direct and pro == L.PRO_LN and ln_u is not None and a.ln_gamma is None and a.taps == 1 and a.stride == 1 \
                 and src1 is None and (force is None or force.get("ln_fold", True)):
             # LayerNorm folded into the epilogue: no pre-pass, the GEMM streams the raw rows
             a.ln_fold, a.ln_u = 1, ln_u.data_ptr()
             a.pro_mode = L.PRO_NONE
             a.direct = 1
-            self._keep.append(ln_u)
         elif want_direct and pro in (L.PRO_GN, L.PRO_GN_SILU, L.PRO_LN):
             # deep level: up to M/16 workgroups would each redo the prologue of the same tiny tile --
             # normalise / activate it ONCE (jen1_norm_apply), then stream the GEMM with no LDS staging
@@ -869,11 +930,8 @@ class OpBuilder:
                 na.groups, na.cpg, na.count, na.eps = a.gn_groups, a.gn_cpg, a.gn_count, a.gn_eps
                 na.film, na.film_row, na.film_step = a.film, a.film_row, a.film_step
                 na.film_off, na.film_C, na.film_ld = a.film_off, a.film_C, a.film_ld
-            nref = C.byref(na)
-            nfn = lambda s, nref=nref, lib=lib: L.check(lib.jen1_norm_apply(nref, s), "jen1_norm_apply")
-            nfn.label = f"norm_apply[{label}] mode={pro} B={a.B} L={a.L_in} C={ctot}"
-            nfn.kind = "norm_apply"
-            ops.append(nfn)
+            ops.append(Launch(lambda s, nref=C.byref(na), lib=lib: L.check(lib.jen1_norm_apply(nref, s), "jen1_norm_apply"), "norm_apply",
+                              f"norm_apply[{label}] mode={pro} B={a.B} L={a.L_in} C={ctot}"))
             self._keep.append((na, xh))
             a.x0, a.c0, a.ld0 = xh.data_ptr(), ctot, ctot
             a.x1, a.c1, a.ld1 = None, 0, 0
@@ -886,161 +944,117 @@ class OpBuilder:
             a.direct = 0          # a raw scaled second source needs the LDS path (or pre-scaled weights)
         if a.direct:
             a.kc_stage = max(1, (a.c0 + a.c1) // 32)
-        if m_split:
+        if rq.m_split:
             assert a.direct, "a dual-range GEMM needs the streaming (direct) mode"
-            a.m_split, a.k_split = m_split, k_split
+            a.m_split, a.k_split = rq.m_split, rq.k_split
         if extra_segs and not tiled:
             assert a.direct, "extra K segments need the streaming (direct) mode"
+            # the streaming kernel walks ONE segment list: its own (tap, source) pairs, then the extras
             segs = []
-            for tap in range(taps):
-                segs.append((a.x0, a.ld0, tap - pad_left, a.c0 // 32))
+            for tap in range(a.taps):
+                segs.append((a.x0, a.ld0, tap - a.pad_left, a.c0 // 32))
                 if a.c1:
-                    segs.append((a.x1, a.ld1, tap - pad_left, a.c1 // 32))
-            for e, sh in extra_segs:
-                assert e.B == a.B and e.L == a.L_in and e.t.dtype == eng.tdtype
-                segs.append((e.t.data_ptr(), e.ld, sh, e.cp // 32))
-            assert len(segs) <= L.MAX_SEG
-            a.nseg = len(segs)
+                    segs.append((a.x1, a.ld1, tap - a.pad_left, a.c1 // 32))
+            assert len(segs) + len(extra_segs) <= L.MAX_SEG
             for i, (xp, ld, sh, kch) in enumerate(segs):
                 a.seg[i].x, a.seg[i].ld, a.seg[i].shift, a.seg[i].kch = xp, ld, sh, kch
+            self._fill_segs(a, extra_segs, first=len(segs), shifts=True)
         if a.splitk > 1:
             self._splitk_args.append(a)
         # the prepared launch holds raw pointers: keep every tensor it references alive
-        self._keep.append((a, src0, src1, w, bias, out, residual, row_scale, gn, film, ln, extra_segs))
-        ref = C.byref(a)
-        fn = lambda s, ref=ref, lib=lib: L.check(lib.jen1_conv_gemm(ref, s), "jen1_conv_gemm")
+        self._keep.append((a, rq))
         # algorithmic traffic / work of this launch (weights once + conv input + output)
-        es = 4 if eng.dt == L.F32 else 2
-        c_real = src0.C + (src1.C if src1 is not None else 0)
-        c_extra = sum(e.C for e, _ in extra_segs) if extra_segs else 0
-        fn.kind = "conv_gemm"
-        fn.w_bytes = (taps * c_real + c_extra) * a.M * es
-        fn.act_bytes = a.B * a.L_in * (c_real + c_extra) * es + a.B * a.L_y * out_C * (4 if y_f32 else es)
-        fn.flops = 2 * (taps * c_real + c_extra) * a.M * a.B * a.L_out
-        fn.label = (f"conv[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} s={a.stride} M={a.M} "
-                    f"ps={a.ps_f}/{a.ps_off} Ly={a.L_y} pro={a.pro_mode} cfg={a.cfg} tb={a.tb} nb={a.nb} kst={a.kc_stage} sk={a.splitk} "
-                    f"direct={a.direct}")
-        ops.append(fn)
+        w_bytes, act_bytes, flops = self._traffic(a, rq)
+        ops.append(Launch(lambda s, ref=C.byref(a), lib=lib: L.check(lib.jen1_conv_gemm(ref, s), "jen1_conv_gemm"), "conv_gemm",
+                          f"conv[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} s={a.stride} M={a.M} "
+                          f"ps={a.ps_f}/{a.ps_off} Ly={a.L_y} pro={a.pro_mode} cfg={a.cfg} tb={a.tb} nb={a.nb} kst={a.kc_stage} sk={a.splitk} "
+                          f"direct={a.direct}", w_bytes=w_bytes, act_bytes=act_bytes, flops=flops))
         if det_gn:
             self.stats_launch(ops, out)
         if det_rs:
-            self.rowstats_launch(ops, out, m_split if m_split else out_C)
+            self.rowstats_launch(ops, out, rq.m_split if rq.m_split else rq.out_C)
         return out
 
     # ---------------------------------------------------------------- tile phases of the persistent launch (long levels)
-    def _conv_tile(self, a: "L.ConvArgs", *, src0, src1, w, bias, out, pro, gn, film, ln, act, residual, row_scale, y_f32, extra_segs,
-                   m_split, flat_w, label, taps, out_C):
-        eng = self.eng
-        if pro not in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU) or act != L.ACT_NONE or row_scale is not None or m_split or out.rs is not None:
+    def _conv_tile(self, a: "L.ConvArgs", rq: ConvRequest):
+        eng, out, label = self.eng, rq.out, rq.label
+        if rq.pro not in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU) or rq.act != L.ACT_NONE or rq.row_scale is not None or rq.m_split or out.rs is not None:
             raise DeepIneligible(f"{label}: option outside the tile phases")
-        if out.ld != out.C and not y_f32:
+        if out.ld != out.C and not rq.y_f32:
             raise DeepIneligible(f"{label}: {out.C} output channels are not a multiple of 32 (padding columns would stay poisoned)")
-        if extra_segs and not (len(extra_segs) <= 2 and all(sh == 0 and e.cp == e.C and e.cp % 32 == 0 for e, sh in extra_segs)):
+        if not _extras_fit_tile(rq.extra_segs):
             raise DeepIneligible(f"{label}: extra K segments outside the tile phases")
         if a.M % 128 != 0:
             raise DeepIneligible(f"{label}: {a.M} output rows are not a multiple of 128")
         if self._prog is not None and any(k in self._prog.kinds for k in ("gemm", "attn")):
             # tile phases and GEMM / attention phases are different kernels: the deep program ends here, with the totals of what this
             # layer normalises
-            self._prog_close([s_ for s_ in (src0, src1) if s_ is not None and pro in (L.PRO_GN, L.PRO_GN_SILU) and not s_.gn_valid and s_.part is None])
+            self._prog_close([s_ for s_ in rq.normed if not s_.gn_valid and s_.part is None])
         prog_was_open = self._prog is not None
         self._prog_open()
         prog = self._prog
-        a.out_gn_stats = a.out_rowstats = None
-        a.dtype = eng.dt                                     # (JEN1_FP8: the long levels stay bf16)
-        if pro in (L.PRO_GN, L.PRO_GN_SILU) and film is not None:
-            a.film = self.film2.data_ptr()
-        a.nseg = 0
-        if extra_segs:
-            for i, (e, sh) in enumerate(extra_segs):
-                assert e.B == a.B and e.L == a.L_in and e.t.dtype == eng.tdtype
-                a.seg[i].x, a.seg[i].ld, a.seg[i].shift, a.seg[i].kch = e.t.data_ptr(), e.ld, 0, e.cp // 32
-            a.nseg = len(extra_segs)
-        srcs_ = [src0] + ([src1] if src1 is not None else []) + [e for e, _ in (extra_segs or [])]
-        a.live_mask = sum(1 << i for i, s_ in enumerate(srcs_) if prog.is_live(s_.t)) | \
-            (256 if residual is not None and prog.is_live(residual.t) else 0)
-        # statistics of the normalised sources: per-tile partials of a tile phase, or the totals somebody wrote before the launch
-        st = []
-        if pro in (L.PRO_GN, L.PRO_GN_SILU):
-            for s_ in [src0] + ([src1] if src1 is not None else []):
+        try:
+            a.out_gn_stats = a.out_rowstats = None
+            a.dtype = eng.dt                                     # (JEN1_FP8: the long levels stay bf16)
+            self._film2(a, rq)
+            self._fill_segs(a, rq.extra_segs)
+            a.live_mask = self._live_mask(prog, rq)
+            # statistics of the normalised sources: per-tile partials of a tile phase, or the totals somebody wrote before the launch
+            st = []
+            for s_ in rq.normed:
                 if s_.part is not None:
                     pt, tiles, nfg = s_.part
                     st.append((pt.data_ptr(), tiles, nfg, prog.is_live(pt)))
                 elif s_.gn is not None and s_.gn_valid:
                     st.append((s_.gn.data_ptr(), 0, 32, False))
                 else:
-                    if not prog_was_open:
-                        self._prog = None
                     raise DeepIneligible(f"{label}: no GroupNorm statistics for a normalised source")
-        # geometry: all output rows in one unit up to 256; the smallest tile that needs the fewest rounds of the resident workgroups
-        bm = 256 if a.M % 256 == 0 else 128
-        mblocks = a.M // bm
-        best = None
-        for tb in ((16, 32, 48, 64) if bm == 128 else (16, 32)):
-            units = mblocks * a.B * -(-a.L_out // tb)
-            rounds = -(-units // max(prog.nwg, 1))
-            if best is None or rounds < best[0]:
-                best = (rounds, tb)
-        tb = best[1]
-        part, nfg_out = None, 0
-        if out.gn is not None and not y_f32:
-            nfg_out = 8 if (out_C % 8 == 0 and (out_C // 8) % 16 == 0) else 0
-            if not nfg_out:
-                if not prog_was_open:
-                    self._prog = None
-                raise DeepIneligible(f"{label}: {out_C} output channels do not split into 8 statistics groups of whole M tiles")
-            tiles = int(eng.lib.jen1_deep_tile_count(a.L_out, tb, a.M, bm))
-            part = torch.empty((a.B, tiles, nfg_out, 2), dtype=torch.float32, device=eng.device)
-        try:
+            # geometry: all output rows in one unit up to 256; the smallest tile that needs the fewest rounds of the resident workgroups
+            bm = 256 if a.M % 256 == 0 else 128
+            rounds = lambda tb: -(-((a.M // bm) * a.B * -(-a.L_out // tb)) // max(prog.nwg, 1))
+            tb = min((16, 32, 48, 64) if bm == 128 else (16, 32), key=rounds)
+            part, nfg_out = None, 0
+            if out.gn is not None and not rq.y_f32:
+                nfg_out = 8 if (rq.out_C % 8 == 0 and (rq.out_C // 8) % 16 == 0) else 0
+                if not nfg_out:
+                    raise DeepIneligible(f"{label}: {rq.out_C} output channels do not split into 8 statistics groups of whole M tiles")
+                tiles = int(eng.lib.jen1_deep_tile_count(a.L_out, tb, a.M, bm))
+                part = torch.empty((a.B, tiles, nfg_out, 2), dtype=torch.float32, device=eng.device)
             prog.add_tile(a, tb, bm, st, part, nfg_out,
                           f"tile[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} s={a.stride} M={a.M} tb={tb} bm={bm}", out)
         except DeepIneligible:
             if not prog_was_open:
-                self._prog = None
+                self._prog = None           # (the program this layer opened stays empty)
             raise
-        self._keep.append((a, src0, src1, w, bias, out, residual, gn, film, extra_segs, part))
+        self._keep.append((a, rq, part))
         if part is not None:
             out.part = (part, tiles, nfg_out)
         out.gn_valid = False
-        es_ = 4 if eng.dt == L.F32 else 2
-        c_real_ = src0.C + (src1.C if src1 is not None else 0)
-        c_extra_ = sum(e.C for e, _ in extra_segs) if extra_segs else 0
-        prog.w_bytes += (taps * c_real_ + c_extra_) * a.M * es_
-        prog.act_bytes += a.B * a.L_in * (c_real_ + c_extra_) * es_ + a.B * a.L_y * out_C * (4 if y_f32 else es_)
-        prog.flops += 2 * (taps * c_real_ + c_extra_) * a.M * a.B * a.L_out
+        self._traffic(a, rq, prog)
         return out
 
     # ---------------------------------------------------------------- phases of the sample-resident long-level launches
-    def _conv_long(self, a: "L.ConvArgs", *, src0, src1, w, bias, out, pro, gn, film, act, residual, row_scale, y_f32, extra_segs, m_split, label,
-                   taps, out_C):
-        eng = self.eng
-        if pro not in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU) or act != L.ACT_NONE or row_scale is not None or m_split or out.rs is not None or y_f32:
+    def _conv_long(self, a: "L.ConvArgs", rq: ConvRequest):
+        eng, out, label = self.eng, rq.out, rq.label
+        if rq.pro not in (L.PRO_NONE, L.PRO_GN, L.PRO_GN_SILU) or rq.act != L.ACT_NONE or rq.row_scale is not None or rq.m_split or out.rs is not None or rq.y_f32:
             raise LongIneligible(f"{label}: option outside the long-level phases")
         if out.ld != out.C:
             raise LongIneligible(f"{label}: {out.C} output channels are not a multiple of 32 (padding columns would stay poisoned)")
-        if extra_segs and not (len(extra_segs) <= 2 and all(sh == 0 and e.cp % 32 == 0 for e, sh in extra_segs)):
+        # (a source with padded channels -- the 257-channel network input -- may ride along: the padding columns meet zero weights)
+        if not _extras_fit_tile(rq.extra_segs, padded_ok=True):
             raise LongIneligible(f"{label}: extra K segments outside the long-level phases")
-        normed = [s_ for s_ in (src0, src1) if s_ is not None and pro in (L.PRO_GN, L.PRO_GN_SILU)]
         if self._prog is not None:
             # the deep program ends here, with the totals of what this layer normalises (tensors a deep phase produced)
-            self._prog_close([s_ for s_ in normed if not s_.gn_valid and s_.lp is None])
+            self._prog_close([s_ for s_ in rq.normed if not s_.gn_valid and s_.lp is None])
         prog = self._lprog
         assert prog is not None
         a.out_gn_stats = a.out_rowstats = None
         a.dtype = eng.dt                                     # (JEN1_FP8: the long levels stay bf16)
-        if pro in (L.PRO_GN, L.PRO_GN_SILU) and film is not None:
-            a.film = self.film2.data_ptr()
-        a.nseg = 0
-        if extra_segs:
-            for i, (e, sh) in enumerate(extra_segs):
-                assert e.B == a.B and e.L == a.L_in and e.t.dtype == eng.tdtype
-                a.seg[i].x, a.seg[i].ld, a.seg[i].shift, a.seg[i].kch = e.t.data_ptr(), e.ld, 0, e.cp // 32
-            a.nseg = len(extra_segs)
-        srcs_ = [src0] + ([src1] if src1 is not None else []) + [e for e, _ in (extra_segs or [])]
-        a.live_mask = sum(1 << i for i, s_ in enumerate(srcs_) if prog.is_live(s_.t)) | \
-            (256 if residual is not None and prog.is_live(residual.t) else 0)
+        self._film2(a, rq)
+        self._fill_segs(a, rq.extra_segs)
+        a.live_mask = self._live_mask(prog, rq)
         st, st_live = [], 0
-        for k, s_ in enumerate(normed):
+        for k, s_ in enumerate(rq.normed):
             if s_.lp is not None:
                 pt, entries, mblocks, nsub = s_.lp
                 st.append((pt.data_ptr(), entries, mblocks, nsub))
@@ -1052,20 +1066,15 @@ class OpBuilder:
         part, lp = None, None
         if out.gn is not None:
             mb, tiles, _ = prog.geometry(a.M, a.L_out)
-            if out_C not in (128, 256):
-                raise LongIneligible(f"{label}: statistics partials of {out_C} output channels")
+            if rq.out_C not in (128, 256):
+                raise LongIneligible(f"{label}: statistics partials of {rq.out_C} output channels")
             part = torch.empty((a.B, 8, tiles * mb, 2), dtype=torch.float32, device=eng.device)
-            lp = (part, tiles * mb, mb, out_C // 16)
+            lp = (part, tiles * mb, mb, rq.out_C // 16)
         prog.add_long(a, st, st_live, part, f"long[{label}] B={a.B} Lin={a.L_in} Lout={a.L_out} c0={a.c0} c1={a.c1} taps={a.taps} s={a.stride} M={a.M}", out)
-        self._keep.append((a, src0, src1, w, bias, out, residual, gn, film, extra_segs, part))
+        self._keep.append((a, rq, part))
         out.lp = lp
         out.gn_valid = False
-        es_ = 4 if eng.dt == L.F32 else 2
-        c_real_ = src0.C + (src1.C if src1 is not None else 0)
-        c_extra_ = sum(e.C for e, _ in extra_segs) if extra_segs else 0
-        prog.w_bytes += (taps * c_real_ + c_extra_) * a.M * es_
-        prog.act_bytes += a.B * a.L_in * (c_real_ + c_extra_) * es_ + a.B * a.L_y * out_C * es_
-        prog.flops += 2 * (taps * c_real_ + c_extra_) * a.M * a.B * a.L_out
+        self._traffic(a, rq, prog)
         return out
 
     def _prog_open(self):
@@ -1077,23 +1086,16 @@ class OpBuilder:
     # ---------------------------------------------------------------- deterministic statistics (Plan(deterministic=True))
     def stats_launch(self, ops, x: Act):
         """fine-group GroupNorm statistics of ``x`` in a fixed summation order (jen1_gn_stats: written, not accumulated)"""
-        lib = self.eng.lib
-        a = (x.t.data_ptr(), x.gn.data_ptr(), x.B, x.L, x.ld, self.eng.dt)
-        fn = lambda s, a=a, lib=lib: L.check(lib.jen1_gn_stats(*a, s), "jen1_gn_stats")
-        fn.kind = "stats"
-        fn.label = f"gn_stats[B={x.B} L={x.L} ld={x.ld}]"
-        self._keep.append(x)
-        ops.append(fn)
+        self._stats_op(ops, x, "jen1_gn_stats", (x.t.data_ptr(), x.gn.data_ptr(), x.B, x.L, x.ld, self.eng.dt), f"gn_stats[B={x.B} L={x.L} ld={x.ld}]")
 
     def rowstats_launch(self, ops, x: Act, C: int):
         """per-row LayerNorm sums over the first ``C`` columns of ``x`` (jen1_row_stats: one wave per row, fixed order)"""
-        lib = self.eng.lib
-        a = (x.t.data_ptr(), x.rs.data_ptr(), x.B * x.L, C, x.ld, self.eng.dt)
-        fn = lambda s, a=a, lib=lib: L.check(lib.jen1_row_stats(*a, s), "jen1_row_stats")
-        fn.kind = "stats"
-        fn.label = f"row_stats[rows={x.B * x.L} C={C}]"
+        self._stats_op(ops, x, "jen1_row_stats", (x.t.data_ptr(), x.rs.data_ptr(), x.B * x.L, C, x.ld, self.eng.dt), f"row_stats[rows={x.B * x.L} C={C}]")
+
+    def _stats_op(self, ops, x: Act, name: str, a: tuple, label: str):
+        fn = getattr(self.eng.lib, name)
         self._keep.append(x)
-        ops.append(fn)
+        ops.append(Launch(lambda s: L.check(fn(*a, s), name), "stats", label))
 
     @staticmethod
     def tile_geometry(B: int, L_out: int, BN: int):
@@ -1229,27 +1231,23 @@ class OpBuilder:
         """fin = (rowstats, u, b, ln_C, eps, finish_q, finish_kv): deferred LayerNorm finish (jen1_attention_fin)"""
         eng = self.eng
         rs_, u_, b_, lnC, eps, fq, fkv = fin if fin is not None else (None, None, None, 0, 0.0, 0, 0)
+        # launch and phase share the arguments up to the softmax scale and the LayerNorm finish (the launch also reads the row statistics)
+        head = (q.t.data_ptr(), kv_t.data_ptr(), kv_t.data_ptr(), out.t.data_ptr(), _ptr(kv_row), _ptr(kv_extra), _ptr(extra_row),
+                _ptr(extra_step), ld_extra, kx_off, vx_off, q.B, H, d, q.L, Nk, q.ld, q_off, ldkv, k_off, v_off, out.ld, 1 if causal else 0,
+                float(d) ** -0.5)
+        finish = (_ptr(u_), _ptr(b_), lnC, float(eps), fq, fkv)
+        label = f"attention B={q.B} H={H} d={d} Nq={q.L} Nk={Nk} causal={causal}"
+        self._keep.append((q, kv_t, out, kv_row, kv_extra, extra_row, extra_step, fin))
         if self._deep_on:
             kv_live = 1 if kv_row is None and kv_extra is None else 0      # self-attention: K / V come from the previous phase
             assert not kv_live or self.deep.is_live(kv_t)
             kv_live |= 2 if self.deep.is_live(q.t) else 0                  # bit 1: q's tensor was produced inside the launch
-            dargs = (q.t.data_ptr(), kv_t.data_ptr(), kv_t.data_ptr(), out.t.data_ptr(), _ptr(kv_row), _ptr(kv_extra),
-                     _ptr(extra_row), _ptr(extra_step), ld_extra, kx_off, vx_off, q.B, H, d, q.L, Nk, q.ld, q_off, ldkv, k_off, v_off,
-                     out.ld, 1 if causal else 0, float(d) ** -0.5, _ptr(u_), _ptr(b_), lnC, float(eps), fq, fkv, kv_live, eng.deep_dt)
-            self._keep.append((q, kv_t, out, kv_row, kv_extra, extra_row, extra_step, fin))
-            self.deep.add_attention(dargs, f"attention B={q.B} H={H} d={d} Nq={q.L} Nk={Nk} causal={causal}", out)
+            self.deep.add_attention(head + finish + (kv_live, eng.deep_dt), label, out)
             return
         if self._prog is not None:
             self._prog_close()
-        args = (q.t.data_ptr(), kv_t.data_ptr(), kv_t.data_ptr(), out.t.data_ptr(), _ptr(kv_row), _ptr(kv_extra),
-                _ptr(extra_row), _ptr(extra_step), ld_extra, kx_off, vx_off, q.B, H, d, q.L, Nk, q.ld, q_off, ldkv, k_off, v_off, out.ld,
-                1 if causal else 0, float(d) ** -0.5, _ptr(rs_), _ptr(u_), _ptr(b_), lnC, float(eps), fq, fkv, eng.deep_dt)
-        lib = eng.lib
-        self._keep.append((q, kv_t, out, kv_row, kv_extra, extra_row, extra_step, fin))
-        fn = lambda s, args=args, lib=lib: L.check(lib.jen1_attention_fin(*args, s), "jen1_attention")
-        fn.label = f"attention B={q.B} H={H} d={d} Nq={q.L} Nk={Nk} causal={causal}"
-        ops.append(fn)
-
+        args, lib = head + (_ptr(rs_),) + finish + (eng.deep_dt,), eng.lib
+        ops.append(Launch(lambda s, args=args, lib=lib: L.check(lib.jen1_attention_fin(*args, s), "jen1_attention"), label=label))
 
 
 class Plan(OpBuilder):
@@ -1351,39 +1349,41 @@ class Plan(OpBuilder):
         """phases are recorded into ONE program as long as consecutive layers are phases (tile phases of the long levels, GEMM /
         attention phases of the deep levels); a layer that runs as a launch closes it (_prog_close) and the next phase opens another"""
         if self._prog is None:
-            if self._deep_err is None:
-                self._deep_err = torch.zeros((16,), dtype=torch.int32, device=self.eng.device)
-            self._prog = DeepProgram(self.eng, leader=self.progs[0] if self.progs else None, err=self._deep_err)
+            self._prog = DeepProgram(self.eng, leader=self.progs[0] if self.progs else None, err=self._err_word())
             self.deep = self._prog
 
-    def _long_begin(self):
-        """from here on layers are phases of ONE sample-resident launch (LongProgram) until _long_end"""
-        self._long_open()               # (a deep program that is still open is closed by the first long layer, with the totals it needs)
-
-    def _long_open(self):
+    def _err_word(self) -> torch.Tensor:
+        """the error word all persistent launches of the plan share"""
         if self._deep_err is None:
             self._deep_err = torch.zeros((16,), dtype=torch.int32, device=self.eng.device)
-        self._lprog = LongProgram(self.eng, self.Beff, leader=self.progs[0] if self.progs else None, err=self._deep_err)
+        return self._deep_err
+
+    def _long_begin(self):
+        """from here on layers are phases of ONE sample-resident launch (LongProgram) until _long_end
+        (a deep program that is still open is closed by the first long layer, with the totals it needs)"""
+        self._lprog = LongProgram(self.eng, self.Beff, leader=self.progs[0] if self.progs else None, err=self._err_word())
         self._long_on = True
 
     def _long_end(self):
         prog, self._lprog, self._long_on = self._lprog, None, False
-        if prog is None or len(prog) == 0:
-            return
-        sync = self._stats(prog.sync_words()).view(torch.int32)
-        prog.finalize(sync)
+        if prog is not None and len(prog) > 0:
+            self._emit_program(prog, "long")
+
+    def _emit_program(self, prog: DeepProgram, kind: str):
+        """a recorded program becomes part of the step: its synchronisation area inside the per-step arena, ONE launch op and the
+        poisoning of its tensors at the head of the step"""
+        prog.finalize(self._stats(prog.sync_words()).view(torch.int32))
         self.progs.append(prog)
-        pz = lambda s, prog=prog: prog.poison(s)
-        pz.kind = "deep_poison"
-        pz.prog = prog
-        pz.label = f"long_poison[{prog.poison_tab.shape[0]} rows, {prog.poison_bytes} B]"
-        self.ops.insert(1, pz)
-        fn = lambda s, prog=prog: prog.launch(s)
-        fn.kind = "long"
-        fn.prog = prog
-        fn.label = f"long[{len(prog)} phases, {prog.Bs} samples x {prog.G} workgroups, {prog.lds} B LDS]"
-        fn.w_bytes, fn.act_bytes, fn.flops = prog.w_bytes, prog.act_bytes, prog.flops
-        self.ops.append(fn)
+        rows, nbytes = prog.poison_tab.shape[0], prog.poison_bytes
+        if kind == "long":
+            pz_label = f"long_poison[{rows} rows, {nbytes} B]"
+            label = f"long[{len(prog)} phases, {prog.Bs} samples x {prog.G} workgroups, {prog.lds} B LDS]"
+        else:
+            pz_label = f"deep_poison[{rows} tensors, {nbytes} B]"
+            label = f"deep[{len(prog)} phases ({prog.kinds.count('tile')} tile), {prog.nwg} workgroups, {prog.lds} B LDS]"
+        # right behind the arena reset: long before the launch, after the previous step's last reader
+        self.ops.insert(1, Launch(prog.poison, "deep_poison", pz_label, prog=prog))
+        self.ops.append(Launch(prog.launch, kind, label, prog=prog, w_bytes=prog.w_bytes, act_bytes=prog.act_bytes, flops=prog.flops))
 
     def _deep_begin(self):
         if self._prog is not None and "tile" in self._prog.kinds:
@@ -1407,21 +1407,7 @@ class Plan(OpBuilder):
             x.gn_valid = True
         self._prog = None
         self._deep_on = False
-        n = prog.sync_words()
-        sync = self._stats(n).view(torch.int32)
-        prog.finalize(sync)
-        self.progs.append(prog)
-        pz = lambda s, prog=prog: prog.poison(s)
-        pz.kind = "deep_poison"
-        pz.prog = prog
-        pz.label = f"deep_poison[{prog.poison_tab.shape[0]} tensors, {prog.poison_bytes} B]"
-        self.ops.insert(1, pz)          # right behind the arena reset: long before the launch, after the previous step's last reader
-        fn = lambda s, prog=prog: prog.launch(s)
-        fn.kind = "deep"
-        fn.prog = prog
-        fn.label = f"deep[{len(prog)} phases ({prog.kinds.count('tile')} tile), {prog.nwg} workgroups, {prog.lds} B LDS]"
-        fn.w_bytes, fn.act_bytes, fn.flops = prog.w_bytes, prog.act_bytes, prog.flops
-        self.ops.append(fn)
+        self._emit_program(prog, "deep")
 
     def take_error(self) -> int:
         """the error word of the plan's persistent launches (shared; see DeepProgram.take_error)"""
@@ -1558,19 +1544,30 @@ class Plan(OpBuilder):
 
     # ---------------------------------------------------------------- whole network
     def _build(self):
-        eng, spec, W = self.eng, self.eng.spec, self.eng.W
-        lib, dev = eng.lib, eng.device
-        B, Be, T, causal = self.B, self.Beff, self.T, self.causal
-        f32 = torch.float32
+        """the sections below in this order: the statistics arena hands out offsets, and ``acts`` lists activations, in creation order"""
+        eng, spec, Be = self.eng, self.eng.spec, self.Beff
         n_tr = len(spec.transformers())
-        lens = spec.level_lengths(T)
+        lens = spec.level_lengths(self.T)
         Ltr = max([lens[i + 1] for i, d in enumerate(spec.downs) if d.transformer] + [lens[-1]])
         deep_sync = 4 * (int(eng.lib.jen1_deep_sync_bytes(256)) // 4) if (self.deep_level is not None or self.tile_lens) else 0    # <= 4 programs of <= 256 phases
-        self.arena = torch.zeros(600 * Be * 64 + (4 * n_tr + 8) * Be * Ltr * 2 + 4096 + deep_sync + 64, dtype=f32, device=dev)
+        self.arena = torch.zeros(600 * Be * 64 + (4 * n_tr + 8) * Be * Ltr * 2 + 4096 + deep_sync + 64, dtype=torch.float32, device=eng.device)
         self._arena_used = 0
-        ops = self.ops
+        X0 = self._build_inputs()
+        self._build_time_tables()
+        self._build_context_kv_table()
+        self._build_unet(X0)
+        self._build_step_head()
+        if n_tr:
+            self._build_context_ops()
+        # split-K workspace shared by all launches of the plan (stream-ordered reuse)
+        self.finalize_workspace()
+        self.n_launch = len(self.ops) + (0 if self.table_mode else len(self.time_ops))
 
-        # ---- static inputs --------------------------------------------------------------------
+    def _build_inputs(self) -> Act:
+        """static inputs, the arena reset and the pack of [B,C,T] + context channels -> channel-last, CFG pair replicated: returns the
+        network's input activation"""
+        eng, spec, lib, dev, ops = self.eng, self.eng.spec, self.eng.lib, self.eng.device, self.ops
+        B, Be, T, f32 = self.B, self.Beff, self.T, torch.float32
         Cx, Cc = spec.in_channels, spec.ctx_ch0
         self.x_in = torch.zeros((B, Cx, T), dtype=f32, device=dev)
         self.ctx_in = torch.zeros((B, max(Cc, 1), T), dtype=f32, device=dev)
@@ -1589,11 +1586,9 @@ class Plan(OpBuilder):
         self.kv_row = torch.cat([ar, ar + B])[:Be].contiguous() if self.nrep == 2 else ar.clone()
         self.extra_row = torch.cat([ar, torch.full_like(ar, -1)])[:Be].contiguous() if self.nrep == 2 else ar.clone()
 
-        arena_bytes = self.arena.numel() * 4
-        arena_ptr = self.arena.data_ptr()
-        ops.append(lambda s: L.check(lib.jen1_memset_zero(arena_ptr, arena_bytes, s), "memset"))
+        arena = (self.arena.data_ptr(), self.arena.numel() * 4)
+        ops.append(Launch(lambda s: L.check(lib.jen1_memset_zero(*arena, s), "memset"), label="arena reset"))
 
-        # ---- 1. pack [B,C,T] + context channels -> channel-last, CFG pair replicated -------------
         X0 = self.new_act(Be, T, Cx + Cc, gn=True)
         if eng.pack_fixed_order:
             # the GroupNorm sums of the network input in a fixed order (per-block partials + one small launch that adds them): with the
@@ -1604,24 +1599,25 @@ class Plan(OpBuilder):
             X0.gn = torch.zeros((Be * 64,), dtype=f32, device=dev)
             a = (self.x_in.data_ptr(), self.ctx_in.data_ptr() if Cc else None, X0.t.data_ptr(), self._pack_parts.data_ptr(), B, Cx, Cc, T,
                  X0.ld, self.nrep, eng.dt)
-            pk = lambda s, a=a: L.check(lib.jen1_pack_input_parts(*a, s), "jen1_pack_input_parts")
+            pk = Launch(lambda s, a=a: L.check(lib.jen1_pack_input_parts(*a, s), "jen1_pack_input_parts"), "pack", "pack_input_parts")
             a2 = (self._pack_parts.data_ptr(), X0.gn.data_ptr(), B, T, X0.ld, self.nrep)
-            st = lambda s, a=a2: L.check(lib.jen1_gn_stats_from_parts(*a, s), "jen1_gn_stats_from_parts")
-            pk.kind = st.kind = "pack"
-            pk.label, st.label = "pack_input_parts", "gn_stats_from_parts"
+            st = Launch(lambda s, a=a2: L.check(lib.jen1_gn_stats_from_parts(*a, s), "jen1_gn_stats_from_parts"), "pack", "gn_stats_from_parts")
             ops += [pk, st]
             self.pack_ops, self.pack_stats_op = [pk, st], st
             self.pack_rows = (X0.t.data_ptr(), self._pack_parts.data_ptr(), X0.ld)      # where a fused step kernel writes the next input
         else:
             a = (self.x_in.data_ptr(), self.ctx_in.data_ptr() if Cc else None, X0.t.data_ptr(), None if self.det else X0.gn.data_ptr(), B, Cx, Cc, T,
                  X0.ld, self.nrep, eng.dt)
-            ops.append(lambda s, a=a: L.check(lib.jen1_pack_input(*a, s), "jen1_pack_input"))
+            ops.append(Launch(lambda s, a=a: L.check(lib.jen1_pack_input(*a, s), "jen1_pack_input"), label="pack_input"))
             if self.det:
                 self.stats_launch(ops, X0)
+        return X0
 
-        # ---- 2. time -> mapping -> FiLM scale/shift of all ResBlocks (model.py:204-223) -------------
-        # (timestep-only work: ``time_ops``; one row per batch element, or per schedule entry in table mode)
-        tops = self.time_ops
+    def _build_time_tables(self):
+        """time -> mapping -> FiLM scale/shift of all ResBlocks (model.py:204-223): timestep-only work (``time_ops``), one row per batch
+        element, or per schedule entry in table mode"""
+        eng, spec, W, lib, dev, ops, tops = self.eng, self.eng.spec, self.eng.W, self.eng.lib, self.eng.device, self.ops, self.time_ops
+        B, NT_, f32 = self.B, self.n_t, torch.float32
         mf, half = spec.mapping_features, spec.channels // 2
         # rows of the mapping tables: one per timestep, or (per_sample) one per (schedule entry, batch element), s-major
         NM = NT_ * B if self.per_sample else NT_
@@ -1634,20 +1630,18 @@ class Plan(OpBuilder):
             self.t_map = torch.zeros((NM,), dtype=torch.int64, device=dev)
             self.t_map_f = torch.zeros((NM,), dtype=torch.float32, device=dev)
         a = (v["to_time.0.0.weights"].data_ptr(), v["to_time.0.1.weight"].data_ptr(), v["to_time.0.1.bias"].data_ptr(), tf.data_ptr(), NM, half, mf)
-        tops.append(lambda s, a=a: self._time_features(a, s, mapping_rows=True))
+        tops.append(Launch(lambda s, a=a: self._time_features(a, s, mapping_rows=True), label=f"time_features of {NM} mapping rows"))
         self.feat_in = None
         if self.has_features:
             # model.py:218-222: the mapping's input is to_time(t) + to_features(features); both CFG halves read row b (film_row)
             Fc = int(spec.context_features)
             self.feat_in = torch.zeros((B, Fc), dtype=f32, device=dev)
             a = (self.feat_in.data_ptr(), v["to_features.0.weight"].data_ptr(), v["to_features.0.bias"].data_ptr(), tf.data_ptr(), NM, B, Fc, mf)
-            fop = lambda s, a=a: L.check(lib.jen1_features_into_mapping(*a, s), "jen1_features_into_mapping")
-            fop.kind, fop.label = "features", f"to_features into {NM} mapping rows"
-            tops.append(fop)
-        a = (tf.data_ptr(), v["to_mapping.0.weight"].data_ptr(), v["to_mapping.0.bias"].data_ptr(), m1.data_ptr(), NM, mf, mf, L.ACT_GELU)
-        tops.append(lambda s, a=a: L.check(lib.jen1_linear_f32(*a, s), "jen1_linear_f32"))
-        a = (m1.data_ptr(), v["to_mapping.2.weight"].data_ptr(), v["to_mapping.2.bias"].data_ptr(), self.mapping.data_ptr(), NM, mf, mf, L.ACT_GELU)
-        tops.append(lambda s, a=a: L.check(lib.jen1_linear_f32(*a, s), "jen1_linear_f32"))
+            tops.append(Launch(lambda s, a=a: L.check(lib.jen1_features_into_mapping(*a, s), "jen1_features_into_mapping"), "features",
+                               f"to_features into {NM} mapping rows"))
+        for k, src, dst in (("to_mapping.0", tf, m1), ("to_mapping.2", m1, self.mapping)):
+            a = (src.data_ptr(), v[f"{k}.weight"].data_ptr(), v[f"{k}.bias"].data_ptr(), dst.data_ptr(), NM, mf, mf, L.ACT_GELU)
+            tops.append(Launch(lambda s, a=a: L.check(lib.jen1_linear_f32(*a, s), "jen1_linear_f32"), label=f"linear_f32[{k}] rows={NM}"))
         map_t = Act(self._empty((1, NM, mf)), 1, NM, mf, mf)
         self._add_cast(tops, self.mapping, map_t.t)
         film_tab = torch.empty((NM, W.film_ld), dtype=f32, device=dev)
@@ -1677,17 +1671,20 @@ class Plan(OpBuilder):
                     tmp_a.add_(1.0).mul_(fa)
                     torch.mul(film, fb, out=tmp_b)
                     torch.add(tmp_a, tmp_b, out=film2)
-            tops.append(film2_op)
+            tops.append(Launch(film2_op, label="film2 table"))
         if self.per_sample:
             # head of every step, inside the captured graph: rows [step B, step B + B) of the tables -> the current tables
             a = (film_tab.data_ptr(), film2_tab.data_ptr() if has_film2 else None, self.film_cur.data_ptr(),
                  self.film2_cur.data_ptr() if has_film2 else None, self.step_idx.data_ptr(), B, W.film_ld, NT_)
-            sel = lambda s, a=a: L.check(lib.jen1_film_select(*a, s), "jen1_film_select")
-            sel.kind, sel.label = "film_select", f"film_select: {B} x {W.film_ld} floats of {'two tables' if has_film2 else 'one table'}"
-            sel.bytes = (2 if has_film2 else 1) * 2 * B * W.film_ld * 4
-            ops.append(sel)
+            ops.append(Launch(lambda s, a=a: L.check(lib.jen1_film_select(*a, s), "jen1_film_select"), "film_select",
+                              f"film_select: {B} x {W.film_ld} floats of {'two tables' if has_film2 else 'one table'}",
+                              bytes=(2 if has_film2 else 1) * 2 * B * W.film_ld * 4))
 
-        # ---- 3. time token of the text context -> its K/V row for every cross-attention ------------
+    def _build_context_kv_table(self):
+        """the K/V caches of the text context, and the time token of the context -> its K/V row for every cross-attention (``time_ops``)"""
+        eng, spec, W, lib, dev, tops = self.eng, self.eng.spec, self.eng.W, self.eng.lib, self.eng.device, self.time_ops
+        B, NT_, F, f32, v = self.B, self.n_t, spec.ctx_features, torch.float32, W.v
+        n_tr = len(spec.transformers())
         self.kv_ctx: Dict[str, torch.Tensor] = {}
         if n_tr:
             for t in spec.transformers():
@@ -1698,18 +1695,21 @@ class Plan(OpBuilder):
             tok = torch.empty((NT_, F), dtype=f32, device=dev)
             self._keep.append(tok)
             a = (v["to_time_embedding.0.0.weights"].data_ptr(), v["to_time_embedding.0.1.weight"].data_ptr(),
-                 v["to_time_embedding.0.1.bias"].data_ptr(), tok.data_ptr(), NT_, half, F)
-            tops.append(lambda s, a=a: self._time_features(a, s))
+                 v["to_time_embedding.0.1.bias"].data_ptr(), tok.data_ptr(), NT_, spec.channels // 2, F)
+            tops.append(Launch(lambda s, a=a: self._time_features(a, s), label=f"time_features of {NT_} time tokens"))
             tok_rs = torch.zeros((NT_ * 2,), dtype=f32, device=dev)     # outside the per-step arena
             tok_t = Act(self._empty((1, NT_, F)), 1, NT_, F, F, rs=tok_rs)
             self._add_cast(tops, tok, tok_t.t)
             a = (tok_t.t.data_ptr(), tok_t.rs.data_ptr(), NT_, F, F, eng.dt)
-            tops.append(lambda s, a=a: L.check(lib.jen1_row_stats(*a, s), "jen1_row_stats"))
+            tops.append(Launch(lambda s, a=a: L.check(lib.jen1_row_stats(*a, s), "jen1_row_stats"), label=f"row_stats[rows={NT_} C={F}]"))
             self.kvx = Act(self._empty((1, NT_, W.kvx_ld)), 1, NT_, W.kvx_ld, W.kvx_ld)
             self.conv(tops, src0=tok_t, w=W.w["kvx"], bias=W.v["kvx.bias"], out=self.kvx, pro=L.PRO_LN,
                       ln=(F, None, None, W.v["kvx.u"]))
 
-        # ---- 4. UNet1d.forward (model.py:243-262) ------------------------------------------------
+    def _build_unet(self, X0: Act):
+        """UNet1d.forward (model.py:243-262)"""
+        eng, spec, W, ops = self.eng, self.eng.spec, self.eng.W, self.ops
+        Be, causal = self.Beff, self.causal
         n_lv = len(spec.downs)
         first_tr = next((i for i, d in enumerate(spec.downs) if d.transformer), n_lv)
         # levels [0, long_levels) (+ to_in / to_out) run as phases of the two sample-resident launches
@@ -1803,16 +1803,19 @@ class Plan(OpBuilder):
         if self._prog is not None:
             self._prog_close()            # (the network's output is read by a launch that normalises nothing)
         self.deep = self._deep_prog if self._deep_prog is not None else (self.progs[-1] if self.progs else None)
+
+    def _build_step_head(self):
+        """ONE node at the head of the step: the arena reset and the poisoning of every persistent launch's tensors (every program's
+        synchronisation words live inside the arena: zeroed with it)"""
+        lib, dev, out = self.eng.lib, self.eng.device, self.net_out
+        arena_ptr, arena_bytes = self.arena.data_ptr(), self.arena.numel() * 4
         pzs = [op for op in self.ops if getattr(op, "kind", "") == "deep_poison"]
         if pzs and arena_bytes % 16 == 0 and arena_ptr % 16 == 0:
-            # ONE node at the head of the step: the arena reset and the poisoning of every persistent launch's tensors (every program's
-            # synchronisation words live inside the arena: zeroed with it)
             tab = torch.cat([op.prog.poison_tab for op in pzs], 0).contiguous()
             self._poison_tab = tab
             sync0 = pzs[0].prog.sync.data_ptr()
-            fused = lambda s, a=(tab.data_ptr(), tab.shape[0], sync0, arena_ptr, arena_bytes): L.check(lib.jen1_deep_poison_zero(*a, s), "jen1_deep_poison_zero")
-            fused.kind, fused.prog = "deep_poison", pzs[0].prog
-            fused.label = f"poison[{tab.shape[0]} rows, {sum(op.prog.poison_bytes for op in pzs)} B] + arena reset"
+            fused = Launch(lambda s, a=(tab.data_ptr(), tab.shape[0], sync0, arena_ptr, arena_bytes): L.check(lib.jen1_deep_poison_zero(*a, s), "jen1_deep_poison_zero"),
+                           "deep_poison", f"poison[{tab.shape[0]} rows, {sum(op.prog.poison_bytes for op in pzs)} B] + arena reset", prog=pzs[0].prog)
             # (a fused sampler runs this node's job in the tail launch of the previous step: DDIMStepper, jen1_step_tail)
             # -- without the rows of the network's output: that launch READS it (nobody polls it: its sentinels are not needed at all)
             lo = out.t.data_ptr()
@@ -1824,46 +1827,42 @@ class Plan(OpBuilder):
             self.poison_op, self.poison_args = fused, (self._tail_tab.data_ptr(), self._tail_tab.shape[0], sync0, arena_ptr, arena_bytes)
             self.ops = [fused] + [op for op in self.ops[1:] if getattr(op, "kind", "") != "deep_poison"]
 
-        # ---- 5. context ops: text K/V (hoisted out of the step loop) -------------------------------
-        if n_tr:
-            cops = self.ctx_ops
-            # (blocks.py:427-434: k, v = to_kv(norm_context(context)) * mask.)  One standardisation of the B * 128 text rows, ONE
-            # grouped matrix-core GEMM for the 13 layers (LayerNorm's gamma / beta live in the stacked weights / the group biases),
-            # mask and row map into the [2B][129][2C] caches in its epilogue, one launch for the unconditional slots.
-            self.emb_t = Act(self._empty((B, NL, F)), B, NL, F, F)
-            a = (self.emb_t.t.data_ptr(), B * NL, F, F, F, 1e-5, eng.dt)
-            # (the source pointer is the caller's float32 embedding when it can be read in place, else the plan's copy: _ctx_src)
-            cops.append(lambda s, a=a: L.check(lib.jen1_standardize_rows(self._ctx_src, *a, s), "jen1_standardize_rows"))
-            groups, fixed_rows = [], []
-            for t in spec.transformers():
-                kv = self.kv_ctx[t.name]
-                mid2 = kv.shape[-1]
-                groups.append((kv.data_ptr(), W.v[f"{t.name}.kv2.bias"].data_ptr(), W.kvx_off[t.name], mid2, mid2))
-                fixed_rows.append((eng.kv_fixed[t.name].data_ptr(), kv[B:].data_ptr(), mid2, 0))
-            self._kv_gemms = []
-            for part in _bgemm_parts(groups):
-                # (one launch for all layers whenever every layer's width is a multiple of the 128-column tile; else one per layer)
-                tab = L.bgemm_group_table([(c, b_, n0 - part[0][2], N, ldc) for c, b_, n0, N, ldc in part], dev)
-                g = L.BGemmArgs()
-                n_lo, n_hi = part[0][2], part[-1][2] + part[-1][3]
-                g.a, g.groups, g.row_scale = self.emb_t.t.data_ptr(), tab.data_ptr(), self.mask_in.data_ptr()
-                g.b = W.w["kv2_all"].data_ptr() + n_lo * F * W.w["kv2_all"].element_size()
-                g.M, g.Ntot, g.K, g.lda, g.ldb, g.n_groups = B * NL, n_hi - n_lo, F, F, F, len(part)
-                g.rows_in, g.rows_out, g.dtype, g.alpha = NL, spec.ctx_len, eng.dt, 1.0
-                g.group_align = _group_align(part)      # (256-column multiples: the product may run on the 256 x 256 tile form)
-                self._kv_gemms.append((g, tab))
-                fn = lambda s, g=g: L.check(lib.jen1_big_gemm(C.byref(g), s), "jen1_big_gemm")
-                fn.kind, fn.label = "big_gemm", f"to_kv of {len(part)} layers: [{B * NL} x {F}] x [{n_hi - n_lo} x {F}]^T"
-                fn.flops = 2.0 * B * NL * (n_hi - n_lo) * F
-                fn.bytes = (B * NL * F + (n_hi - n_lo) * F + B * NL * (n_hi - n_lo)) * W.w["kv2_all"].element_size()
-                cops.append(fn)
-            self._kv_fixed_tab = torch.tensor(fixed_rows, dtype=torch.int64).to(dev)
-            a = (self._kv_fixed_tab.data_ptr(), len(fixed_rows), self.mask_in.data_ptr(), B, spec.ctx_len, eng.dt)
-            cops.append(lambda s, a=a: L.check(lib.jen1_kv_fixed_fill(*a, s), "jen1_kv_fixed_fill"))
-
-        # ---- split-K workspace shared by all launches of the plan (stream-ordered reuse) -----------
-        self.finalize_workspace()
-        self.n_launch = len(self.ops) + (0 if self.table_mode else len(self.time_ops))
+    def _build_context_ops(self):
+        """context ops: text K/V (hoisted out of the step loop)"""
+        eng, spec, W, lib, dev, cops = self.eng, self.eng.spec, self.eng.W, self.eng.lib, self.eng.device, self.ctx_ops
+        B, F, NL = self.B, spec.ctx_features, spec.ctx_max_length
+        # (blocks.py:427-434: k, v = to_kv(norm_context(context)) * mask.)  One standardisation of the B * 128 text rows, ONE
+        # grouped matrix-core GEMM for the 13 layers (LayerNorm's gamma / beta live in the stacked weights / the group biases),
+        # mask and row map into the [2B][129][2C] caches in its epilogue, one launch for the unconditional slots.
+        self.emb_t = Act(self._empty((B, NL, F)), B, NL, F, F)
+        a = (self.emb_t.t.data_ptr(), B * NL, F, F, F, 1e-5, eng.dt)
+        # (the source pointer is the caller's float32 embedding when it can be read in place, else the plan's copy: _ctx_src)
+        cops.append(Launch(lambda s, a=a: L.check(lib.jen1_standardize_rows(self._ctx_src, *a, s), "jen1_standardize_rows"),
+                           label=f"standardize_rows[rows={B * NL} C={F}]"))
+        groups, fixed_rows = [], []
+        for t in spec.transformers():
+            kv = self.kv_ctx[t.name]
+            mid2 = kv.shape[-1]
+            groups.append((kv.data_ptr(), W.v[f"{t.name}.kv2.bias"].data_ptr(), W.kvx_off[t.name], mid2, mid2))
+            fixed_rows.append((eng.kv_fixed[t.name].data_ptr(), kv[B:].data_ptr(), mid2, 0))
+        self._kv_gemms = []
+        for part in _bgemm_parts(groups):
+            # (one launch for all layers whenever every layer's width is a multiple of the 128-column tile; else one per layer)
+            tab = L.bgemm_group_table([(c, b_, n0 - part[0][2], N, ldc) for c, b_, n0, N, ldc in part], dev)
+            g = L.BGemmArgs()
+            n_lo, n_hi = part[0][2], part[-1][2] + part[-1][3]
+            g.a, g.groups, g.row_scale = self.emb_t.t.data_ptr(), tab.data_ptr(), self.mask_in.data_ptr()
+            g.b = W.w["kv2_all"].data_ptr() + n_lo * F * W.w["kv2_all"].element_size()
+            g.M, g.Ntot, g.K, g.lda, g.ldb, g.n_groups = B * NL, n_hi - n_lo, F, F, F, len(part)
+            g.rows_in, g.rows_out, g.dtype, g.alpha = NL, spec.ctx_len, eng.dt, 1.0
+            g.group_align = _group_align(part)      # (256-column multiples: the product may run on the 256 x 256 tile form)
+            self._kv_gemms.append((g, tab))
+            cops.append(Launch(lambda s, g=g: L.check(lib.jen1_big_gemm(C.byref(g), s), "jen1_big_gemm"), "big_gemm",
+                               f"to_kv of {len(part)} layers: [{B * NL} x {F}] x [{n_hi - n_lo} x {F}]^T", flops=2.0 * B * NL * (n_hi - n_lo) * F,
+                               bytes=(B * NL * F + (n_hi - n_lo) * F + B * NL * (n_hi - n_lo)) * W.w["kv2_all"].element_size()))
+        self._kv_fixed_tab = torch.tensor(fixed_rows, dtype=torch.int64).to(dev)
+        a = (self._kv_fixed_tab.data_ptr(), len(fixed_rows), self.mask_in.data_ptr(), B, spec.ctx_len, eng.dt)
+        cops.append(Launch(lambda s, a=a: L.check(lib.jen1_kv_fixed_fill(*a, s), "jen1_kv_fixed_fill"), label=f"kv_fixed_fill of {len(fixed_rows)} layers"))
 
     def _time_features(self, a, s, mapping_rows: bool = False):
         """mapping_rows: the launch fills a mapping table, whose rows are (schedule entry, batch element) pairs in a per_sample plan"""
@@ -1896,10 +1895,7 @@ class Plan(OpBuilder):
 
     def run_time(self, stream: Optional[int] = None):
         """timestep-only work (time MLP -> FiLM table, time token -> K/V rows) for every entry of t_in"""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-        for op in self.time_ops:
-            op(stream)
+        self._run_ops(self.time_ops, stream)
 
     def run(self, stream: Optional[int] = None, pack: bool = True, poison: bool = True):
         if stream is None:
@@ -1911,20 +1907,15 @@ class Plan(OpBuilder):
     def run_pack(self, stream: Optional[int] = None):
         """only the ops that write the network input from x_in / ctx_in (a fused sampler runs them once per trajectory: its step kernel
         writes the next step's input itself, DDIMStepper)"""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-        for op in self.pack_ops:
-            op(stream)
+        self._run_ops(self.pack_ops, stream)
 
     def run_poison(self, stream: Optional[int] = None):
         """only the head-of-step sentinel / arena reset node (a fused sampler runs it once per trajectory; jen1_step_tail after that)"""
-        if stream is None:
-            stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-        self.poison_op(stream)
+        self._run_ops([self.poison_op], stream)
 
     def _add_cast(self, ops, src: torch.Tensor, dst: torch.Tensor):
         """dtype cast through torch (device plumbing, captured like any other node)."""
-        ops.append(lambda s, src=src, dst=dst: dst.view(src.shape).copy_(src))
+        ops.append(Launch(lambda s, src=src, dst=dst: dst.view(src.shape).copy_(src), label=f"cast {tuple(src.shape)} to {str(dst.dtype)[6:]}"))
 
     # ---------------------------------------------------------------- running
     def set_context(self, embedding: torch.Tensor, mask: Optional[torch.Tensor], stream: int):
