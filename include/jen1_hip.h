@@ -521,6 +521,27 @@ int jen1_resample(const float* x, float* y, const float* taps, const int32_t* fi
 /* frames (o inputs -> n outputs each) one workgroup of jen1_resample owns: min(2048 / n, 4096 / o), at least 1 */
 int jen1_resample_tile_frames(int o, int n);
 
+/*
+ * Long-form sampling on overlapping windows (csrc/windows.hip, jen1_amd/windows.py; not in the reference).  The latents of a piece
+ * live on a canvas [n][C][L] (float32); the sampler's batch rows [n W][C][T] are W windows of T frames per piece, row s W + j = window
+ * j of piece s, which starts at canvas frame offsets[j].  offsets: DEVICE int32 [W], ascending, 0 <= offsets[j] <= L - T; that every
+ * canvas frame is covered is the host's check (the table is not read on the host here).  Neither launch reads or writes outside its
+ * tensors whatever the table holds.  No allocation and no synchronisation: capturable.
+ *
+ * jen1_window_merge, in place on ``rows``: with k(p) = min(p + 1, T - p, ramp) and, over the windows j covering canvas frame l in
+ * ascending j, acc = fmaf((float)k_j, x_j, acc) from 0 at p = l - offsets[j], every covering row element becomes
+ * m = acc / (float)(sum k_j); ``canvas`` (or NULL) receives m at [s][c][l].  A frame covered by exactly one window keeps its bits (and
+ * canvas gets a copy).  One thread owns a canvas frame and all row elements lying on it: race-free and bit-reproducible.
+ * Checked: 1 <= W <= 8192 (the offsets are staged in LDS), 1 <= ramp <= T <= L, W x ramp <= 2^24, sizes inside the 64-bit index
+ * range the kernels use.
+ *
+ * jen1_window_gather: rows[z][s W + j][c][t] = canvas[z][s][c][offsets[j] + t] for z < lead, bit for bit, in one launch (lead = the
+ * schedule length for a per-step noise table, 1 for everything else).
+ */
+int jen1_window_merge(float* rows, const int32_t* offsets, int n, int W, int C, int T, int L, int ramp, float* canvas /* or NULL */,
+                      void* stream);
+int jen1_window_gather(const float* canvas, float* rows, const int32_t* offsets, int lead, int n, int W, int C, int T, int L, void* stream);
+
 const char* jen1_last_error(void);
 /* "gfx950" build tag + ABI version, for the loader's sanity check */
 const char* jen1_build_info(void);

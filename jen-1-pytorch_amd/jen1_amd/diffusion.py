@@ -372,8 +372,9 @@ class GaussianDiffusion(torch.nn.Module):
         return st
 
     def _ddim_generic(self, model, shape, conditioning, return_all_timesteps, causal, init_data, init_noise, step_noises,
-                      dropout_rows, known=None, keep=None, known_noise=None):
-        """Literal restatement of gdm.py:181-225 for arbitrary callables / unfused settings (+ the known-region blend in torch)."""
+                      dropout_rows, known=None, keep=None, known_noise=None, edit=None):
+        """Literal restatement of gdm.py:181-225 for arbitrary callables / unfused settings (+ the known-region blend in torch).
+        ``edit(x, i) -> x`` (not in the reference): applied to the latents after step i and its blend (``sample_windows``: the merge)."""
         batch = shape[0]
         audio = torch.randn(shape, device=self.device) if init_noise is None else init_noise.to(self.device, torch.float32).reshape(shape)
         eps_k = audio if known_noise is None else known_noise
@@ -393,6 +394,8 @@ class GaussianDiffusion(torch.nn.Module):
             audios.append(audio)
             if time_next < 0:
                 audio = x_start if known is None else blend_known(x_start, known, keep, eps_k, *kb[i])
+                if edit is not None:
+                    audio = edit(audio, i)
                 continue
             alpha, alpha_next = self.alphas_cumprod[time], self.alphas_cumprod[time_next]
             sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
@@ -401,6 +404,8 @@ class GaussianDiffusion(torch.nn.Module):
             audio = x_start * alpha_next.sqrt() + c * pred_noise + sigma * noise
             if known is not None:
                 audio = blend_known(audio, known, keep, eps_k, *kb[i])
+            if edit is not None:
+                audio = edit(audio, i)
         _check_model_errors(model)               # the LAST call's persistent launch too (forward checks its predecessor asynchronously)
         return audio if not return_all_timesteps else torch.stack(audios, dim=1)
 
@@ -426,11 +431,12 @@ class GaussianDiffusion(torch.nn.Module):
                                 known, keep_mask, known_noise)
 
     def _dpm_generic(self, model, shape, conditioning, return_all_timesteps=False, causal=False, init_data=None, init_noise=None,
-                     dropout_rows=None, order: int = 2, known=None, keep=None, known_noise=None):
+                     dropout_rows=None, order: int = 2, known=None, keep=None, known_noise=None, edit=None):
         """The sampler as a literal loop over any callable: x0_i is the clipped x-start of the model at (x_t, t), and
             x_next = (b0 x0_i + a x_t) + b1 x0_{i-1}
         with the float32 (b0, a, b1) of ``dpm_coeff_table`` (b1 = 0 on the first step: the history starts empty); the step that ends
-        at t < 0 returns x0_i.  The known-region blend acts on x_next, never on the history."""
+        at t < 0 returns x0_i.  The known-region blend acts on x_next, never on the history.  ``edit(x, i) -> x``: applied after step i
+        and its blend to the latents and to the history (``sample_windows``: the merge keeps both consistent across windows)."""
         batch = shape[0]
         rows = self.dpm_coeff_table(order)[0].tolist()
         audio = torch.randn(shape, device=self.device) if init_noise is None else init_noise.to(self.device, torch.float32).reshape(shape)
@@ -456,6 +462,8 @@ class GaussianDiffusion(torch.nn.Module):
             x0_prev = x_start
             if known is not None:
                 audio = blend_known(audio, known, keep, eps_k, *kb[i])
+            if edit is not None:
+                audio, x0_prev = edit(audio, i), edit(x0_prev, i)
         _check_model_errors(model)
         return audio if not return_all_timesteps else torch.stack(audios, dim=1)
 
@@ -476,13 +484,14 @@ class GaussianDiffusion(torch.nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, model, shape, conditioning, return_all_timesteps=False, init_data=None, *, init_noise=None,
                       step_noises=None, dropout_rows=None, use_graph: bool = True, fused: bool = True,
-                      known=None, keep_mask=None, known_noise=None):
+                      known=None, keep_mask=None, known_noise=None, edit=None):
         """gdm.py:165-179.  On the HIP denoiser the loop is the same fused stepper as DDIM with ancestral-sampling rows
         (``ddpm_coeff_table``): one replayed graph per step, uniform per-step noise as the reference draws it (gdm.py:161);
         ``fused=False`` (or any other callable) runs the literal loop below.  ``known`` / ``keep_mask`` / ``known_noise``: as in
-        ``ddim_sample``."""
+        ``ddim_sample``.  ``edit(x, i) -> x`` (not in the reference; it selects the literal loop): applied to the latents after step i
+        and its blend."""
         known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
-        if fused and self._fused_ok(model, conditioning, shape[0], self.num_timesteps):
+        if fused and edit is None and self._fused_ok(model, conditioning, shape[0], self.num_timesteps):
             st = self.stepper(model, shape, conditioning, causal=False, use_graph=use_graph, mode="ddpm",   # causal is not forwarded (gdm.py:145)
                               blend=known is not None)
             return self._fused_loop(st, shape, return_all_timesteps, init_data, init_noise, step_noises, dropout_rows,
@@ -500,6 +509,8 @@ class GaussianDiffusion(torch.nn.Module):
             audio, _ = self.p_sample(audio, t, model, conditioning, None if step_noises is None else step_noises[i].to(self.device))
             if known is not None:
                 audio = blend_known(audio, known, keep_mask, eps_k, *kb[i])
+            if edit is not None:
+                audio = edit(audio, i)
             audios.append(audio)
         _check_model_errors(model)
         return audio if not return_all_timesteps else torch.stack(audios, dim=1)
@@ -518,6 +529,53 @@ class GaussianDiffusion(torch.nn.Module):
             return self.p_sample_loop(model, shape, conditioning, return_all_timesteps=return_all_timesteps, init_data=init_data, **kw)
         return self.ddim_sample(model, shape, conditioning, return_all_timesteps=return_all_timesteps, causal=causal,
                                 init_data=init_data, **kw)
+
+    @torch.no_grad()
+    def sample_windows(self, model, plan, n: int, conditioning, *, sampler=None, causal=False, init_noise=None,
+                       step_noises: Optional[Sequence[torch.Tensor]] = None, dropout_rows: Optional[Sequence[torch.Tensor]] = None,
+                       known=None, keep_mask=None, known_noise=None, use_graph: bool = True, fused: bool = True):
+        """Long-form sampling (not in the reference): ``n`` pieces of ``plan.length`` frames, each denoised as the ``plan.W`` overlapping
+        windows of a ``jen1_amd.windows.WindowPlan`` -- ordinary batch rows, row ``s * W + j`` = window j of piece s -- which are merged
+        on the shared canvas after every step (``jen1_window_merge``; with ``sampler="dpmpp2m"`` the multistep history too).  Returns
+        the canvas ``[n, C, L]``.
+
+        ``conditioning`` is the ordinary dict with ``n * W`` rows (per-window prompts and ``global_cond`` are free).  ``init_noise``,
+        ``step_noises``, ``known``, ``keep_mask`` and ``known_noise`` are given ON THE CANVAS (``[n, C, L]``, ``[n, 1, L]``) and
+        gathered, so overlapping windows see identical noise and identical known audio at a shared frame; without injected draws the
+        start noise and the whole per-step table are drawn on the canvas.  ``sampler`` and the dispatch are ``sample``'s; the fused
+        stepper is built with one part (the merge works on one tensor holding every window) and keeps its cache key, ``rebind`` and
+        ``check``; its persistent launches, tail launch and graph are those of ``sample``.  ``fused=False``, or a model that is not
+        ``UNetCFG1d``, runs the literal loops with the merge as their ``edit``.  A plan of one window launches no merge and gives the
+        bits of ``sample`` on the same draws.  After the last merge the kept frames are set to ``known`` exactly
+        (``windows.finish_known``).  ``return_all_timesteps`` is not offered."""
+        from . import windows as WN
+        if sampler not in (None, "dpmpp2m"):
+            raise ValueError(f"unknown sampler {sampler!r}: None or 'dpmpp2m'")
+        C = _latent_channels(model, init_noise, known)
+        n, W, T = int(n), plan.W, plan.window
+        shape, cshape = (n * W, C, T), (n, C, plan.length)
+        WN.check_canvas_args(plan, n, C, conditioning, init_noise=(init_noise, C), known=(known, C), keep_mask=(keep_mask, 1),
+                             known_noise=(known_noise, C))
+        known, keep_mask, known_noise = check_known(cshape, known, keep_mask, known_noise, self.device)
+        mode = "dpmpp" if sampler == "dpmpp2m" else ("ddim" if self.is_ddim_sampling else "ddpm")
+        S = self.num_timesteps if mode == "ddpm" else self.sampling_timesteps
+        causal = bool(causal) and mode != "ddpm"              # (p_sample does not forward it, gdm.py:145)
+        if fused and self._fused_ok(model, conditioning, shape[0], S) and (mode != "dpmpp" or _step_pack_enabled(model)):
+            st = self.stepper(model, shape, conditioning, causal=causal, use_graph=use_graph, n_streams=1, mode=mode,
+                              blend=known is not None)
+            return WN.sample_fused(self, st, plan, n, init_noise=init_noise, step_noises=None if mode == "dpmpp" else step_noises,
+                                   dropout_rows=dropout_rows, known=known, keep_mask=keep_mask, known_noise=known_noise)
+        start, noises, kn, kp, ek = WN.literal_draws(self, plan, n, C, S, mode == "ddpm", mode != "dpmpp", init_noise, step_noises,
+                                                     known, keep_mask, known_noise)
+        edit = WN.merge_edit(plan) if W > 1 else None
+        if mode == "ddim":
+            rows = self._ddim_generic(model, shape, conditioning, False, causal, None, start, noises, dropout_rows, kn, kp, ek, edit=edit)
+        elif mode == "dpmpp":
+            rows = self._dpm_generic(model, shape, conditioning, False, causal, None, start, dropout_rows, 2, kn, kp, ek, edit=edit)
+        else:                                                 # (the literal ancestral loop lets the model draw the dropout rows)
+            rows = self.p_sample_loop(model, shape, conditioning, init_noise=start, step_noises=noises, fused=False, known=kn,
+                                      keep_mask=kp, known_noise=ek, edit=edit)
+        return WN.finish_known(WN.canvas_of(plan, rows), known, keep_mask)
 
     # ------------------------------------------------------------------ training (forward value)
     def q_sample(self, x_start, t, noise=None):
@@ -552,6 +610,17 @@ class GaussianDiffusion(torch.nn.Module):
         loss = self.loss_fn(model_out, target, reduction="none")
         per_sample = loss.reshape(loss.shape[0], -1).mean(dim=1)
         return per_sample if reduction == "none" else per_sample.mean()
+
+
+def _latent_channels(model, *tensors) -> int:
+    """the channel count of the latents a windowed sampler run works on: the denoiser's, or that of a given canvas tensor"""
+    spec = getattr(model, "spec", None)
+    if spec is not None:
+        return int(spec.out_channels)
+    for t in tensors:
+        if t is not None:
+            return int(t.shape[1])
+    raise ValueError("sample_windows: the model states no channel count (model.spec.out_channels); give init_noise on the canvas")
 
 
 def _step_pack_enabled(model) -> bool:

@@ -188,8 +188,20 @@ class Jen1:
     def generate(self, prompt, seed: int = -1, steps: int = 100, batch_size: int = 1, seconds: int = 30, use_gdm: bool = False,
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
                  inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
-                 decode: str = "whole", segment_scales: str = "unit", conditions=None, preserve_known: bool = False) -> torch.Tensor:
-        """``conditions`` (not in the reference, whose ``generate`` can only pass a prompt): further metadata for the conditioner --
+                 decode: str = "whole", segment_scales: str = "unit", conditions=None,
+                 window_seconds: Optional[float] = None, window_overlap: float = 0.5, preserve_known: bool = False) -> torch.Tensor:
+        """``window_seconds`` / ``window_overlap`` (not in the reference): long-form generation.  With ``seconds > window_seconds`` the
+        piece is not handed to the denoiser as one sample of a length it was never trained on: its latents live on one canvas of L
+        frames and are denoised as W overlapping windows of T frames -- T the frame count the encoder gives ``window_seconds``,
+        hop = max(1, round(T * (1 - window_overlap))) -- which run as ordinary batch rows (``batch_size * W`` of them) and are merged
+        on the canvas after every sampler step (``jen1_amd.windows``, ``sample_windows``).  The known audio is encoded for the whole
+        length as always; ``masked_input`` and ``mask`` are built on the canvas and gathered per window row, so here the concat context
+        is PER ROW -- a deviation from ``get_conditioning``'s first-element quirk, which cannot hold when windows differ.  ``prompt``
+        may be one string or a list of W strings (one per window, the same for every piece) and ``conditions`` additionally a list of
+        ``batch_size * W`` dicts (row ``s * W + j`` = window j of piece s).  ``preserve_known``, every ``sampler``, ``decode``,
+        ``segment_scales`` and ``output_sr`` act on the canvas latents unchanged.  With ``seconds <= window_seconds`` (or None) the call
+        is the call without the keywords, bit for bit.
+        ``conditions`` (not in the reference, whose ``generate`` can only pass a prompt): further metadata for the conditioner --
         a dict (the same for every row) or a list of ``batch_size`` dicts -- merged into the ``{"prompt": prompt}`` rows before the
         conditioner is called (``jen1_amd.conditioners.MultiConditionerHIP``: tempo, key, seconds_start, ...); the entries named by
         ``global_cond_ids`` reach the denoiser as ``features``.  None keeps the call as it was.
@@ -225,7 +237,8 @@ class Jen1:
             raise ValueError("segment_scales='known' needs known audio: task 'music_inpaint' or 'music_cont'")
         if decode == "segments" and not hasattr(self.audio_encoder, "decode_latents"):
             raise ValueError("decode='segments' needs an audio_encoder with decode_latents (jen1_amd.encodec.EncodecHIP)")
-        rows = self._metadata_rows(prompt, batch_size, conditions)
+        windowed = self._check_windows(seconds, window_seconds, window_overlap)
+        rows = None if windowed else self._metadata_rows(prompt, batch_size, conditions)
         torch.manual_seed(seed if seed != -1 else int(np.random.randint(0, 2 ** 32 - 1)))
         self.batch_size = batch_size
         diffusion, model = self.get_model_and_diffusion(steps, use_gdm)
@@ -235,25 +248,77 @@ class Jen1:
         keep = self.get_mask(total, start_s, end_s, batch_size)                 # 1 = keep the known audio, 0 = generate
         out = self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
                            preserve_known=preserve_known, sampler=sampler, decode=decode, segment_scales=segment_scales, length=total,
-                           metadata=rows)
+                           metadata=rows, windows=(float(window_seconds), float(window_overlap), conditions) if windowed else None)
         if output_sr is not None and int(output_sr) != self.sample_rate:
             from . import audio
             # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
             out = audio.resample(out, self.sample_rate, int(output_sr), device=out.device if out.device.type == "cuda" else self.device)
         return out
 
-    @torch.no_grad()
-    def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
-                steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None, decode: str = "whole",
-                segment_scales: str = "unit", length: Optional[int] = None, metadata=None) -> torch.Tensor:
-        B = wav.shape[0]
-        keep_samples = keep
-        if decode == "segments":
-            known, seg_frames, enc_scales = self.get_emb_segments(wav.to(self.device))
-            known = known.to(self.device)
+    @staticmethod
+    def _check_windows(seconds, window_seconds, window_overlap) -> bool:
+        """the ``window_seconds`` / ``window_overlap`` keywords: ValueError for values that make no plan, else whether the windowed path
+        is taken (a piece no longer than a window is today's call)"""
+        if window_seconds is None:
+            return False
+        if not float(window_seconds) > 0:
+            raise ValueError(f"window_seconds must be positive, not {window_seconds!r}")
+        if not 0.0 <= float(window_overlap) < 1.0:
+            raise ValueError(f"window_overlap must be in [0, 1), not {window_overlap!r}")
+        return float(seconds) > float(window_seconds)
+
+    def _window_rows(self, prompt, batch_size: int, W: int, conditions):
+        """the conditioner's metadata for the ``batch_size * W`` window rows (row s W + j = window j of piece s): ``prompt`` one string or
+        W of them, ``conditions`` None, one dict, ``batch_size`` dicts (one per piece) or ``batch_size * W`` (one per row)"""
+        if isinstance(prompt, (list, tuple)):
+            if len(prompt) != W:
+                raise ValueError(f"prompt is a list of {len(prompt)} strings, the piece has W = {W} windows")
+            prompts = list(prompt) * batch_size
         else:
-            known = self.get_emb(wav.to(self.device)).to(self.device)           # [B, 128, T']
-        keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
+            prompts = [prompt] * (batch_size * W)
+        if conditions is None:
+            extra = [{}] * (batch_size * W)
+        elif isinstance(conditions, dict):
+            extra = [conditions] * (batch_size * W)
+        else:
+            extra = list(conditions)
+            if len(extra) == batch_size and W > 1:
+                extra = [c for c in extra for _ in range(W)]
+            if len(extra) != batch_size * W or not all(isinstance(c, dict) for c in extra):
+                raise ValueError(f"conditions must be a dict or a list of batch_size = {batch_size} or batch_size * W = {batch_size * W} dicts")
+        return [{"prompt": p, **c} for p, c in zip(prompts, extra)]
+
+    def _sample_windows(self, diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler, n_samples,
+                        window_seconds, window_overlap, conditions) -> torch.Tensor:
+        """the windowed form of the sampler call of ``_sample``: canvas latents [B, 128, L] of the known audio -> WindowPlan -> per-row
+        conditioning -> ``sample_windows``"""
+        from .windows import WindowPlan
+        B, _, Lc = known.shape
+        n_win = int(window_seconds * self.sample_rate)
+        frames = getattr(self.audio_encoder, "segment_frames", None)          # (EncodecHIP: encodec.segment_frame_counts)
+        T = sum(frames(n_win)) if frames is not None else round(Lc * n_win / n_samples)
+        T = max(1, min(int(T), Lc))
+        plan = WindowPlan(Lc, T, max(1, round(T * (1.0 - window_overlap))))
+        cond = self.conditioner(self._window_rows(prompt, B, plan.W, conditions), self.device)
+        for k in self.global_cond_ids:
+            if k not in cond:
+                raise KeyError(f"global_cond_ids names {k!r}, which the conditioner did not return (it returned {sorted(cond)})")
+        # the concat context per row: every window sees its own crop of the masked known audio and of the mask
+        cond = get_conditioning(cond, self.cross_attn_cond_ids, self.global_cond_ids, ())
+        if len(self.input_concat_ids) > 0:
+            canvas = {"masked_input": known * keep, "mask": keep}
+            cond["input_concat_cond"] = torch.cat([plan.gather(canvas[k].contiguous()) for k in self.input_concat_ids], dim=1)
+        extra = {"sampler": sampler} if isinstance(diffusion, GaussianDiffusion) else {"step": steps}
+        if seed_with_audio:              # (``init_data`` of the plain call: the given audio's latents added to the start noise)
+            noise = torch.randn(tuple(known.shape), device=self.device)
+            extra.update(init_noise=noise + known, known_noise=noise if preserve_known else None)
+        if preserve_known:
+            extra.update(known=known, keep_mask=keep)
+        return diffusion.sample_windows(model, plan, B, cond, causal=causal, **extra)
+
+    def _sample_plain(self, diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler, metadata):
+        """the sampler call of ``_sample`` for a piece that is one sample of the denoiser"""
+        B = known.shape[0]
         cond = self.conditioner([{"prompt": prompt}] * B if metadata is None else metadata, self.device)
         for k in self.global_cond_ids:
             if k not in cond:
@@ -266,7 +331,25 @@ class Jen1:
             extra.update(known=known, keep_mask=keep)
         if sampler is not None:
             extra["sampler"] = sampler
-        z = diffusion.sample(model, tuple(known.shape), cond, causal=causal, init_data=known if seed_with_audio else None, **extra)
+        return diffusion.sample(model, tuple(known.shape), cond, causal=causal, init_data=known if seed_with_audio else None, **extra)
+
+    @torch.no_grad()
+    def _sample(self, diffusion, model, prompt, wav: torch.Tensor, keep: torch.Tensor, causal: bool, seed_with_audio: bool,
+                steps: int = 100, preserve_known: bool = False, sampler: Optional[str] = None, decode: str = "whole",
+                segment_scales: str = "unit", length: Optional[int] = None, metadata=None, windows=None) -> torch.Tensor:
+        B = wav.shape[0]
+        keep_samples = keep
+        if decode == "segments":
+            known, seg_frames, enc_scales = self.get_emb_segments(wav.to(self.device))
+            known = known.to(self.device)
+        else:
+            known = self.get_emb(wav.to(self.device)).to(self.device)           # [B, 128, T']
+        keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
+        if windows is not None:
+            z = self._sample_windows(diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler,
+                                     wav.shape[-1], *windows)
+        else:
+            z = self._sample_plain(diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler, metadata)
         # the reference hands the latents to its CPU decoder (generation.py:129-130); a decoder that lives on a device says so
         # (EncodecHIP.decoder_device) and gets them where they are
         if decode == "segments":

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -268,6 +268,9 @@ SYMBOLS = {
     # csrc/audio.hip: sample-rate / channel conversion of waveforms
     "jen1_resample": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int, _P]),
     "jen1_resample_tile_frames": (c_int, [c_int, c_int]),
+    # csrc/windows.hip: overlapping sampler windows on one canvas
+    "jen1_window_merge": (c_int, [_P, _P] + [c_int] * 6 + [_P, _P]),
+    "jen1_window_gather": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
     "jen1_last_error": (C.c_char_p, []),
     "jen1_build_info": (C.c_char_p, []),
     "jen1_abi_version": (c_int, []),

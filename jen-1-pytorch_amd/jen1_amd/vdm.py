@@ -82,6 +82,25 @@ class VDM(torch.nn.Module):
         p0, q0 = rows[0, 0:2].tolist()
         return kb.contiguous(), (p0, q0)
 
+    def stepper(self, model, shape, conditioning, step: int, causal=False, use_graph=True, blend=False, n_streams=None) -> DDIMStepper:
+        """one fused stepper (plan + schedule tables + captured graph) per (model, shape, causal, steps), built once and kept: later calls
+        rebind the conditioning"""
+        self._steps = step
+        cache = self.__dict__.setdefault("_steppers", {})
+        _STEPPER_CACHES.add(self)            # (an engine invalidation drops this model's steppers: model._drop_steppers_of)
+        key = (id(model), id(model.engine()), tuple(shape), bool(causal), bool(use_graph), int(step), float(self.embedding_scale),
+               bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic), bool(blend),
+               has_global_cond(model, conditioning), n_streams)
+        st = cache.get(key)
+        if st is not None and st.model is model and st.eng is model.engine():
+            st.rebind(conditioning)
+            return st
+        st = DDIMStepper(self, model, shape, conditioning, causal, use_graph, n_streams, 0, "vdm", blend=blend)
+        if len(cache) >= 8:
+            cache.pop(next(iter(cache)))
+        cache[key] = st
+        return st
+
     @torch.no_grad()
     def p_sample(self, x, i: int, model, conditioning, causal, dropout_rows=None):
         """one step of the repaired loop: ``i`` is the step index (see the module docstring)"""
@@ -94,9 +113,10 @@ class VDM(torch.nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, model, shape, conditioning, step=1000, return_all_timesteps=False, init_data=None, causal=False, *,
                       init_noise=None, dropout_rows: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True, fused: bool = True,
-                      known=None, keep_mask=None, known_noise=None):
+                      known=None, keep_mask=None, known_noise=None, edit=None):
         """``known`` / ``keep_mask`` / ``known_noise`` (not in the reference): the known-region blend, as in
-        ``GaussianDiffusion.ddim_sample``, at the levels of ``blend_table``"""
+        ``GaussianDiffusion.ddim_sample``, at the levels of ``blend_table``.  ``edit(x, i) -> x`` (not in the reference; it selects the
+        literal loop): applied to the latents after step i and its blend"""
         known, keep_mask, known_noise = check_known(shape, known, keep_mask, known_noise, self.device)
         audio = torch.randn(shape, device=self.device) if init_noise is None else init_noise.to(self.device, torch.float32).reshape(shape)
         eps_k = audio if known_noise is None else known_noise
@@ -104,25 +124,11 @@ class VDM(torch.nn.Module):
             audio = audio + init_data
         self.steps = torch.linspace(1., 0., step + 1, device=self.device)
         self.get_alpha_sigma(self.steps)
-        fused = (fused and isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+        fused = (fused and edit is None and isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
                  and film_tables_fit(model, conditioning, shape[0], step))          # (diffusion.FILM_TABLE_BUDGET)
         audios = [audio]
         if fused:
-            self._steps = step
-            # one stepper (plan + schedule tables + captured graph) per (model, shape, causal, steps): later calls rebind the conditioning
-            cache = self.__dict__.setdefault("_steppers", {})
-            _STEPPER_CACHES.add(self)            # (an engine invalidation drops this model's steppers: model._drop_steppers_of)
-            key = (id(model), id(model.engine()), tuple(shape), bool(causal), bool(use_graph), int(step), float(self.embedding_scale),
-                   bool(self.batch_cfg), bool(self.scale_cfg), bool(model.deterministic), known is not None,
-                   has_global_cond(model, conditioning))
-            st = cache.get(key)
-            if st is not None and st.model is model and st.eng is model.engine():
-                st.rebind(conditioning)
-            else:
-                st = DDIMStepper(self, model, shape, conditioning, causal, use_graph, None, 0, "vdm", blend=known is not None)
-                if len(cache) >= 8:
-                    cache.pop(next(iter(cache)))
-                cache[key] = st
+            st = self.stepper(model, shape, conditioning, step, causal=causal, use_graph=use_graph, blend=known is not None)
             if known is not None:
                 st.set_known(known, keep_mask, noise=eps_k)
             st.reset(audio)
@@ -150,6 +156,8 @@ class VDM(torch.nn.Module):
                 audio = self.p_sample(audio, i, model, conditioning, causal, drop)
                 if known is not None:
                     audio = blend_known(audio, known, keep_mask, eps_k, *kb[i])
+                if edit is not None:
+                    audio = edit(audio, i)
                 audios.append(audio)
         if fused:
             audio = st.x.clone()
@@ -163,6 +171,33 @@ class VDM(torch.nn.Module):
         """vdm.py:77-79"""
         return self.p_sample_loop(model, shape, conditioning, step, return_all_timesteps=return_all_timesteps, init_data=init_data,
                                   causal=causal, **kw)
+
+    @torch.no_grad()
+    def sample_windows(self, model, plan, n: int, conditioning, *, step=100, causal=False, init_noise=None,
+                       dropout_rows: Optional[Sequence[torch.Tensor]] = None, known=None, keep_mask=None, known_noise=None,
+                       use_graph: bool = True, fused: bool = True):
+        """long-form sampling on the overlapping windows of a ``jen1_amd.windows.WindowPlan``, merged on the shared canvas after every
+        step: ``GaussianDiffusion.sample_windows`` for this sampler (``init_noise`` / ``known`` / ``keep_mask`` / ``known_noise`` on the
+        canvas, ``conditioning`` with ``n * plan.W`` rows; returns the canvas ``[n, C, L]``)"""
+        from . import windows as WN
+        from .diffusion import _latent_channels
+        C = _latent_channels(model, init_noise, known)
+        n = int(n)
+        shape, cshape = (n * plan.W, C, plan.window), (n, C, plan.length)
+        WN.check_canvas_args(plan, n, C, conditioning, init_noise=(init_noise, C), known=(known, C), keep_mask=(keep_mask, 1),
+                             known_noise=(known_noise, C))
+        known, keep_mask, known_noise = check_known(cshape, known, keep_mask, known_noise, self.device)
+        if (fused and isinstance(model, UNetCFG1d) and not (self.embedding_scale != 1.0 and not self.batch_cfg)
+                and film_tables_fit(model, conditioning, shape[0], step)):
+            self.steps = torch.linspace(1., 0., step + 1, device=self.device)
+            self.get_alpha_sigma(self.steps)
+            st = self.stepper(model, shape, conditioning, step, causal=causal, use_graph=use_graph, blend=known is not None, n_streams=1)
+            return WN.sample_fused(self, st, plan, n, init_noise=init_noise, dropout_rows=dropout_rows, known=known, keep_mask=keep_mask,
+                                   known_noise=known_noise)
+        start, _, kn, kp, ek = WN.literal_draws(self, plan, n, C, step, False, False, init_noise, None, known, keep_mask, known_noise)
+        rows = self.p_sample_loop(model, shape, conditioning, step, causal=causal, init_noise=start, dropout_rows=dropout_rows, fused=False,
+                                  known=kn, keep_mask=kp, known_noise=ek, edit=WN.merge_edit(plan) if plan.W > 1 else None)
+        return WN.finish_known(WN.canvas_of(plan, rows), known, keep_mask)
 
     # ------------------------------------------------------------------ training (vdm.py:81-110)
     def q_sample(self, x_start, times, noise=None):
