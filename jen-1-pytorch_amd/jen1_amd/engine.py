@@ -34,7 +34,7 @@ import torch
 from . import lib as L
 from .config import ResSpec, TransformerSpec, UNetSpec
 from .packing import (conv_weight_to_gemm, convT_weight_to_gemm, ff_out_matrix, fold_layernorm, fold_linear_into_upsample,
-                      pack_gemm_weight)
+                      o1q2_matrix, o2f1_matrix, pack_gemm_weight, pqkv_matrix, s1q2_matrix)
 
 FG = 32  # fine groups per tensor for GroupNorm statistics
 
@@ -203,43 +203,31 @@ class Weights:
             # dual-range GEMM; the LayerNorm finish rstd (raw - mean u) + b moves into the attention kernel
             #   [x1 | qkv_raw] = [P ; Wqkv' P] xh + [p_b ; Wqkv' p_b]                        (blocks.py:530-531, :427-429)
             #   [x2 | q2_raw]  = [W_o | 0 ; Wq2' W_o | Wq2'] [a1 | x1] + [b_o ; Wq2' b_o]     (+ x1 on the x2 rows)
-            P64, pb64 = p[f"{n}.conv1d.conv.weight"][:, :, 0].double(), p[f"{n}.conv1d.conv.bias"].double()
-            wqkv64, wq264 = torch.cat([wq, wkv], 0).double(), wq2.double()
-            self.w[f"{n}.pqkv"] = pk(torch.cat([P64, wqkv64 @ P64], 0).float()[None]).flatten(0, 1).contiguous()
-            self.v[f"{n}.pqkv.bias"] = torch.cat([pb64, wqkv64 @ pb64]).float().contiguous()
-            Cc_, mid_ = P64.shape[0], wq264.shape[0]
+            # (packing.py: pqkv_matrix, o1q2_matrix)
+            flat = lambda w64: pk(w64.float()[None]).flatten(0, 1).contiguous()
+            wqkv, wo1, bo1 = torch.cat([wq, wkv], 0), p[f"{a}.attention.to_out.weight"], p[f"{a}.attention.to_out.bias"]
+            wm, bm = pqkv_matrix(p[f"{n}.conv1d.conv.weight"], p[f"{n}.conv1d.conv.bias"], wqkv)
+            self.w[f"{n}.pqkv"], self.v[f"{n}.pqkv.bias"] = flat(wm), bm.float().contiguous()
+            Cc_ = wo1.shape[0]
             zc = lambda m_: torch.zeros(m_, dtype=torch.float32, device=device)
             self.v[f"{n}.pqkv.u"] = torch.cat([zc(Cc_), self.v[f"{n}.qkv.u"]]).contiguous()
             self.v[f"{n}.pqkv.b"] = torch.cat([zc(Cc_), self.v[f"{n}.qkv.bias"]]).contiguous()
-            wo164, bo164 = p[f"{a}.attention.to_out.weight"].double(), p[f"{a}.attention.to_out.bias"].double()
-            top1 = torch.cat([wo164, torch.zeros(Cc_, Cc_, dtype=torch.float64, device=device)], 1)
-            bot1 = torch.cat([wq264 @ wo164, wq264], 1)
-            self.w[f"{n}.o1q2"] = pk(torch.cat([top1, bot1], 0).float()[None]).flatten(0, 1).contiguous()
-            self.v[f"{n}.o1q2.bias"] = torch.cat([bo164, wq264 @ bo164]).float().contiguous()
+            wm, bm = o1q2_matrix(wo1, bo1, wq2)
+            self.w[f"{n}.o1q2"], self.v[f"{n}.o1q2.bias"] = flat(wm), bm.float().contiguous()
             self.v[f"{n}.o1q2.u"] = torch.cat([zc(Cc_), self.v[f"{n}.q2.u"]]).contiguous()
             self.v[f"{n}.o1q2.b"] = torch.cat([zc(Cc_), self.v[f"{n}.q2.bias"]]).contiguous()
             # ONE position (the levels with T' = 1): softmax over a single key is 1, so self-attention is to_out(v) with
-            # v = to_v(norm_context(x1)) (blocks.py:355-380, :427-437), and a LayerNorm over the channels of a single position is a
-            # one-group GroupNorm -- the staging prologue of the GEMM that follows.  The whole sub-block is then
-            #   [x2 | q2_raw] = [W_o W_v | 0 ; Wq2' W_o W_v | Wq2'] [LN_ctx(x1) | x1] + [b_o ; Wq2' b_o]     (+ x1 on the x2 rows)
-            # (same biases and finish vectors as o1q2; gamma / beta of norm_context are applied by the prologue): no q / k projection, no
-            # attention phase.
-            wv64 = p[f"{a}.to_kv.weight"].double()[wq.shape[0]:]
-            wc64 = wo164 @ wv64
-            tops = torch.cat([wc64, torch.zeros(Cc_, Cc_, dtype=torch.float64, device=device)], 1)
-            bots = torch.cat([wq264 @ wc64, wq264], 1)
-            self.w[f"{n}.s1q2"] = pk(torch.cat([tops, bots], 0).float()[None]).flatten(0, 1).contiguous()
+            # v = to_v(norm_context(x1)), and a LayerNorm over the channels of a single position is a one-group GroupNorm -- the
+            # staging prologue of the GEMM that follows (packing.py: s1q2_matrix; same biases and finish vectors as o1q2; gamma /
+            # beta of norm_context are applied by the prologue): no q / k projection, no attention phase.
+            self.w[f"{n}.s1q2"] = flat(s1q2_matrix(wo1, p[f"{a}.to_kv.weight"][wq.shape[0]:], wq2))
             self.v[f"{n}.nc.g"] = f32(p[f"{a}.norm_context.weight"])
             self.v[f"{n}.nc.b"] = f32(p[f"{a}.norm_context.bias"])
             # streaming levels: cross-attention output projection and the first FeedForward layer as ONE
-            # dual-range GEMM over the K concat [a | x2]:  x3 = x2 + W_o a + b_o  (rows < C, K = a only) and
-            # f = gelu(W_1 x3 + b_1) = gelu((W_1 W_o) a + W_1 x2 + W_1 b_o + b_1)   (blocks.py:485-488, :440-446)
-            wo64, w164 = p[f"{x}.attention.to_out.weight"].double(), p[f"{b}.feed_forward.0.weight"].double()
-            top = torch.cat([wo64, torch.zeros(wo64.shape[0], w164.shape[1], dtype=torch.float64, device=device)], 1)
-            bot = torch.cat([w164 @ wo64, w164], 1)
-            self.w[f"{n}.o2f1"] = pk(torch.cat([top, bot], 0).float()[None]).flatten(0, 1).contiguous()
-            self.v[f"{n}.o2f1.bias"] = torch.cat([p[f"{x}.attention.to_out.bias"].double(),
-                                                  p[f"{b}.feed_forward.0.bias"].double() + w164 @ p[f"{x}.attention.to_out.bias"].double()]).float().contiguous()
+            # dual-range GEMM over the K concat [a | x2] (packing.py: o2f1_matrix)
+            wm, bm = o2f1_matrix(p[f"{x}.attention.to_out.weight"], p[f"{x}.attention.to_out.bias"],
+                                 p[f"{b}.feed_forward.0.weight"], p[f"{b}.feed_forward.0.bias"])
+            self.w[f"{n}.o2f1"], self.v[f"{n}.o2f1.bias"] = flat(wm), bm.float().contiguous()
             # streaming levels: the output 1x1 conv applied to x + ff2(f) is ONE GEMM over the K concat
             # [x | f] with weights [P | P @ W_ff2] (blocks.py:446, :488, :536): no x4 round trip
             wp64 = p[f"{n}.conv1d.conv.weight"][:, :, 0].double()

@@ -56,6 +56,48 @@ def fold_layernorm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
     return w * gamma[None, :], w @ beta
 
 
+def pqkv_matrix(w_proj: torch.Tensor, b_proj: torch.Tensor, w_qkv: torch.Tensor):
+    """The transformer's input 1x1 conv and the LayerNorm-folded q / k / v projection that reads its output as ONE dual-range
+    map over xh = GN(x):  [x1 | qkv_raw] = [P ; Wqkv' P] xh + [p_b ; Wqkv' p_b]  (reference blocks.py:530-531, :427-429).  The
+    LayerNorm finish rstd (raw - mean u) + b is the consumer's.  w_qkv: ``fold_layernorm`` rows [3 mid][C].  Returns
+    (W [C + 3 mid][C], bias [C + 3 mid]) in float64."""
+    P, pb, wqkv = (w_proj[:, :, 0] if w_proj.dim() == 3 else w_proj).double(), b_proj.double(), w_qkv.double()
+    return torch.cat([P, wqkv @ P], 0), torch.cat([pb, wqkv @ pb])
+
+
+def o1q2_matrix(w_o: torch.Tensor, b_o: torch.Tensor, w_q2: torch.Tensor):
+    """Self-attention's output projection and the LayerNorm-folded cross-attention query over the K concat [a1 | x1]:
+    [x2 | q2_raw] = [W_o | 0 ; Wq2' W_o | Wq2'] [a1 | x1] + [b_o ; Wq2' b_o]  (+ x1 on the x2 rows: the residual operand of the
+    launch).  w_o: [C][mid], w_q2: ``fold_layernorm`` rows [mid][C].  Returns (W [C + mid][mid + C], bias [C + mid]) in float64."""
+    wo, bo, wq2 = w_o.double(), b_o.double(), w_q2.double()
+    top = torch.cat([wo, torch.zeros(wo.shape[0], wq2.shape[1], dtype=torch.float64, device=wo.device)], 1)
+    bot = torch.cat([wq2 @ wo, wq2], 1)
+    return torch.cat([top, bot], 0), torch.cat([bo, wq2 @ bo])
+
+
+def s1q2_matrix(w_o: torch.Tensor, w_v: torch.Tensor, w_q2: torch.Tensor):
+    """ONE position: softmax over a single key is 1, so self-attention is to_out(to_v(norm_context(x1))) (reference
+    blocks.py:355-380, :427-437) and the whole sub-block is
+    [x2 | q2_raw] = [W_o W_v | 0 ; Wq2' W_o W_v | Wq2'] [LN_ctx(x1) | x1] + [b_o ; Wq2' b_o]  (+ x1 on the x2 rows), with the
+    bias of ``o1q2_matrix``.  w_v: the v rows of to_kv [mid][C], NOT folded (the launch's one-group GroupNorm prologue applies gamma /
+    beta of norm_context).  Returns W [C + mid][C + C] in float64."""
+    wo, wq2 = w_o.double(), w_q2.double()
+    wc = wo @ w_v.double()
+    top = torch.cat([wc, torch.zeros(wc.shape[0], wq2.shape[1], dtype=torch.float64, device=wc.device)], 1)
+    bot = torch.cat([wq2 @ wc, wq2], 1)
+    return torch.cat([top, bot], 0)
+
+
+def o2f1_matrix(w_o: torch.Tensor, b_o: torch.Tensor, w_1: torch.Tensor, b_1: torch.Tensor):
+    """Cross-attention's output projection and the first FeedForward layer over the K concat [a | x2]:  x3 = x2 + W_o a + b_o  (rows
+    < C, K = a only, + x2 as the residual operand) and  f = gelu(W_1 x3 + b_1) = gelu((W_1 W_o) a + W_1 x2 + W_1 b_o + b_1)
+    (reference blocks.py:485-488, :440-446).  Returns (W [C + F][mid + C], bias [C + F]) in float64."""
+    wo, bo, w1 = w_o.double(), b_o.double(), w_1.double()
+    top = torch.cat([wo, torch.zeros(wo.shape[0], w1.shape[1], dtype=torch.float64, device=wo.device)], 1)
+    bot = torch.cat([w1 @ wo, w1], 1)
+    return torch.cat([top, bot], 0), torch.cat([bo, b_1.double() + w1 @ bo])
+
+
 def ff_out_matrix(w_proj: torch.Tensor, b_proj: torch.Tensor, w_ff2: torch.Tensor, b_ff2: torch.Tensor):
     """The transformer's tail  y = P (x + W_ff2 f + b_ff2) + b_P  (reference blocks.py:446, :488, :536) as ONE linear map over
     the K concat [x | f]: returns (Wm = [P | P W_ff2]  [C][C + F],  b_m = b_P + P b_ff2) in float64.
