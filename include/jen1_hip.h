@@ -522,6 +522,57 @@ int jen1_resample(const float* x, float* y, const float* taps, const int32_t* fi
 int jen1_resample_tile_frames(int o, int n);
 
 /*
+ * Programme loudness of float32 waveforms and the gain that sets it (csrc/loudness.hip, jen1_amd/audio.py: loudness,
+ * normalize_audio; not in the reference): ITU-R BS.1770-4 integrated loudness with every channel weight 1.0.
+ *
+ * jen1_kweight_energy: x [rows][C][L], C in {1, 2}, L >= 1; hop = sr / 10 samples (100 ms), H = L / hop whole hops.
+ *   e [rows][C][H] float64:  e[r][c][h] = sum over the samples i of hop h of y[i]^2, y = the channel through the K-weighting cascade
+ *     (high shelf, then high-pass) started from zero state at sample 0.  e may be NULL when H = 0.
+ *   stats [rows][2] float64: the sum of x^2 over all C L samples of the row, and max |x|.
+ *   coef: HOST pointer to 10 doubles, read during the call: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (a0 = 1;
+ *     jen1_amd/audio.py: k_weighting computes them for any rate).
+ * The recurrence state and every sum are float64.  A channel is cut into chunks of N = jen1_kweight_chunk(hop) samples and the
+ * chunk-to-chunk dependency is carried as state, exactly: each chunk's end state from zero state, a carry pass
+ * s[c + 1] = A^N s[c] + f[c] (A^N formed on the host in float64), then the filter again from every chunk's true start state, then
+ * the chunks of a hop summed in ascending order -- four launches in stream order, ordinary kernel boundaries.  Every sum has one
+ * fixed order and there are no float atomics: bit-reproducible.  No allocation and no synchronisation: capturable.  workspace:
+ * DEVICE scratch, 8-byte aligned, of at least jen1_kweight_energy_workspace_bytes(rows, C, L, hop) bytes (0 for arguments the call
+ * would refuse); its contents before and after the call mean nothing.
+ */
+int jen1_kweight_energy(const float* x, double* e, double* stats, const double* coef /* HOST */, int rows, int C, int64_t L, int hop,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int64_t jen1_kweight_energy_workspace_bytes(int rows, int C, int64_t L, int hop);
+/* samples per chunk: the largest divisor of hop up to 128; where that is below 16 (hop = 2 x a prime, ...) the smallest divisor
+ * above 128 instead, hop itself at the worst.  A chunk never straddles a hop. */
+int jen1_kweight_chunk(int hop);
+/* chunks one workgroup of the two filter passes stages in LDS: min(128, 15872 / (N | 1)) */
+int jen1_kweight_tile_chunks(int hop);
+
+/*
+ * e [rows][C][H] -> lufs [rows] float64, one workgroup per row.  With J = max(0, H - 3) blocks of 4 hops (400 ms, 75 % overlap):
+ *   s[j] = sum_c (e[c][j] + e[c][j+1] + e[c][j+2] + e[c][j+3]) / (4 hop),   l[j] = -0.691 + 10 log10 s[j]
+ *   A = {j : l[j] > -70};   G = -0.691 + 10 log10(mean_{j in A} s[j]) - 10;   lufs = -0.691 + 10 log10(mean_{j in A, l[j] > G} s[j])
+ * and -inf when J = 0 or either set is empty.  Sums in a fixed order.
+ */
+int jen1_loudness_gate(const double* e, double* lufs, int rows, int C, int64_t H, int hop, void* stream);
+
+enum { JEN1_GAIN_LOUDNESS = 0, JEN1_GAIN_PEAK = 1, JEN1_GAIN_RMS = 2, JEN1_GAIN_CLIP = 3 };
+enum { JEN1_LIMIT_NONE = 0, JEN1_LIMIT_CLIP = 1, JEN1_LIMIT_TANH = 2 };
+/*
+ * y[r] = limit(g[r] * x[r]) over x, y [rows][C][L] float32 (y == x is allowed), one launch.  The gain is formed on the device per row
+ * in float64 from lufs [rows] (jen1_loudness_gate), stats [rows][2] (jen1_kweight_energy) and target [rows] (float64, LUFS), rounded
+ * to float32 once and also written to gain [rows].  With rms = sqrt(stats[r][0] / (C L)) and peak = stats[r][1]:
+ *   JEN1_GAIN_LOUDNESS  10^((target - lufs) / 20); 1 where lufs is not finite or rms < energy_floor
+ *   JEN1_GAIN_PEAK      10^(-headroom_db / 20) / peak; 1 where peak == 0
+ *   JEN1_GAIN_RMS       10^(-headroom_db / 20) / rms;  1 where rms == 0
+ *   JEN1_GAIN_CLIP      1
+ * limit: JEN1_LIMIT_NONE, JEN1_LIMIT_CLIP (clamp to [-1, 1]) or JEN1_LIMIT_TANH.  lufs and target are read by the loudness strategy
+ * only, stats by every strategy but JEN1_GAIN_CLIP; the others may pass NULL.
+ */
+int jen1_gain_apply(const float* x, float* y, float* gain, const double* lufs, const double* stats, const double* target, int rows,
+                    int C, int64_t L, int strategy, int limit, double headroom_db, double energy_floor, void* stream);
+
+/*
  * Long-form sampling on overlapping windows (csrc/windows.hip, jen1_amd/windows.py; not in the reference).  The latents of a piece
  * live on a canvas [n][C][L] (float32); the sampler's batch rows [n W][C][T] are W windows of T frames per piece, row s W + j = window
  * j of piece s, which starts at canvas frame offsets[j].  offsets: DEVICE int32 [W], ascending, 0 <= offsets[j] <= L - T; that every

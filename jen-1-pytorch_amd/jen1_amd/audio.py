@@ -16,6 +16,10 @@ form: ``taps [n, W]`` and ``first [n]`` with ``h[p][first[p] + t] = taps[p][t]``
 a dependency: parity with the packages themselves is not pinned.
 
 There is no fallback: whatever needs arithmetic runs on the HIP kernel of ``device``; only "nothing to do" returns without it.
+
+Behind the decoder (and in front of the encoder, for training clips) the same file sets the LEVEL of a waveform, which the reference
+never does: ``loudness`` (ITU-R BS.1770-4 integrated loudness) and ``normalize_audio`` (gain to a target + limiter) on
+csrc/loudness.hip; see the second half of this file and DESIGN.md section 10e.
 """
 from __future__ import annotations
 
@@ -138,3 +142,153 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: i
     if int(sr) == int(target_sr) and c_in == target_channels:
         return wav
     return _run(wav, sr, target_sr, int(target_channels), device)
+
+
+# ---------------------------------------------------------------------------------------------------------------- loudness
+#
+# ITU-R BS.1770-4 integrated loudness with every channel weight 1.0 (mono and stereo), and the gain + limiter that bring a waveform
+# to a target (csrc/loudness.hip: jen1_kweight_energy, jen1_loudness_gate, jen1_gain_apply).  Not in the reference, whose output
+# has whatever level the decoder gives it (Encodec 48 kHz: unit RMS per segment, peaks far above full scale).
+STRATEGIES = ("loudness", "peak", "rms", "clip")
+LIMITS = ("none", "clip", "tanh")
+DEFAULT_HEADROOM_DB = {"loudness": 0.0, "peak": 1.0, "rms": 18.0, "clip": 0.0}
+
+
+def k_weighting(sr: int) -> np.ndarray:
+    """the K-weighting cascade at sample rate ``sr`` as float64 second-order sections ``[2, 6]``: rows (b0, b1, b2, 1, a1, a2) of the
+    high shelf and of the high-pass behind it.  The analogue prototypes of BS.1770 through the bilinear transform with pre-warping
+    (K = tan(pi f0 / sr)); at 48 kHz this reproduces the standard's tables to 1e-15.  Host only (numpy)."""
+    sr = int(sr)
+    if sr <= 0:
+        raise ValueError(f"sample rate must be positive, not {sr}")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    high = [1.0, -2.0, 1.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    return np.array([shelf, high], dtype=np.float64)
+
+
+def hop_samples(sr: int) -> int:
+    """the 100 ms hop of the meter's 400 ms blocks in samples; the rate must give a whole number"""
+    sr = int(sr)
+    if sr <= 0 or sr % 10 != 0:
+        raise ValueError(f"the loudness meter needs a positive sample rate that is a multiple of 10 (a whole 100 ms hop), not {sr}")
+    return sr // 10
+
+
+def chunk_samples(hop: int) -> int:
+    """samples per chunk of the time-parallel K-weighting filter for this hop: the library's own rule"""
+    from . import lib as L
+    return int(L.load().jen1_kweight_chunk(int(hop)))
+
+
+def _check_wave(wav: torch.Tensor, what: str) -> None:
+    if wav.dtype != torch.float32:
+        raise TypeError(f"waveforms are float32, not {wav.dtype}")
+    if wav.dim() < 2:
+        raise ValueError(f"{what}: audio must have at least a channel and a time axis")
+    if int(wav.shape[-2]) not in (1, 2):
+        raise ValueError(f"{what}: audio must have one or two channels, not {int(wav.shape[-2])}")
+    if int(wav.shape[-1]) < 1:
+        raise ValueError(f"{what}: the time axis is empty")
+
+
+def _device(device, what: str) -> torch.device:
+    from . import lib as L
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise L.Jen1HipError(f"{what} runs on a GPU, not on {dev}: there is no CPU fallback")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _measure(x: torch.Tensor, sr: int, gate: bool = True):
+    """x [rows, C, L] float32, contiguous, on a GPU (the current device) -> (lufs float64 [rows] or None, stats float64 [rows, 2]):
+    the four launches of jen1_kweight_energy and, with ``gate``, jen1_loudness_gate behind them on the current stream"""
+    from . import lib as L
+    lib = L.load()
+    rows, C, n = (int(s) for s in x.shape)
+    hop = hop_samples(sr)
+    H = n // hop
+    dev = x.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    nbytes = int(lib.jen1_kweight_energy_workspace_bytes(rows, C, n, hop))
+    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+    e = torch.empty((rows, C, H), dtype=torch.float64, device=dev)
+    stats = torch.empty((rows, 2), dtype=torch.float64, device=dev)
+    sos = k_weighting(sr)
+    coef = (L.C.c_double * 10)(*sos[0, [0, 1, 2, 4, 5]], *sos[1, [0, 1, 2, 4, 5]])
+    L.check(lib.jen1_kweight_energy(x.data_ptr(), e.data_ptr() if H else None, stats.data_ptr(), coef, rows, C, n, hop, work.data_ptr(), nbytes,
+                                    stream), "jen1_kweight_energy")
+    if not gate:
+        return None, stats
+    lufs = torch.empty((rows,), dtype=torch.float64, device=dev)
+    L.check(lib.jen1_loudness_gate(e.data_ptr() if H else None, lufs.data_ptr(), rows, C, H, hop, stream), "jen1_loudness_gate")
+    return lufs, stats
+
+
+def loudness(wav: torch.Tensor, sr: int, device="cuda") -> torch.Tensor:
+    """BS.1770-4 integrated loudness in LUFS of ``wav [..., C, L]`` (float32, C in {1, 2}, channel weights 1.0): float64 ``[...]`` on
+    wav's device.  ``-inf`` for a row shorter than one 400 ms block or with nothing above the gates."""
+    _check_wave(wav, "loudness")
+    hop_samples(sr)
+    src = wav.device
+    dev = _device(device, "the loudness meter")
+    lead = tuple(wav.shape[:-2])
+    x = wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:]))
+    with torch.cuda.device(dev):
+        lufs, _ = _measure(x, sr)
+    return lufs.reshape(lead).to(src)
+
+
+def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", target_lufs=-14.0, headroom_db=None, limit: str = "clip",
+                    energy_floor: float = 2e-3, device="cuda", return_gain: bool = False):
+    """``limit(g * wav)`` over ``wav [..., C, L]`` (float32, C in {1, 2}) with one gain per row ``[...]``, formed on the device (nothing is
+    read back on the way) and rounded to float32 once:
+
+        "loudness"  10^((target_lufs - loudness) / 20); 1 for a row whose loudness is -inf or whose RMS is below ``energy_floor`` (such a
+                    row comes back bit for bit)
+        "peak"      10^(-headroom_db / 20) / max |wav| (headroom_db: 1 by default); 1 for an all-zero row
+        "rms"       10^(-headroom_db / 20) / rms (headroom_db: 18 by default); 1 for an all-zero row
+        "clip"      1
+
+    ``target_lufs``: a float or a tensor ``[...]``, one target per row.  ``limit``: "none", "clip" (clamp to [-1, 1]) or "tanh".  The result is
+    a new tensor on wav's device; ``return_gain=True`` returns ``(result, gain float32 [...])``."""
+    from . import lib as L
+    if strategy not in STRATEGIES:
+        raise ValueError(f"unknown strategy {strategy!r}: one of {STRATEGIES}")
+    if limit not in LIMITS:
+        raise ValueError(f"unknown limit {limit!r}: one of {LIMITS}")
+    _check_wave(wav, "normalize_audio")
+    hop_samples(sr)
+    lead = tuple(wav.shape[:-2])
+    if torch.is_tensor(target_lufs) and tuple(target_lufs.shape) != lead:
+        raise ValueError(f"target_lufs {tuple(target_lufs.shape)} must have one entry per row {lead}")
+    src = wav.device
+    dev = _device(device, "normalize_audio")
+    x = wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:]))
+    rows, C, n = (int(s) for s in x.shape)
+    if torch.is_tensor(target_lufs):
+        target =target_lufs.to(dev, torch.float64).contiguous().reshape(-1)
+    else:
+        target = torch.full((rows,), float(target_lufs), dtype=torch.float64, device=dev)
+    headroom = DEFAULT_HEADROOM_DB[strategy] if headroom_db is None else float(headroom_db)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        lufs, stats = (None, None) if strategy == "clip" else _measure(x, sr, gate=strategy == "loudness")
+        y = torch.empty_like(x)
+        gain = torch.empty((rows,), dtype=torch.float32, device=dev)
+        L.check(lib.jen1_gain_apply(x.data_ptr(), y.data_ptr(), gain.data_ptr(), None if lufs is None else lufs.data_ptr(),
+                                    None if stats is None else stats.data_ptr(), target.data_ptr(), rows, C, n, STRATEGIES.index(strategy),
+                                    LIMITS.index(limit), headroom, float(energy_floor), torch.cuda.current_stream(dev).cuda_stream),
+                "jen1_gain_apply")
+    y = y.reshape(tuple(wav.shape)).to(src)
+    return (y, gain.reshape(lead).to(src)) if return_gain else y

@@ -113,11 +113,19 @@ class LatentCollate:
     Runs in the process that owns the GPU.  Clips of one input rate are converted together (one ``convert_audio`` call per distinct rate;
     the channel rule of ``encodec.utils.convert_audio`` -- mono repeated, stereo averaged -- is applied on the host first, so that clips of
     one rate stack), every clip is trimmed or zero-padded to exactly ``sample_duration * sample_rate`` samples, and the batch is encoded by
-    one ``audio_encoder.encode_latents`` call."""
+    one ``audio_encoder.encode_latents`` call.  ``normalize`` / ``target_lufs`` (not in the reference): a strategy of
+    ``jen1_amd.audio.normalize_audio`` applied with ``limit="clip"`` to the padded, converted batch in front of the encoder, so that clips
+    reach it at one level and not at whatever level their files have; None feeds them as they are."""
 
-    def __init__(self, audio_encoder, device="cuda", sample_duration=10, convert_audio: Optional[Callable] = None):
+    def __init__(self, audio_encoder, device="cuda", sample_duration=10, convert_audio: Optional[Callable] = None,
+                 normalize: Optional[str] = None, target_lufs=-14.0):
         self.audio_encoder, self.device, self.sample_duration = audio_encoder, device, sample_duration
         self._convert = convert_audio
+        if normalize is not None:
+            from . import audio
+            if normalize not in audio.STRATEGIES:
+                raise ValueError(f"unknown normalize {normalize!r}: None or one of {audio.STRATEGIES}")
+        self.normalize, self.target_lufs = normalize, target_lufs
 
     def convert_audio(self, wav, sr, target_sr, target_channels):
         if self._convert is not None:
@@ -154,6 +162,9 @@ class LatentCollate:
             conv = self.convert_audio(group.to(self.device), sr, rate, channels)
             n = min(n_out, conv.shape[-1])
             out[idx, :, :n] = conv[:, :, :n].to(self.device, torch.float32)
+        if self.normalize is not None:             # the level of every clip, set in one call on the padded batch (not in the reference)
+            from . import audio
+            out = audio.normalize_audio(out, rate, strategy=self.normalize, target_lufs=self.target_lufs, limit="clip", device=self.device)
         emb = ae.encode_latents(out)[0]
         return emb, [meta for _chunk, _sr, meta in batch]
 
@@ -175,11 +186,12 @@ class LatentLoader:
 
 def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sample_duration, aug_shift, batch_size: int = 50, shuffle: bool = True,
                     split_ratio=0.8, device="cpu", durations_path=None, cumsum_path=None, audio_file_txt_path=None, *, audio_encoder=None,
-                    num_workers: int = 0, dataset_cls=None):
+                    num_workers: int = 0, dataset_cls=None, normalize: Optional[str] = None, target_lufs=-14.0):
     """(train loader, validation loader) of ``(emb, metadata)`` batches.  ``dataset_dir``: one folder (split by ``split_ratio``) or a
     (train, validation) pair.  ``audio_encoder`` (an ``EncodecHIP``) installs ``LatentCollate`` on ``device``; without it the loaders yield
     the raw item lists.  ``num_workers`` > 0 reads the files in spawned worker processes, which never touch the GPU.  ``dataset_cls``: a
-    ``MusicDataset`` subclass to build instead (one that selects or tags items; importable by name when workers are used)."""
+    ``MusicDataset`` subclass to build instead (one that selects or tags items; importable by name when workers are used).  ``normalize`` /
+    ``target_lufs`` are handed to ``LatentCollate``."""
     cls = MusicDataset if dataset_cls is None else dataset_cls
 
     def make(folder):
@@ -192,7 +204,7 @@ def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sampl
         train_dataset, val_dataset = random_split(dataset, [train_size, len(dataset) - train_size])
     else:
         train_dataset, val_dataset = make(dataset_dir[0]), make(dataset_dir[1])
-    fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration)
+    fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs)
     kw = dict(batch_size=batch_size, collate_fn=collate, drop_last=True, num_workers=num_workers)
     if num_workers > 0:
         kw["multiprocessing_context"] = "spawn"        # never fork a process that has initialised the GPU

@@ -2,7 +2,7 @@
 
 Host-side mirror of /root/reference/generation.py:16-192 -- same constructor arguments, ``get_model_and_diffusion``,
 ``generate(prompt, seed, steps, batch_size, seconds, use_gdm, task, init_audio, init_audio_sr, inpainting_scope)`` (plus the keyword
-additions ``sampler``, ``preserve_known`` and ``output_sr``), ``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
+additions ``sampler``, ``preserve_known``, ``output_sr`` and ``normalize`` / ``target_lufs`` / ``limit``),``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
 passed in instead (their weights are outside this build):
 
   * ``audio_encoder``: the object the reference gets from ``EncodecModel.encodec_model_48khz()``; used exactly as
@@ -189,8 +189,16 @@ class Jen1:
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
                  inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
                  decode: str = "whole", segment_scales: str = "unit", conditions=None,
-                 window_seconds: Optional[float] = None, window_overlap: float = 0.5, preserve_known: bool = False) -> torch.Tensor:
-        """``window_seconds`` / ``window_overlap`` (not in the reference): long-form generation.  With ``seconds > window_seconds`` the
+                 window_seconds: Optional[float] = None, window_overlap: float = 0.5, normalize: Optional[str] = None,
+                 target_lufs=-14.0, limit: str = "clip", preserve_known: bool = False) -> torch.Tensor:
+        """``normalize`` / ``target_lufs`` / ``limit`` (not in the reference): set the level of the decoder's output, which otherwise comes
+        back as the codec leaves it (Encodec 48 kHz decodes every segment at unit RMS: peaks far above full scale, hard-clipped by a
+        16-bit writer).  ``normalize``: a strategy of ``jen1_amd.audio.normalize_audio`` -- "loudness" (BS.1770-4 integrated loudness
+        brought to ``target_lufs``), "peak", "rms" or "clip" -- applied with ``limit`` ("none", "clip", "tanh") on the device the
+        decoder left its output on, at the model's rate, BEFORE the ``output_sr`` resample.  ``target_lufs="input"`` (music_inpaint /
+        music_cont with ``init_audio``): each row's target is the measured loudness of its own given audio after conversion.  None
+        keeps the call as it was, bit for bit.
+        ``window_seconds`` / ``window_overlap`` (not in the reference): long-form generation.  With ``seconds > window_seconds`` the
         piece is not handed to the denoiser as one sample of a length it was never trained on: its latents live on one canvas of L
         frames and are denoised as W overlapping windows of T frames -- T the frame count the encoder gives ``window_seconds``,
         hop = max(1, round(T * (1 - window_overlap))) -- which run as ordinary batch rows (``batch_size * W`` of them) and are merged
@@ -237,6 +245,18 @@ class Jen1:
             raise ValueError("segment_scales='known' needs known audio: task 'music_inpaint' or 'music_cont'")
         if decode == "segments" and not hasattr(self.audio_encoder, "decode_latents"):
             raise ValueError("decode='segments' needs an audio_encoder with decode_latents (jen1_amd.encodec.EncodecHIP)")
+        if normalize is not None:
+            from . import audio
+            if normalize not in audio.STRATEGIES:
+                raise ValueError(f"unknown normalize {normalize!r}: None or one of {audio.STRATEGIES}")
+            if limit not in audio.LIMITS:
+                raise ValueError(f"unknown limit {limit!r}: one of {audio.LIMITS}")
+            audio.hop_samples(self.sample_rate)
+            if isinstance(target_lufs, str):
+                if target_lufs != "input":
+                    raise ValueError(f"target_lufs must be a number, a tensor or 'input', not {target_lufs!r}")
+                if task == "text_guided" or init_audio is None:
+                    raise ValueError("target_lufs='input' needs known audio: task 'music_inpaint' or 'music_cont' with init_audio")
         windowed = self._check_windows(seconds, window_seconds, window_overlap)
         rows = None if windowed else self._metadata_rows(prompt, batch_size, conditions)
         torch.manual_seed(seed if seed != -1 else int(np.random.randint(0, 2 ** 32 - 1)))
@@ -249,6 +269,12 @@ class Jen1:
         out = self._sample(diffusion, model, prompt, wav, keep, causal, seed_with_audio=not placeholder, steps=steps,
                            preserve_known=preserve_known, sampler=sampler, decode=decode, segment_scales=segment_scales, length=total,
                            metadata=rows, windows=(float(window_seconds), float(window_overlap), conditions) if windowed else None)
+        if normalize is not None:
+            from . import audio
+            on = out.device if out.device.type == "cuda" else self.device
+            if isinstance(target_lufs, str):                   # "input": the level of each row's given audio, measured where the output is
+                target_lufs = audio.loudness(wav[:, :, :prefix].to(on), self.sample_rate, device=on)
+            out = audio.normalize_audio(out, self.sample_rate, strategy=normalize, target_lufs=target_lufs, limit=limit, device=on)
         if output_sr is not None and int(output_sr) != self.sample_rate:
             from . import audio
             # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
@@ -396,11 +422,17 @@ class Jen1:
 
 
 # generation.py:194-213
-def save_audio_tensor(audio_tensor: torch.Tensor, file_path: str, sample_rate: int = 48000) -> None:
+def save_audio_tensor(audio_tensor: torch.Tensor, file_path: str, sample_rate: int = 48000, normalize: Optional[str] = None,
+                      target_lufs=-14.0, limit: str = "clip") -> None:
     """saves audio ``[C, N]`` (or ``[1, C, N]``: the batch axis is dropped) as a 16-bit PCM ``.wav`` file (``jen1_amd.wav.save`` in the place
-    of ``torchaudio.save``)"""
+    of ``torchaudio.save``).  ``normalize`` / ``target_lufs`` / ``limit`` (not in the reference): ``jen1_amd.audio.normalize_audio`` at
+    ``sample_rate`` in front of the writer, on the tensor's GPU or the current one; None writes the samples as they are."""
     from . import wav
     audio_tensor = audio_tensor.detach()
     if audio_tensor.ndim == 3:
         audio_tensor = audio_tensor.squeeze(0)
+    if normalize is not None:
+        from . import audio
+        audio_tensor = audio.normalize_audio(audio_tensor.to(torch.float32), sample_rate, strategy=normalize, target_lufs=target_lufs, limit=limit,
+                                             device=audio_tensor.device if audio_tensor.device.type == "cuda" else "cuda")
     wav.save(file_path, audio_tensor.to("cpu", torch.float32), sample_rate)

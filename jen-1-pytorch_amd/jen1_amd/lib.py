@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -29,6 +29,8 @@ CFG_T128x64, CFG_T128x32, CFG_T128x16, CFG_T256x32, CFG_T256x16, CFG_T64x64 = 5,
 T5_ACT_GELU_NEW, T5_ACT_RELU, T5_MAX_TOKENS = 0, 1, 128      # include/jen1_t5.h
 FORM_SCALAR, FORM_VECTOR, FORM_FUSED256, FORM_FUSED1024 = 0, 1, 2, 3                 # include/jen1_train.h: the jen1_*_form queries
 LN_BWD_SCALAR256, LN_BWD_SCALAR512, LN_BWD_VECTOR256, LN_BWD_VECTOR512 = 0, 1, 2, 3
+GAIN_LOUDNESS, GAIN_PEAK, GAIN_RMS, GAIN_CLIP = 0, 1, 2, 3           # include/jen1_hip.h: jen1_gain_apply
+LIMIT_NONE, LIMIT_CLIP, LIMIT_TANH = 0, 1, 2
 
 c_void_p, c_int, c_float, c_int64 = C.c_void_p, C.c_int32, C.c_float, C.c_int64
 
@@ -268,6 +270,13 @@ SYMBOLS = {
     # csrc/audio.hip: sample-rate / channel conversion of waveforms
     "jen1_resample": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int, _P]),
     "jen1_resample_tile_frames": (c_int, [c_int, c_int]),
+    # csrc/loudness.hip: BS.1770 meter (K-weighted hop energies, gate) and the gain + limiter
+    "jen1_kweight_energy": (c_int, [_P, _P, _P, C.POINTER(C.c_double), c_int, c_int, c_int64, c_int, _P, c_int64, _P]),
+    "jen1_kweight_energy_workspace_bytes": (c_int64, [c_int, c_int, c_int64, c_int]),
+    "jen1_kweight_chunk": (c_int, [c_int]),
+    "jen1_kweight_tile_chunks": (c_int, [c_int]),
+    "jen1_loudness_gate": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, _P]),
+    "jen1_gain_apply": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, C.c_double, C.c_double, _P]),
     # csrc/windows.hip: overlapping sampler windows on one canvas
     "jen1_window_merge": (c_int, [_P, _P] + [c_int] * 6 + [_P, _P]),
     "jen1_window_gather": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
