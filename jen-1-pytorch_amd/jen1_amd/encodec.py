@@ -28,7 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 
 from . import lib as L
-from .train import ConvGeom, TrainRuntime, _conv_forward, _operand, pad8
+from .gemm_host import ConvGeom, GemmRuntime, conv_forward, operand, pad8
 
 HOP_48K = 320
 
@@ -57,9 +57,8 @@ class ResidualVectorQuantizerHIP:
         """ResidualVectorQuantization.encode (core_vq.py): per codebook the nearest entry of the running residual.
         emb float32 [B, 128, T] -> codes int64 [n_q, B, T].  The distance search -(|x|^2 - 2 x.E + |E|^2) is one float32
         GEMM per codebook (2 x.E with -|E|^2 as its bias; |x|^2 does not change the argmax)."""
-        from .train import TrainRuntime, _operand
         if self._rt is None:
-            self._rt = TrainRuntime("f32", self.device)
+            self._rt = GemmRuntime("f32", self.device)
             self._neg_sq = (-(self.tables ** 2).sum(-1)).contiguous()          # [n_q][bins]
         rt = self._rt
         src = emb.device
@@ -70,7 +69,7 @@ class ResidualVectorQuantizerHIP:
         scores = torch.empty((B * T, bins), dtype=torch.float32, device=self.device)
         out = []
         for q in range(nq):
-            rt.gemm(_operand(res.data_ptr(), D, 1), _operand(self.tables[q].data_ptr(), D, 1), scores.data_ptr(), B * T, bins, D,
+            rt.gemm(operand(res.data_ptr(), D, 1), operand(self.tables[q].data_ptr(), D, 1), scores.data_ptr(), B * T, bins, D,
                     dtype=L.F32, ldc_m=bins, bias=self._neg_sq[q], alpha=2.0)
             idx = scores.argmax(dim=-1)
             res = res - self.tables[q][idx]
@@ -130,7 +129,7 @@ class _SEANetOps:
     """the building blocks both halves of the SEANet share (encodec modules/conv.py, modules/lstm.py, modules/seanet.py)"""
 
     def __init__(self, params: Dict[str, torch.Tensor], lstm_name: str, compute_dtype: str, device):
-        self.rt = TrainRuntime(compute_dtype, device)
+        self.rt = GemmRuntime(compute_dtype, device)
         self.device = self.rt.device
         self.p = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in params.items()}
         assert "layers.0.norm.weight" in self.p, "only the 48 kHz model's norm='time_group_norm' is built (no weight_norm)"
@@ -202,7 +201,7 @@ class _SEANetOps:
             g = ConvGeom("conv", k, stride, 0, Lx + left + right, Lout, ci, co)
         else:
             g = ConvGeom("conv", k, stride, left, Lx, Lout, ci, co, reflect=True)
-        y = _conv_forward(self.rt, x, self.rt.packed(w, "conv", x.dtype), b, g)
+        y = conv_forward(self.rt, x, self.rt.packed(w, "conv", x.dtype), b, g)
         return self._norm(y, name, co)
 
     def _conv_transpose(self, x: torch.Tensor, name: str, stride: int) -> torch.Tensor:
@@ -212,7 +211,7 @@ class _SEANetOps:
         Lx = x.shape[1]
         full = (Lx - 1) * stride + k
         g = ConvGeom("convT", k, stride, 0, Lx, full, ci, co)
-        y = self._norm(_conv_forward(self.rt, x, self.rt.packed(w, "convT", x.dtype), b, g), name, co)
+        y = self._norm(conv_forward(self.rt, x, self.rt.packed(w, "convT", x.dtype), b, g), name, co)
         total = k - stride
         right = total // 2
         return y[:, total - right: full - right].contiguous()
@@ -241,7 +240,7 @@ class _SEANetOps:
         for l in range(self.n_lstm):
             wih = rt.packed(self.p[f"{self.lstm_name}.lstm.weight_ih_l{l}"], "linear", x.dtype)
             gin = torch.empty((B, T, 4 * H), dtype=torch.float32, device=x.device)
-            rt.gemm(_operand(h.data_ptr(), h.shape[-1], 1), _operand(wih.data_ptr(), wih.shape[-1], 1), gin.data_ptr(), B * T, 4 * H, H,
+            rt.gemm(operand(h.data_ptr(), h.shape[-1], 1), operand(wih.data_ptr(), wih.shape[-1], 1), gin.data_ptr(), B * T, 4 * H, H,
                     dtype=dt, ldc_m=4 * H, bias=self.lstm_bias[l], c_f32=True)
             y = torch.empty_like(x)
             last = l == self.n_lstm - 1

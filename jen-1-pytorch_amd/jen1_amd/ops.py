@@ -17,8 +17,8 @@ to ``torch.compile`` / ``torch.export`` / FakeTensor tracing and show up by name
 There is no CPU implementation behind any of them: without the HIP extension (or off a ROCm device) they raise ``Jen1HipError``.
 The training graph (jen1_amd/train.py) keeps its own ``autograd.Function``s for the parameterised operators: those accumulate
 weight gradients in place into the flat ``.grad`` buffer RCCL reduces and read compute copies of the weights that are refreshed once
-per optimiser step; the functional ops here run the same kernels through the same host code (train._conv_forward / _conv_dgrad /
-_conv_wgrad, AttentionCoreFn) but return the gradients as tensors and pack the weight per call.
+per optimiser step; the functional ops here run the same kernels through the same host code (gemm_host.conv_forward / conv_dgrad /
+conv_wgrad / bias_grad, train.AttentionCoreFn) but return the gradients as tensors and pack the weight per call (gemm_host.compute_copy).
 """
 from __future__ import annotations
 
@@ -28,7 +28,10 @@ from typing import Optional, Tuple
 import torch
 from torch.library import custom_op
 
+from . import gemm_host
 from . import lib as L
+from .gemm_host import ConvGeom, bias_grad, compute_copy, pad8
+from .train import AttentionCoreFn, TrainRuntime
 
 _models: "weakref.WeakValueDictionary[int, torch.nn.Module]" = weakref.WeakValueDictionary()
 _next_handle = [1]
@@ -276,7 +279,6 @@ _rts: dict = {}
 
 
 def _rt(t: torch.Tensor):
-    from .train import TrainRuntime
     _stream(t)
     key = (t.device.index, t.dtype)
     rt = _rts.get(key)
@@ -285,20 +287,7 @@ def _rt(t: torch.Tensor):
     return rt
 
 
-def _pad8(c: int) -> int:
-    return (c + 7) // 8 * 8
-
-
-def _compute_copy(rt, w: torch.Tensor, kind: str, dtype: torch.dtype) -> torch.Tensor:
-    d = rt._layout(w, kind)
-    k, r, c = d.shape
-    out = torch.zeros((k, r, _pad8(c)), dtype=dtype, device=w.device)
-    out[:, :, :c] = d
-    return out
-
-
 def _geom(kind: int, weight: torch.Tensor, x: torch.Tensor, stride: int, pad: int, L_out: int):
-    from .train import ConvGeom
     if kind == 2:
         co, ci = weight.shape
         rows = x.numel() // x.shape[-1]
@@ -316,33 +305,27 @@ def conv_forward(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     (kind 0 Conv1d [Co, Ci, k], 1 ConvTranspose1d [Ci, Co, k], 2 Linear [Co, Ci]); bias float32 [Co] or None.  kind 0: output position
     t reads input rows t * stride - pad + tap (rows outside [0, L_in) are zeros); kind 1: ``pad`` is ConvTranspose1d's padding;
     kind 2: L_out is ignored (rows in = rows out).  -> [B, L_out, pad8(Co)]"""
-    from .train import _conv_forward
     assert 0 <= kind <= 2 and x.dim() == 3
     rt = _rt(x)
     x = x.contiguous()
     g = _geom(kind, weight, x, stride, pad, L_out)
-    assert x.shape[-1] == _pad8(g.ci), f"jen1::conv_forward: {x.shape[-1]} input lanes for {g.ci} channels (pad to a multiple of 8)"
-    wp = _compute_copy(rt, weight, _KINDS[kind], x.dtype)
+    assert x.shape[-1] == pad8(g.ci), f"jen1::conv_forward: {x.shape[-1]} input lanes for {g.ci} channels (pad to a multiple of 8)"
+    wp = compute_copy(weight, _KINDS[kind], x.dtype)
     xin = x.view(1, -1, x.shape[-1]) if kind == 2 else x
-    y = _conv_forward(rt, xin, wp, None if bias is None else bias.detach().to(torch.float32).contiguous(), g)
+    y = gemm_host.conv_forward(rt, xin, wp, None if bias is None else bias.detach().to(torch.float32).contiguous(), g)
     return y.view(x.shape[0], x.shape[1], y.shape[-1]) if kind == 2 else y
-
-
-def _conv_out_len(kind, x, weight, L_out):
-    return x.shape[1] if kind == 2 else int(L_out)
 
 
 @conv_forward.register_fake
 def _(x, weight, bias, kind, stride, pad, L_out):
     co = weight.shape[1] if kind == 1 else weight.shape[0]
-    return x.new_empty((x.shape[0], _conv_out_len(kind, x, weight, L_out), _pad8(co)))
+    return x.new_empty((x.shape[0], x.shape[1] if kind == 2 else int(L_out), pad8(co)))
 
 
 @custom_op("jen1::conv_backward", mutates_args=())
 def conv_backward(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, kind: int, stride: int, pad: int, has_bias: bool,
                   need_dx: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(dx [x's shape; empty(0) unless need_dx], dweight float32 in the reference layout, dbias float32 [Co]; empty(0) unless has_bias)"""
-    from .train import _conv_dgrad, _conv_wgrad
     rt = _rt(x)
     x, dy = x.contiguous(), dy.contiguous()
     g = _geom(kind, weight, x, stride, pad, dy.shape[1])
@@ -350,14 +333,13 @@ def conv_backward(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, kind:
     dyin = dy.view(1, -1, dy.shape[-1]) if kind == 2 else dy
     dw = torch.zeros(weight.shape, dtype=torch.float32, device=x.device)
     db = torch.zeros((g.co,), dtype=torch.float32, device=x.device) if has_bias else x.new_empty((0,), dtype=torch.float32)
-    if not _conv_wgrad(rt, xin, dyin, dw, g, db if has_bias else None) and has_bias:
-        ldy = dy.shape[-1]
-        L.check(rt.lib.jen1_colsum(dy.data_ptr(), db.data_ptr(), dy.numel() // ldy, g.co, ldy, rt.dt_of(dy), rt.stream()), "jen1_colsum")
+    if not gemm_host.conv_wgrad(rt, xin, dyin, dw, g, db if has_bias else None) and has_bias:
+        bias_grad(rt, dy, db, g.co)
     if not need_dx:
         return x.new_empty((0,)), dw, db
-    wp = _compute_copy(rt, weight, _KINDS[kind], x.dtype)
-    wd = _compute_copy(rt, weight, _KINDS[kind] + "D", x.dtype)
-    return _conv_dgrad(rt, dyin, wp, g, wd).view(x.shape), dw, db
+    wp = compute_copy(weight, _KINDS[kind], x.dtype)
+    wd = compute_copy(weight, _KINDS[kind] + "D", x.dtype)
+    return gemm_host.conv_dgrad(rt, dyin, wp, g, wd).view(x.shape), dw, db
 
 
 @conv_backward.register_fake
@@ -413,7 +395,6 @@ class _Ctx:
 def attention(q: torch.Tensor, kv: torch.Tensor, heads: int, causal: bool, kv_mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """softmax(q k^T / sqrt(d) [+ causal mask]) v per head (blocks.py:300-330 AttentionBase; kv = to_kv's output K | V [B, Nk, 2 C],
     kv_mask [B, Nk] multiplied into the rows of K and V, blocks.py:431-434).  -> (out [B, Nq, C], probabilities [B heads, Nq, pad8(Nk)])"""
-    from .train import AttentionCoreFn
     rt = _rt(q)
     q, kv = q.contiguous(), kv.contiguous()
     small = bool(rt.small_attn and rt.lib.jen1_attn_small_fits(q.shape[1], kv.shape[1], q.shape[2] // heads, rt.dt_of(q)))
@@ -426,14 +407,13 @@ def attention(q: torch.Tensor, kv: torch.Tensor, heads: int, causal: bool, kv_ma
 
 @attention.register_fake
 def _(q, kv, heads, causal, kv_mask):
-    return torch.empty_like(q), q.new_empty((q.shape[0] * heads, q.shape[1], _pad8(kv.shape[1])))
+    return torch.empty_like(q), q.new_empty((q.shape[0] * heads, q.shape[1], pad8(kv.shape[1])))
 
 
 @custom_op("jen1::attention_backward", mutates_args=())
 def attention_backward(dout: torch.Tensor, q: torch.Tensor, kv: torch.Tensor, probs: torch.Tensor, heads: int,
                        kv_mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """(dq, dkv) from the saved probabilities"""
-    from .train import AttentionCoreFn
     rt = _rt(q)
     q, kv = q.contiguous(), kv.contiguous()
     ctx = _Ctx()

@@ -28,6 +28,8 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
+from .gemm_host import GemmRuntime, operand, want_skinny
+
 EPS = 1e-6                      # T5Config.layer_norm_epsilon
 MAX_DISTANCE = 128              # T5Config.relative_attention_max_distance
 BLOCK = "encoder.block.{}.layer.{}."
@@ -126,7 +128,6 @@ class T5EncoderHIP:
 
     def __init__(self, sd: Dict[str, torch.Tensor], compute_dtype: str = "f32", device="cuda", act: Optional[str] = None):
         from . import lib as L
-        from .train import TrainRuntime
         geo = infer_geometry({k: tuple(v.shape) for k, v in sd.items()})
         act = act or ("gelu_new" if geo.gated else "relu")
         if (geo.gated, act) not in ((True, "gelu_new"), (False, "relu")):
@@ -136,7 +137,7 @@ class T5EncoderHIP:
         if geo.d_model % 8 or geo.d_ff % 8:
             raise ValueError(f"d_model = {geo.d_model} and d_ff = {geo.d_ff} must be multiples of 8")
         self.L, self.geo, self.act = L, geo, act
-        self.rt = rt = TrainRuntime(compute_dtype, device)
+        self.rt = rt = GemmRuntime(compute_dtype, device)
         self.device, self.compute_dtype = rt.device, compute_dtype
         dev, td = rt.device, rt.tdtype
 
@@ -187,13 +188,12 @@ class T5EncoderHIP:
     # ------------------------------------------------------------------ the pass
     def _linear(self, x: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> None:
         """out[M][n] = x[M][K] w[n][K]^T; a float32 ``out`` in bf16 mode is the GEMM's float32 epilogue"""
-        from .train import _operand
         M, K = x.shape
         n = w.shape[0]
         assert w.shape[1] == K and out.shape == (M, n)
         rt = self.rt
-        rt.gemm(_operand(x.data_ptr(), K, 1), _operand(w.data_ptr(), K, 1, tap_stride=n * K), out.data_ptr(), M, n, K, dtype=rt.dt,
-                ldc_m=n, c_f32=out.dtype == torch.float32 and rt.tdtype != torch.float32, skinny=rt.want_skinny(M, n, (K + 31) // 32))
+        rt.gemm(operand(x.data_ptr(), K, 1), operand(w.data_ptr(), K, 1, tap_stride=n * K), out.data_ptr(), M, n, K, dtype=rt.dt,
+                ldc_m=n, c_f32=out.dtype == torch.float32 and rt.tdtype != torch.float32, skinny=want_skinny(rt, M, n, (K + 31) // 32))
         self.launches += 1
 
     def _norm(self, b: _Buffers, add: Optional[torch.Tensor], weight: torch.Tensor, y: torch.Tensor) -> None:

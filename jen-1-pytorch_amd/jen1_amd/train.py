@@ -18,8 +18,6 @@ There is no fallback: without libjen1_hip.so / a ROCm device every entry point r
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import math
 import os
 import weakref
@@ -31,78 +29,25 @@ from torch.autograd import Function, Variable
 from . import lib as L
 from .graphs import capture as capture_graph
 from .config import ResSpec, TransformerSpec, UNetSpec
+from .gemm_host import (ConvGeom, GemmRuntime, backward_plan, bias_grad, big_gemm, conv_dgrad, conv_forward, conv_wgrad, operand,
+                        out_rows, pad8)
 
 
-def pad8(c: int) -> int:
-    return (c + 7) // 8 * 8
-
-
-class Map:
-    """index map of ``jen1_gemm_operand`` (include/jen1_train.h)"""
-
-    def __init__(self, axis: int, L_idx: int, L_src: int, mul: int = 1, tapmul: int = 0, shift: int = 0, div: int = 1, reflect: bool = False,
-                 per_batch: bool = False):
-        self.axis, self.L, self.Lsrc, self.mul, self.tapmul, self.shift, self.div, self.reflect = axis, L_idx, L_src, mul, tapmul, shift, div, reflect
-        self.per_batch = per_batch        # the shift of batch element b comes from jen1_gemm_args.map_shift_b[b] (CausalRows)
-
-
-def _operand(ptr: int, ld_r: int, ld_k: int, tap_stride: int = 0, zs0: int = 0, zs1: int = 0, zdiv: int = 1,
-             m: Optional[Map] = None) -> L.GemmOperand:
-    o = L.GemmOperand()
-    o.p, o.zs0, o.zs1, o.ld_r, o.ld_k, o.tap_stride, o.zdiv = ptr, zs0, zs1, ld_r, ld_k, tap_stride, zdiv
-    if m is None:
-        o.map_axis, o.map_L, o.map_Lsrc, o.map_mul, o.map_tapmul, o.map_shift, o.map_div = 0, 1, 1, 1, 0, 0, 1
-    else:
-        o.map_axis, o.map_L, o.map_Lsrc, o.map_mul, o.map_tapmul, o.map_shift, o.map_div = m.axis, m.L, m.Lsrc, m.mul, m.tapmul, m.shift, m.div
-        o.map_reflect = int(m.reflect)
-        o.reserved = 1 if m.per_batch else 0
-    return o
-
-
-class TrainRuntime:
-    """Handle on the library + the per-optimiser-step cache of packed compute weights."""
+class TrainRuntime(GemmRuntime):
+    """The GEMM host layer's runtime + what only training needs: the weight-gradient queue, the K/V banks, the training switches."""
 
     def __init__(self, compute_dtype: str = "bf16", device="cuda"):
-        self.lib = L.load()                      # raises when the HIP extension is missing
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.Jen1HipError("the training path needs a ROCm GPU (device='cuda'); no CPU path exists in this package")
-        assert compute_dtype in ("f32", "bf16")
-        self.dt = L.F32 if compute_dtype == "f32" else L.BF16
-        self.tdtype = torch.float32 if compute_dtype == "f32" else torch.bfloat16
-        self._packed: Dict[tuple, list] = {}          # (id, kind, dtype) -> [weakref, buffer, epoch of last refresh, kind]
-        self.epoch = 0
-        self._fresh_epoch = -1
-        self._acc32: Optional[torch.Tensor] = None        # persistent float32 split-K accumulator, zero at rest
+        super().__init__(compute_dtype, device)
         # keep a second, transposed compute copy of every weight so that the data gradient is K-contiguous on both operands
         self.dgrad_copies = os.environ.get("JEN1_TRAIN_DGRAD_COPIES", "1") == "1"
-        self.wgrad_plain_rmw = os.environ.get("JEN1_TRAIN_WGRAD_RMW", "1") == "1"
         # plain many-row linears (the text-context K/V projections) on the large-M matrix-core kernels (BigLinearFn, csrc/big_gemm.hip)
         self.big_linears = os.environ.get("JEN1_TRAIN_BIG_LINEARS", "1") == "1"
         # the ends of a pass (q_sample / cat / layout change, context rows, time features, CFG combine + loss) as own launches
         # (csrc/train_glue.hip) instead of ATen elementwise / cat / reduce kernels
         self.fused_glue = os.environ.get("JEN1_TRAIN_FUSED_GLUE", "1") == "1"
-        self._consts: Dict[tuple, torch.Tensor] = {}
-        self.stats: Optional[dict] = None        # {"family": [launches, flops, algorithmic bytes]} while a counting pass runs (bench.py)
-        self.skinny_gemm = os.environ.get("JEN1_TRAIN_SKINNY", "1") == "1"
         self.dual_norms = os.environ.get("JEN1_TRAIN_DUAL_NORMS", "1") == "1"          # self-attention's two LayerNorms of x in one launch
-        self.fused_repack = os.environ.get("JEN1_TRAIN_FUSED_REPACK", "1") == "1"      # every compute copy in one launch (jen1_repack)
-        self.repack_twins = os.environ.get("JEN1_TRAIN_REPACK_TWINS", "1") == "1"      # ... a weight's two copies from one read of it
-        self._repack_tab, self._repack_meta, self._repack_n = None, (0, 0), -1
-        self.skinny_max_steps = int(os.environ.get("JEN1_TRAIN_SKINNY_STEPS", "64"))      # K steps per wave
-        self.target_wgs = int(os.environ.get("JEN1_TRAIN_TARGET_WGS", "256"))
-        self.min_steps = int(os.environ.get("JEN1_TRAIN_MIN_STEPS", "4"))      # K steps (of 32) a split keeps at least
-        # weight gradients over many rows (>= big_wgrad_rows) on jen1_big_gemm_tn_conv: 23 us at 24 000 x 128 x (3 x 128) with the bias
-        # gradient against 40 on train_gemm's weight-gradient form; the pass 13.58 -> 13.31 ms.  (First version: 45 us -- a tile of one tap adds
-        # floats `taps` apart in lines it shares with the other taps' workgroups, and every reduction slice's bias atomics land on the same
-        # four lines; the kernel now holds a chunk of every tap per tile and interleaves them through LDS, bias sums have workgroups of
-        # their own.)  big_wgrad_unpair: also take the mid-size layers out of the paired launches (measured: nothing, 13.34)
-        self.big_wgrads = os.environ.get("JEN1_TRAIN_BIG_WGRADS", "1") == "1"
+        # also take the mid-size layers out of the paired launches (measured: nothing, 13.34 ms against 13.31)
         self.big_wgrad_unpair = os.environ.get("JEN1_TRAIN_BIG_WGRAD_UNPAIR", "0") == "1"
-        # forward / data gradient of convolutions over many rows on jen1_big_gemm_conv
-        self.big_convs = os.environ.get("JEN1_TRAIN_BIG_CONVS", "1") == "1"
-        self.big_conv_rows = int(os.environ.get("JEN1_TRAIN_BIG_CONV_ROWS", "4096"))
-        self.big_wgrad_rows = int(os.environ.get("JEN1_TRAIN_BIG_WGRAD_ROWS", "4096"))
         # weight gradients on their own stream (weight_grad below)
         # layers per fork; 0 (default): on the pass's own stream.  The fork was worth 1 ms while every weight gradient went through it; since
         # a layer's two gradients share a launch only the FiLM / many-row / library-GEMM ones are left, and the branch costs the replayed
@@ -125,7 +70,6 @@ class TrainRuntime:
         self.fork_skips = os.environ.get("JEN1_TRAIN_FORK_SKIPS", "1") == "1"
         # the unconditional half of the CFG pair reads ONE shared set of context rows (the fixed embedding) instead of B copies
         self.share_fixed_context = os.environ.get("JEN1_TRAIN_SHARE_FIXED", "1") == "1"
-        self._banks: Dict[tuple, list] = {}      # (ids of the weights, dtype) -> [weakrefs, weight matrix, weakrefs of the biases, bias vector, epoch]
         # the text-context K / V projections of all cross-attention layers as ONE product per pass (KvBank, ContextKVFn; csrc/train_kvbank.hip)
         self.kv_grouped = os.environ.get("JEN1_TRAIN_KV_GROUPED", "1") == "1"
         self._kv_banks: Dict[tuple, "KvBank"] = {}
@@ -137,21 +81,6 @@ class TrainRuntime:
         if t is None:
             t = self._consts[("kv_rows", B)] = torch.cat([torch.arange(B, dtype=torch.int32), torch.full((B,), B, dtype=torch.int32)]).to(self.device)
         return t
-
-    def const(self, n: int, v: float) -> torch.Tensor:
-        """a cached float32 vector of n copies of v (read-only operands of the glue kernels)"""
-        t = self._consts.get((n, v))
-        if t is None:
-            t = self._consts[(n, v)] = torch.full((n,), float(v), dtype=torch.float32, device=self.device)
-        return t
-
-    # ------------------------------------------------------------------ plumbing
-    def stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def invalidate(self) -> None:
-        """the parameters changed (optimiser step / load): every packed compute copy is stale"""
-        self.epoch += 1
 
     def weight_grad(self, launch, *keep: torch.Tensor) -> None:
         """Nothing in the backward pass reads a weight gradient, but every launch costs the chain ~4.5 us + its run time, and one third
@@ -212,79 +141,6 @@ class TrainRuntime:
         self._wheld.clear()
         self._wforked = False
 
-    def dt_of(self, t: torch.Tensor) -> int:
-        if t.dtype == torch.float32:
-            return L.F32
-        if t.dtype == torch.bfloat16:
-            return L.BF16
-        raise L.Jen1HipError(f"unsupported activation dtype {t.dtype}")
-
-    @staticmethod
-    def _layout(w: torch.Tensor, kind: str) -> torch.Tensor:
-        d = w.detach()
-        if kind == "linear":
-            return d.unsqueeze(0)                          # [1][Co][Ci]
-        if kind == "conv":
-            return d.permute(2, 0, 1)                      # [k][Co][Ci]
-        if kind == "convT":
-            return d.permute(2, 1, 0)                      # ConvTranspose1d [Ci][Co][k] -> [k][Co][Ci]
-        # the data-gradient copies: rows = input channels, K = output channels contiguous (register-direct GEMM path)
-        if kind == "linearD":
-            return d.t().unsqueeze(0)                      # [1][Ci][Co]
-        if kind == "convD":
-            return d.permute(2, 1, 0)                      # [Co][Ci][k] -> [k][Ci][Co]
-        assert kind == "convTD"
-        return d.permute(2, 0, 1)                          # [Ci][Co][k] -> [k][Ci][Co]
-
-    def packed(self, w: torch.Tensor, kind: str, dtype: torch.dtype) -> torch.Tensor:
-        """compute copy [k][C_out][pad8(C_in)] of a Conv1d [Co, Ci, k] / ConvTranspose1d [Ci, Co, k] / Linear [Co, Ci]
-        weight.  The buffer is allocated once and refreshed IN PLACE when the parameters moved, so a captured graph
-        keeps reading the same address (GraphedLossStep refreshes outside the graph, once per optimiser step)."""
-        key = (id(w), kind, dtype)
-        hit = self._packed.get(key)
-        if hit is not None and hit[0]() is not w:          # id() of a dead parameter can be reused
-            hit = None
-        if hit is None:
-            with torch.no_grad():
-                d = self._layout(w, kind)
-                k, co, ci = d.shape
-                if kind == "linear" and dtype == d.dtype and ci % 8 == 0:
-                    hit = [weakref.ref(w), d, -1, kind]    # float32 mode: the parameter itself is the compute copy
-                else:
-                    hit = [weakref.ref(w), torch.zeros((k, co, pad8(ci)), dtype=dtype, device=w.device), -2, kind]
-            self._packed[key] = hit
-        if hit[2] != self.epoch and hit[2] != -1:
-            self._refresh(hit, w)
-        return hit[1]
-
-    def packed_bank(self, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Compute copies of several Linear weights of one input width as ONE matrix [1][sum C_out][pad8(C_in)] (+ their biases as one
-        float32 vector): each weight's copy is a row slice of it, registered like any other packed copy (refreshed by the same
-        jen1_repack launch).  The C_out must be multiples of 8 (slices start on 16-byte boundaries in either dtype)."""
-        key = (tuple(id(w) for w in weights), dtype)
-        hit = self._banks.get(key)
-        if hit is not None and any(r() is not w for r, w in zip(hit[0], weights)):
-            hit = None
-        if hit is None:
-            ci = weights[0].shape[1]
-            assert all(w.shape[1] == ci and w.shape[0] % 8 == 0 and w.dtype == torch.float32 for w in weights)
-            assert all(b.shape[0] == w.shape[0] for w, b in zip(weights, biases))
-            total = sum(w.shape[0] for w in weights)
-            dev = weights[0].device
-            mat = torch.zeros((1, total, pad8(ci)), dtype=dtype, device=dev)
-            off = 0
-            for w in weights:
-                self._packed[(id(w), "linear", dtype)] = [weakref.ref(w), mat[:, off:off + w.shape[0], :], -2, "linear"]
-                off += w.shape[0]
-            self._repack_tab = None                # (entries may have been replaced: rebuild the table of jen1_repack)
-            hit = [[weakref.ref(w) for w in weights], mat, [weakref.ref(b) for b in biases],
-                   torch.zeros(total, dtype=torch.float32, device=dev), -2]
-            self._banks[key] = hit
-        for w in weights:
-            self.packed(w, "linear", dtype)        # (refreshes a stale slice; after refresh_all none is)
-        self._refresh_bank_bias(hit)
-        return hit[1], hit[3]
-
     def kv_bank(self, weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor], betas: Sequence[torch.Tensor]) -> "KvBank":
         """the folded operands of the stacked text-context projection (KvBank), cached on the identity of the parameters and kept up to
         date like the other compute copies (one jen1_kv_fold launch per optimiser step)"""
@@ -297,70 +153,13 @@ class TrainRuntime:
         hit.refresh()
         return hit
 
-    def _refresh_bank_bias(self, hit) -> None:
-        if hit[4] != self.epoch:
-            bs = [r() for r in hit[2]]
-            if all(b is not None for b in bs):
-                with torch.no_grad():
-                    torch.cat([b.detach() for b in bs], out=hit[3])
-            hit[4] = self.epoch
-
-    def _refresh(self, hit, w) -> None:
-        with torch.no_grad():
-            d = self._layout(w, hit[3])
-            hit[1][:, :, :d.shape[2]].copy_(d)
-        hit[2] = self.epoch
-
     def refresh_all(self) -> None:
-        """bring every packed copy up to date now (outside any graph capture)"""
-        if self._fresh_epoch == self.epoch:
-            return
-        for bank in self._banks.values():
-            self._refresh_bank_bias(bank)
-        # (banks whose parameters were freed or replaced are dropped: their weak references are dead)
-        self._kv_banks = {k: kvb for k, kvb in self._kv_banks.items() if kvb.alive()}
-        for kvb in self._kv_banks.values():
-            kvb.refresh()
-        live = [(hit, hit[0]()) for hit in self._packed.values() if hit[2] != -1]
-        live = [(hit, w) for hit, w in live if w is not None]
-        if self.fused_repack and live:
-            # ONE launch for every copy (jen1_repack): the table of (source view, destination) is rebuilt when a copy was added
-            if self._repack_tab is None or self._repack_n != len(self._packed):
-                self._repack_tab = []              # one table per destination dtype (the time MLPs keep float32 copies in bf16 mode)
-                for dt_t, dt_c in ((torch.float32, L.F32), (torch.bfloat16, L.BF16)):
-                    ents, t0 = [], 0
-                    # a weight's forward copy [k][Co][Ci] and its data-gradient transpose [k][Ci][Co] come from ONE read (dst2)
-                    twins = {(id(w), hit[3][:-1]): hit for hit, w in live if hit[1].dtype == dt_t and hit[3].endswith("D")} if self.repack_twins else {}
-                    fwd = {(id(w), hit[3]) for hit, w in live if hit[1].dtype == dt_t and not hit[3].endswith("D")}
-                    for hit, w in live:
-                        if hit[1].dtype != dt_t or (hit[3].endswith("D") and twins and (id(w), hit[3][:-1]) in fwd):
-                            continue                   # (a transpose whose forward copy is in this table rides on that entry)
-                        d = self._layout(w, hit[3])
-                        assert w.dtype == torch.float32
-                        e = L.RepackEntry()
-                        e.src, e.dst = d.data_ptr(), hit[1].data_ptr()
-                        e.d0, e.d1, e.d2, e.ld = d.shape[0], d.shape[1], d.shape[2], hit[1].shape[2]
-                        e.s0, e.s1, e.s2 = d.stride(0), d.stride(1), d.stride(2)
-                        twin = twins.get((id(w), hit[3]))
-                        if twin is not None and twin[0]() is w:
-                            assert twin[1].shape[0] == d.shape[0] and twin[1].shape[1] == d.shape[2] and twin[1].shape[2] >= d.shape[1]
-                            e.dst2, e.ld2 = twin[1].data_ptr(), twin[1].shape[2]
-                        e.tile0 = t0
-                        t0 += d.shape[0] * ((d.shape[1] + 31) // 32) * ((d.shape[2] + 31) // 32)
-                        ents.append(e)
-                    if ents:
-                        arr = (L.RepackEntry * len(ents))(*ents)
-                        self._repack_tab.append((torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), len(ents), t0, dt_c))
-                self._repack_n = len(self._packed)
-            for tab, n, tiles, dt_c in self._repack_tab:
-                L.check(self.lib.jen1_repack(tab.data_ptr(), n, tiles, dt_c, self.stream()), "jen1_repack")
-            for hit, _ in live:
-                hit[2] = self.epoch
-        else:
-            for hit, w in live:
-                if hit[2] != self.epoch:
-                    self._refresh(hit, w)
-        self._fresh_epoch = self.epoch
+        """the K/V banks too (the three refreshes touch disjoint buffers: their order is free)"""
+        if self._fresh_epoch != self.epoch:          # (banks whose parameters were freed or replaced are dropped)
+            self._kv_banks = {k: kvb for k, kvb in self._kv_banks.items() if kvb.alive()}
+            for kvb in self._kv_banks.values():
+                kvb.refresh()
+        super().refresh_all()
 
     @staticmethod
     def grad_of(p: torch.Tensor) -> torch.Tensor:
@@ -370,297 +169,10 @@ class TrainRuntime:
         assert p.grad.dtype == torch.float32 and p.grad.is_contiguous()
         return p.grad
 
-    # ------------------------------------------------------------------ the GEMM
-    def gemm(self, a: L.GemmOperand, b: L.GemmOperand, c_ptr: int, M: int, N: int, K: int, *, dtype: int, taps: int = 1,
-             batches: int = 1, taps_in_z: bool = False, ldc_m: int, ldc_n: int = 1, c_tap_stride: int = 0, c_zs0: int = 0,
-             c_zs1: int = 0, c_zdiv: int = 1, bias: Optional[torch.Tensor] = None, splitk: int = 1, atomic: bool = False,
-             accumulate: bool = False, c_f32: bool = False, alpha: float = 1.0, rowsum: Optional[torch.Tensor] = None,
-             residual: Optional[torch.Tensor] = None, skinny: bool = False, defer: bool = False, pair_with=None,
-             shift_b: Optional[torch.Tensor] = None):
-        """``defer``: no launch, the filled argument block comes back; ``pair_with`` (such a block): both products in ONE launch
-        (jen1_train_gemm_pair: the deferred one first)"""
-        g = L.GemmArgs()
-        g.a, g.b, g.c, g.bias = a, b, c_ptr, (None if bias is None else bias.data_ptr())
-        g.c_zs0, g.c_zs1, g.ldc_m, g.ldc_n, g.c_tap_stride, g.c_zdiv = c_zs0, c_zs1, ldc_m, ldc_n, c_tap_stride, c_zdiv
-        g.M, g.N, g.K, g.taps, g.batches = M, N, K, taps, batches
-        g.taps_in_z, g.splitk, g.atomic, g.accumulate, g.c_f32, g.dtype = int(taps_in_z), splitk, int(atomic), int(accumulate), int(c_f32), dtype
-        g.alpha = alpha
-        g.rowsum = None if rowsum is None else rowsum.data_ptr()
-        g.residual = None if residual is None else residual.data_ptr()
-        g.reserved = 1 if skinny else 0
-        g.map_shift_b = None if shift_b is None else shift_b.data_ptr()
-        if self.stats is not None:
-            # executed work of the launch (bench.py's training roofline counts the pass's OWN launch list): 2 M N K per tap and batch;
-            # algorithmic bytes = the two operands once + the result (float32 read-modify-write when it accumulates)
-            es = 4 if dtype == L.F32 else 2
-            fl = 2.0 * M * N * K * taps * batches
-            by = (M * K * taps + N * K * taps) * batches * es + M * N * batches * (taps if taps_in_z else 1) * ((8 if (atomic or accumulate) else 4) if c_f32 else es)
-            e = self.stats.setdefault("train_gemm", [0, 0.0, 0.0])
-            e[0] += 0 if pair_with is not None else 1
-            e[1] += fl
-            e[2] += by
-        if defer:
-            return g
-        if pair_with is not None:
-            L.check(self.lib.jen1_train_gemm_pair(pair_with, g, self.stream()), "jen1_train_gemm_pair")
-        else:
-            L.check(self.lib.jen1_train_gemm(g, self.stream()), "jen1_train_gemm")
-        return None
-
-    def split_accumulator(self, n: int) -> torch.Tensor:
-        """the persistent zeroed float32 scratch every split-K forward / data-gradient GEMM of the stream accumulates
-        into; ``hand_over`` converts it into the output and zeroes it again in the same launch"""
-        if self._acc32 is None or self._acc32.numel() < n:
-            assert not torch.cuda.is_current_stream_capturing(), "the split-K accumulator must be sized before graph capture"
-            self._acc32 = torch.zeros(max(n, 1 << 23), dtype=torch.float32, device=self.device)
-        return self._acc32
-
-    def hand_over(self, acc: torch.Tensor, out: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        n = out.numel()
-        if residual is not None:
-            L.check(self.lib.jen1_convert_clear_add(acc.data_ptr(), out.data_ptr(), residual.data_ptr(), n, self.dt_of(out), self.stream()),
-                    "jen1_convert_clear_add")
-            return out
-        L.check(self.lib.jen1_convert_clear(acc.data_ptr(), out.data_ptr(), n, self.dt_of(out), self.stream()), "jen1_convert_clear")
-        return out
-
-    def want_skinny(self, M: int, N: int, ksteps: int) -> bool:
-        """few rows against a big weight: 32 x 16 tiles with the K split inside the workgroup (train_gemm_skinny_kernel) instead of a
-        split-K launch + conversion; as long as that gives the chip enough workgroups of a reasonable length"""
-        if not self.skinny_gemm:
-            return False
-        tiles = ((M + 63) // 64) * ((N + 63) // 64)
-        wgs = ((M + 31) // 32) * ((N + 15) // 16)
-        return tiles < self.target_wgs // 2 and wgs <= 4096 and ksteps <= 4 * self.skinny_max_steps
-
-    def count(self, family: str, flops: float, nbytes: float) -> None:
-        """one launch of ``family`` in the counting pass of bench.py"""
-        if self.stats is not None:
-            e = self.stats.setdefault(family, [0, 0.0, 0.0])
-            e[0] += 1; e[1] += flops; e[2] += nbytes
-
-    def pick_splitk(self, M: int, N: int, ksteps: int, z: int = 1) -> int:
-        tiles = ((M + 63) // 64) * ((N + 63) // 64) * z
-        if tiles >= self.target_wgs // 2:
-            return 1
-        # (a few rows against a very long K -- the data gradient of the stacked FiLM projections, 16 x 512 x 55 296: the output is tiny, the
-        # atomics cost nothing, and 256 workgroups of 54 serial steps took 82 us)
-        wgs = self.target_wgs * (4 if (M <= 64 and ksteps >= 1024) else 1)
-        s = min(max(1, wgs // tiles), max(1, ksteps // self.min_steps))
-        return max(1, min(s, 65535 // max(1, z)))
-
 
 # =====================================================================================================================
 # convolution family: _Conv1d (blocks.py:34-53), nn.Conv1d / nn.ConvTranspose1d of Upsample1d (blocks.py:69-95), nn.Linear
 # =====================================================================================================================
-class ConvGeom:
-    """static description of one convolution call"""
-
-    def __init__(self, kind: str, taps: int, stride: int, pad: int, L_in: int, L_out: int, ci: int, co: int, reflect: bool = False,
-                 pad_b: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-        self.kind, self.taps, self.stride, self.pad, self.L_in, self.L_out, self.ci, self.co = kind, taps, stride, pad, L_in, L_out, ci, co
-        self.reflect = reflect        # forward only: F.pad(mode="reflect") instead of zeros (SEANet convolutions)
-        # (-pad, +pad) per batch element as int32 tensors: a pass that mixes causal and non-causal clips ("conv" kind only)
-        self.pad_b = pad_b
-        assert pad_b is None or kind == "conv"
-
-    def fwd_map(self, axis: int) -> Optional[Map]:
-        """activation index (b, t_out) [+ tap] -> input row"""
-        if self.kind == "linear":
-            return None
-        if self.kind == "conv":
-            return Map(axis, self.L_out, self.L_in, mul=self.stride, tapmul=1, shift=-self.pad, reflect=self.reflect,
-                       per_batch=self.pad_b is not None)
-        return Map(axis, self.L_out, self.L_in, mul=1, tapmul=-1, shift=self.pad, div=self.stride)
-
-    def bwd_map(self, axis: int) -> Optional[Map]:
-        """activation index (b, t_in) [+ tap] -> output row"""
-        if self.kind == "linear":
-            return None
-        if self.kind == "conv":
-            return Map(axis, self.L_in, self.L_out, mul=1, tapmul=-1, shift=self.pad, div=self.stride, per_batch=self.pad_b is not None)
-        return Map(axis, self.L_in, self.L_out, mul=self.stride, tapmul=1, shift=-self.pad)
-
-    @property
-    def fwd_shift_b(self) -> Optional[torch.Tensor]:
-        return None if self.pad_b is None else self.pad_b[0]
-
-    @property
-    def bwd_shift_b(self) -> Optional[torch.Tensor]:
-        return None if self.pad_b is None else self.pad_b[1]
-
-
-def _conv_forward(rt: TrainRuntime, x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom,
-                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x: [..rows.., ldx] channel-last with ldx == wp.shape[2]; returns [B, L_out, pad8(co)] (+ ``residual`` of that shape, added in
-    the epilogue of the GEMM or of the split-K hand-over)"""
-    dt = rt.dt_of(x)
-    ldx = x.shape[-1]
-    k, co, cip = wp.shape
-    assert ldx == cip and x.is_contiguous() and k == g.taps and co == g.co, (x.shape, wp.shape, g.__dict__)
-    rows_in = x.numel() // ldx
-    B = rows_in // g.L_in
-    M = B * g.L_out
-    ldy = pad8(co)
-    a = _operand(x.data_ptr(), ldx, 1, m=g.fwd_map(1))
-    b = _operand(wp.data_ptr(), cip, 1, tap_stride=co * cip)
-    ksteps = k * ((cip + 31) // 32)
-    if residual is not None:
-        assert residual.is_contiguous() and residual.numel() == B * g.L_out * ldy and residual.dtype == x.dtype, (residual.shape, B, g.L_out, ldy)
-    if (rt.big_convs and dt == L.BF16 and g.kind in ("conv", "linear") and M >= rt.big_conv_rows and not g.reflect
-            and cip % 8 == 0 and co % 4 == 0):
-        # many rows (the long levels): the 128 x 128 matrix-core kernel with the taps in its row map (jen1_big_gemm_conv: 10 us at
-        # 24 000 x 128 x (3 x 128) against 25 on the register-direct form)
-        y = (torch.zeros if ldy != co else torch.empty)((B, g.L_out, ldy), dtype=x.dtype, device=x.device)
-        conv = g.kind == "conv"
-        L.check(rt.lib.jen1_big_gemm_conv(x.data_ptr(), wp.data_ptr(), None if bias is None else bias.data_ptr(),
-                                          None if residual is None else residual.data_ptr(), y.data_ptr(), B if conv else M, g.L_in if conv else 1,
-                                          g.L_out if conv else 1, cip, co, k, g.stride if conv else 1, (0 if g.pad_b is not None else g.pad) if conv else 0,
-                                          0, ldx, cip, co * cip, ldy, None if g.pad_b is None else g.fwd_shift_b.data_ptr(), 1, rt.stream()), "jen1_big_gemm_conv")
-        rt.count("big_gemm", 2.0 * M * co * cip * k, 2.0 * (rows_in * ldx + k * co * cip + M * ldy))
-        return y
-    if (rt.big_convs and dt == L.BF16 and g.kind == "convT" and M >= rt.big_conv_rows and g.ci % 64 == 0 and cip == g.ci and co % 4 == 0):
-        # ConvTranspose1d: output position t reads input (t + padding - tap) / stride where that is whole -- the conv form with the taps
-        # reversed and the division in its row map (the other taps' rows arrive as zeros: no traffic, wasted MFMA steps only)
-        y = (torch.zeros if ldy != co else torch.empty)((B, g.L_out, ldy), dtype=x.dtype, device=x.device)
-        L.check(rt.lib.jen1_big_gemm_conv(x.data_ptr(), wp.data_ptr(), None if bias is None else bias.data_ptr(),
-                                          None if residual is None else residual.data_ptr(), y.data_ptr(), B, g.L_in, g.L_out, g.ci, co, k, 1,
-                                          k - 1 - g.pad, 1, ldx, cip, co * cip, ldy, None, g.stride, rt.stream()), "jen1_big_gemm_conv")
-        rt.count("big_gemm", 2.0 * M * co * cip * k / g.stride, 2.0 * (rows_in * ldx + k * co * cip + M * ldy))
-        return y
-    skinny = rt.want_skinny(M, co, ksteps)
-    sk = 1 if skinny else rt.pick_splitk(M, co, ksteps)
-    alloc = torch.zeros if (ldy != co or sk > 1) else torch.empty
-    if sk > 1:
-        acc = rt.split_accumulator(B * g.L_out * ldy)
-        rt.gemm(a, b, acc.data_ptr(), M, co, cip, dtype=dt, taps=k, ldc_m=ldy, bias=bias, splitk=sk, atomic=True, c_f32=True, shift_b=g.fwd_shift_b)
-        return rt.hand_over(acc, torch.empty((B, g.L_out, ldy), dtype=x.dtype, device=x.device), residual)
-    if residual is not None and ldy != co:
-        y = residual.clone()                   # (padding columns: keep the residual's)
-        rt.gemm(a, b, y.data_ptr(), M, co, cip, dtype=dt, taps=k, ldc_m=ldy, bias=bias, accumulate=True, skinny=skinny, shift_b=g.fwd_shift_b)
-        return y
-    y = alloc((B, g.L_out, ldy), dtype=x.dtype, device=x.device)
-    rt.gemm(a, b, y.data_ptr(), M, co, cip, dtype=dt, taps=k, ldc_m=ldy, bias=bias, residual=residual, skinny=skinny, shift_b=g.fwd_shift_b)
-    return y
-
-
-def _conv_dgrad(rt: TrainRuntime, dy: torch.Tensor, wp: torch.Tensor, g: ConvGeom, wd: Optional[torch.Tensor] = None, pair_with=None,
-                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``wd``: the data-gradient copy [k][Ci][pad8(Co)] of the weight (both GEMM operands K-contiguous: the register-direct
-    path of jen1_train_gemm); without it the forward copy ``wp`` is read transposed through LDS.  ``pair_with``: the deferred
-    weight-gradient product of the same layer, launched together with this one.  ``residual`` (dx's shape): added in the epilogue
-    (the gradient that reached the layer's input along a branch around it: ConvFn's ``fork``)"""
-    dt = rt.dt_of(dy)
-    ldy = dy.shape[-1]
-    k, co, cip = wp.shape
-    assert dy.is_contiguous() and ldy == pad8(co)
-    B = dy.numel() // ldy // g.L_out
-    M = B * g.L_in
-    a = _operand(dy.data_ptr(), ldy, 1, m=g.bwd_map(1))
-    if wd is not None:
-        assert wd.shape[0] == k and wd.shape[2] == ldy
-        ci_rows = wd.shape[1]
-        b = _operand(wd.data_ptr(), ldy, 1, tap_stride=ci_rows * ldy)
-        co = ldy                                               # K runs over the padded (zero) output channels too
-        cip_n = ci_rows
-    else:
-        b = _operand(wp.data_ptr(), 1, cip, tap_stride=co * cip)
-        cip_n = cip
-    if (rt.big_convs and wd is not None and pair_with is None and dt == L.BF16 and M >= rt.big_conv_rows and ldy % 64 == 0
-            and g.kind in ("linear", "conv") and cip_n % 4 == 0):
-        # the data gradient over many rows: the same kernel on dy, taps reversed, pad' = taps - 1 - pad (a strided convolution: the
-        # stride as the divisor of the row map)
-        dx = (torch.zeros if cip_n != cip else torch.empty)((B, g.L_in, cip), dtype=dy.dtype, device=dy.device)
-        conv = g.kind == "conv"
-        L.check(rt.lib.jen1_big_gemm_conv(dy.data_ptr(), wd.data_ptr(), None, None if residual is None else residual.data_ptr(), dx.data_ptr(),
-                                          B if conv else M, g.L_out if conv else 1, g.L_in if conv else 1, ldy, cip_n, k, 1,
-                                          ((k - 1) if g.pad_b is not None else (k - 1 - g.pad)) if conv else 0, 1, ldy, ldy, cip_n * ldy, cip,
-                                          None if g.pad_b is None else g.bwd_shift_b.data_ptr(), g.stride if conv else 1, rt.stream()), "jen1_big_gemm_conv")
-        rt.count("big_gemm", 2.0 * M * cip_n * ldy * k, 2.0 * (B * g.L_out * ldy + k * cip_n * ldy + M * cip))
-        return dx
-    if (rt.big_convs and wd is not None and pair_with is None and dt == L.BF16 and M >= rt.big_conv_rows // 4 and g.kind == "convT" and ldy % 64 == 0
-            and cip_n % 4 == 0):
-        # ConvTranspose1d's data gradient IS a strided convolution of dY (row t_in stride + tap - padding) with the [k][Ci][Co] copy
-        dx = (torch.zeros if cip_n != cip else torch.empty)((B, g.L_in, cip), dtype=dy.dtype, device=dy.device)
-        L.check(rt.lib.jen1_big_gemm_conv(dy.data_ptr(), wd.data_ptr(), None, None if residual is None else residual.data_ptr(), dx.data_ptr(),
-                                          B, g.L_out, g.L_in, ldy, cip_n, k, g.stride, g.pad, 0, ldy, ldy, cip_n * ldy, cip, None, 1, rt.stream()),
-                "jen1_big_gemm_conv")
-        rt.count("big_gemm", 2.0 * M * cip_n * ldy * k, 2.0 * (B * g.L_out * ldy + k * cip_n * ldy + M * cip))
-        return dx
-    ksteps = k * ((co + 31) // 32)
-    skinny = wd is not None and rt.want_skinny(M, cip_n, ksteps)
-    sk = 1 if skinny else rt.pick_splitk(M, cip, ksteps)
-    if sk > 1:
-        acc = rt.split_accumulator(B * g.L_in * cip)
-        rt.gemm(a, b, acc.data_ptr(), M, cip_n, co, dtype=dt, taps=k, ldc_m=cip, splitk=sk, atomic=True, c_f32=True, pair_with=pair_with, shift_b=g.bwd_shift_b)
-        return rt.hand_over(acc, torch.empty((B, g.L_in, cip), dtype=dy.dtype, device=dy.device), residual)
-    if residual is not None and cip_n != cip:
-        dx = residual.clone()                  # (padding columns: keep the residual's)
-        rt.gemm(a, b, dx.data_ptr(), M, cip_n, co, dtype=dt, taps=k, ldc_m=cip, skinny=skinny, pair_with=pair_with, accumulate=True, shift_b=g.bwd_shift_b)
-        return dx
-    dx = (torch.zeros if cip_n != cip else torch.empty)((B, g.L_in, cip), dtype=dy.dtype, device=dy.device)
-    rt.gemm(a, b, dx.data_ptr(), M, cip_n, co, dtype=dt, taps=k, ldc_m=cip, skinny=skinny, pair_with=pair_with, residual=residual, shift_b=g.bwd_shift_b)
-    return dx
-
-
-def _conv_wgrad(rt: TrainRuntime, x: torch.Tensor, dy: torch.Tensor, gw: torch.Tensor, g: ConvGeom, gb: Optional[torch.Tensor] = None,
-                defer: bool = False):
-    """gw (float32, reference layout) += the weight gradient.  ``gb`` (bias gradient) is accumulated by the same launch
-    when dy is the row operand (Conv1d / Linear); returns whether it was -- with ``defer`` (whether, the argument block of the
-    launch that has NOT been issued)."""
-    dt = rt.dt_of(x)
-    ldx, ldy = x.shape[-1], dy.shape[-1]
-    rows_dy = dy.numel() // ldy
-    if not dy.is_contiguous():                 # a column slice of a wider matrix (FilmBankFn): rows dy.stride(0) apart
-        assert dy.dim() == 2 and dy.stride(1) == 1 and g.kind == "linear"
-        ldy = dy.stride(0)
-    k = g.taps
-    if g.kind == "convT":
-        # W[ci][co][k]: rows m = ci from x (K = (b, t_in)), rows n = co from dy at the mapped row
-        K = x.numel() // ldx
-        a = _operand(x.data_ptr(), 1, ldx)
-        b = _operand(dy.data_ptr(), 1, ldy, m=g.bwd_map(2))
-        M, N = g.ci, g.co
-    else:
-        # W[co][ci][k]: rows m = co from dy (K = (b, t_out)), rows n = ci from x at the mapped row
-        K = rows_dy
-        a = _operand(dy.data_ptr(), 1, ldy)
-        b = _operand(x.data_ptr(), 1, ldx, m=g.fwd_map(2))
-        M, N = g.co, g.ci
-    if (rt.big_wgrads and not defer and g.kind in ("conv", "linear") and dt == L.BF16 and K >= rt.big_wgrad_rows
-            and not g.reflect and x.is_contiguous() and dy.is_contiguous() and g.co % 8 == 0 and K % g.L_out == 0
-            and (g.co % 128 == 0 or ldy >= -(-g.co // 128) * 128)
-            and (x.numel() // ldx) * g.L_out == K * g.L_in and gw.is_contiguous()):
-        # many reduction rows against a small output (the long levels): the transposing matrix-core kernel with the tap shift in its
-        # row map and the bias gradient as one more MFMA (switch: TrainRuntime.big_wgrads, off by default)
-        L.check(rt.lib.jen1_big_gemm_tn_conv(dy.data_ptr(), x.data_ptr(), gw.data_ptr(), None if gb is None else gb.data_ptr(), K // g.L_out,
-                                             g.L_out, g.L_in, g.co, g.ci, k, g.stride if g.kind == "conv" else 1,
-                                             (0 if g.pad_b is not None else g.pad) if g.kind == "conv" else 0, ldy, ldx, 1.0,
-                                             None if g.pad_b is None else g.fwd_shift_b.data_ptr(), rt.stream()), "jen1_big_gemm_tn_conv")
-        if rt.stats is not None:
-            e = rt.stats.setdefault("big_gemm", [0, 0.0, 0.0])
-            e[0] += 1; e[1] += 2.0 * K * g.co * g.ci * k; e[2] += 2.0 * K * (g.co + g.ci) + 8.0 * g.co * g.ci * k
-        return gb is not None
-    if (rt.big_wgrads and not defer and g.kind == "convT" and dt == L.BF16 and K >= rt.big_wgrad_rows // 4 and x.is_contiguous() and dy.is_contiguous()
-            and g.co % 8 == 0 and g.ci % 8 == 0 and k <= 16 and K % g.L_in == 0 and rows_dy * g.L_in == K * g.L_out and gw.is_contiguous()
-            and (g.ci % 128 == 0 or ldx >= -(-g.ci // 128) * 128)):
-        # ConvTranspose1d W[ci][co][k]: dW[ci][co][tap] = sum x[b, t][ci] dy[b, t stride + tap - padding][co]: the same kernel with the input
-        # as its row operand and dY as the shifted one (82 us on train_gemm's weight-gradient form at 6 000 x 128 x (8 x 128))
-        L.check(rt.lib.jen1_big_gemm_tn_conv(x.data_ptr(), dy.data_ptr(), gw.data_ptr(), None, K // g.L_in, g.L_in, g.L_out, g.ci, g.co, k, g.stride,
-                                             g.pad, ldx, ldy, 1.0, None, rt.stream()), "jen1_big_gemm_tn_conv")
-        rt.count("big_gemm", 2.0 * K * g.co * g.ci * k, 2.0 * (K * g.ci + rows_dy * g.co) + 8.0 * g.co * g.ci * k)
-        return (False, None) if defer else False
-    sk = rt.pick_splitk(M, N, (K + 31) // 32, z=k)
-    fused_bias = gb is not None and g.kind != "convT"
-    # one K slice: every (tap, tile) of the gradient belongs to exactly one workgroup of this launch and launches are
-    # stream-ordered, so a plain read-modify-write accumulates; float atomics only when the K range is split
-    na = sk == 1 and rt.wgrad_plain_rmw
-    blk = rt.gemm(a, b, gw.data_ptr(), M, N, K, dtype=dt, taps=k, taps_in_z=True, ldc_m=N * k, ldc_n=k, c_tap_stride=1,
-                  splitk=sk, atomic=not na, accumulate=na, c_f32=True, rowsum=gb if fused_bias else None, defer=defer,
-                  shift_b=g.fwd_shift_b if g.kind == "conv" else None)
-    return (fused_bias, blk) if defer else fused_bias
-
-
 class ConvFn(Function):
     """y = conv(x, weight) + bias; backward writes the parameter gradients into ``.grad`` itself"""
 
@@ -673,7 +185,7 @@ class ConvFn(Function):
         ctx.wd = rt.packed(weight, g.kind + "D", x.dtype) if (ctx.needs_input_grad[0] and rt.dgrad_copies) else None
         ctx.has_res = residual is not None
         ctx.save_for_backward(x)
-        y = _conv_forward(rt, x, wp, None if bias is None else bias.detach(), g, None if residual is None else residual.detach().contiguous())
+        y = conv_forward(rt, x, wp, None if bias is None else bias.detach(), g, None if residual is None else residual.detach().contiguous())
         ctx.set_materialize_grads(False)
         return (y, x.view_as(x)) if fork else y
 
@@ -689,29 +201,19 @@ class ConvFn(Function):
         gb = None if ctx.bias is None else rt.grad_of(ctx.bias)
         gw = rt.grad_of(ctx.weight)
         has_bias = ctx.bias is not None
-
-        def colsum():
-            ldy = dy.shape[-1]
-            L.check(rt.lib.jen1_colsum(dy.data_ptr(), gb.data_ptr(), dy.numel() // ldy, g.co, ldy, rt.dt_of(dy), rt.stream()), "jen1_colsum")
-
-        # (many-row layers: both products fill the chip, a pair would last their sum; the data gradient runs as the lean register-direct
-        # kernel instead and the weight gradient goes to the queue)
-        rows = (x.numel() // x.shape[-1])
-        many_rows = ((rows + 63) // 64) * ((g.ci + 63) // 64) >= rt.target_wgs or (
-            rt.big_wgrads and rt.big_wgrad_unpair and rows >= rt.big_wgrad_rows and g.kind in ("conv", "linear") and rt.dt_of(x) == L.BF16)
-        if ctx.needs_input_grad[0] and rt.pair_grads and not many_rows:
+        if backward_plan(rt, g.kind, x.numel() // x.shape[-1], g.ci, rt.dt_of(x), ctx.needs_input_grad[0]) == ("pair",):
             # both gradients of the layer in one launch: they share dY and nothing orders them
-            fused, blk = _conv_wgrad(rt, x, dy, gw, g, gb, defer=True)
-            dx = _conv_dgrad(rt, dy, ctx.wp, g, ctx.wd, pair_with=blk, residual=dskip).view(x.shape)
+            fused, blk = conv_wgrad(rt, x, dy, gw, g, gb, defer=True)
+            dx = conv_dgrad(rt, dy, ctx.wp, g, ctx.wd, pair_with=blk, residual=dskip).view(x.shape)
             if not fused and has_bias:
-                rt.weight_grad(colsum, dy)
+                rt.weight_grad(lambda: bias_grad(rt, dy, gb, g.co), dy)
             return dx, None, None, None, None, (dy if ctx.has_res else None), None
 
         def wgrad():
-            if not _conv_wgrad(rt, x, dy, gw, g, gb) and has_bias:
-                colsum()
+            if not conv_wgrad(rt, x, dy, gw, g, gb) and has_bias:
+                bias_grad(rt, dy, gb, g.co)
         rt.weight_grad(wgrad, x, dy)
-        dx = _conv_dgrad(rt, dy, ctx.wp, g, ctx.wd, residual=dskip).view(x.shape) if ctx.needs_input_grad[0] else None
+        dx = conv_dgrad(rt, dy, ctx.wp, g, ctx.wd, residual=dskip).view(x.shape) if ctx.needs_input_grad[0] else None
         return dx, None, None, None, None, (dy if ctx.has_res else None), None       # (the residual's gradient IS dy: no launch)
 
 
@@ -769,21 +271,6 @@ def conv_transpose1d(rt: TrainRuntime, x: torch.Tensor, weight, bias, stride: in
     return ConvFn.apply(x, weight, bias, rt, ConvGeom("convT", k, stride, padding, Lin, Lout, ci, co))
 
 
-def _big_gemm(rt: "TrainRuntime", a2d: torch.Tensor, b2d: torch.Tensor, out: torch.Tensor, K: int, bias: Optional[torch.Tensor] = None) -> None:
-    """out[M][N] = a2d[M][:K] @ b2d[N][:K]^T (+ bias[N], float32) on jen1_big_gemm (one column group)"""
-    g = L.BGemmArgs()
-    g.a, g.b, g.c, g.ldc = a2d.data_ptr(), b2d.data_ptr(), out.data_ptr(), out.stride(0)      # (one inline group: nothing to copy while capturing)
-    g.bias = None if bias is None else bias.data_ptr()
-    g.M, g.Ntot, g.K, g.lda, g.ldb, g.n_groups = a2d.shape[0], b2d.shape[0], K, a2d.stride(0), b2d.stride(0), 1
-    g.dtype, g.alpha = rt.dt_of(a2d), 1.0
-    if rt.stats is not None:
-        e = rt.stats.setdefault("big_gemm", [0, 0.0, 0.0])
-        e[0] += 1
-        e[1] += 2.0 * a2d.shape[0] * b2d.shape[0] * K
-        e[2] += (a2d.shape[0] * K + b2d.shape[0] * K + a2d.shape[0] * b2d.shape[0]) * a2d.element_size()
-    L.check(rt.lib.jen1_big_gemm(C.byref(g), rt.stream()), "jen1_big_gemm")
-
-
 class BigLinearFn(Function):
     """A PLAIN bias-free linear with many rows and a big weight -- the to_kv projections of the text context (blocks.py:402-407,
     :428: 2B x 129 rows, 1024 -> 512 / 1024 / 2048) -- on the large-M matrix-core kernels of csrc/big_gemm.hip: forward and data
@@ -797,7 +284,7 @@ class BigLinearFn(Function):
         ctx.rt, ctx.weight = rt, weight
         ctx.save_for_backward(x2d)
         y = torch.empty((x2d.shape[0], wp.shape[0]), dtype=x2d.dtype, device=x2d.device)
-        _big_gemm(rt, x2d, wp, y, wp.shape[1])
+        big_gemm(rt, x2d, wp, y, wp.shape[1])
         return y
 
     @staticmethod
@@ -808,12 +295,7 @@ class BigLinearFn(Function):
         co, ci = weight.shape
         gw = rt.grad_of(weight)
         rows = x2d.shape[0]
-
-        if rt.stats is not None:
-            e = rt.stats.setdefault("big_gemm", [0, 0.0, 0.0])
-            e[0] += 1
-            e[1] += 2.0 * rows * co * ci
-            e[2] += (rows * co + rows * ci) * 2 + co * ci * 8
+        rt.count("big_gemm", 2.0 * rows * co * ci, (rows * co + rows * ci) * 2 + co * ci * 8)      # (counted when the node runs, even if the launch is queued)
 
         def wgrad():
             L.check(rt.lib.jen1_big_gemm_tn(dy.data_ptr(), x2d.data_ptr(), gw.data_ptr(), rows, co, ci, dy.stride(0), x2d.stride(0), gw.stride(0), 1.0,
@@ -822,10 +304,8 @@ class BigLinearFn(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             wt = rt.packed(weight, "linearD", x2d.dtype)[0]         # [ci][pad8(co)]: the data gradient is K-contiguous too
-            dx = torch.empty_like(x2d)
-            if x2d.shape[1] != ci:
-                dx.zero_()
-            _big_gemm(rt, dy, wt, dx, co)
+            dx = out_rows(x2d, x2d.shape, x2d.shape[1] != ci)
+            big_gemm(rt, dy, wt, dx, co)
         return dx, None, None
 
 
@@ -915,7 +395,7 @@ class ContextKVFn(Function):
         L.check(rt.lib.jen1_ln_forward(x2d.data_ptr(), bank.ones.data_ptr(), bank.zeros.data_ptr(), xhat.data_ptr(), stats.data_ptr(), R, K, K, 1e-5,
                                        L.BF16, rt.stream()), "jen1_ln_forward")
         kv_all = torch.empty((R, bank.Ntot), dtype=torch.bfloat16, device=rows.device)
-        _big_gemm(rt, xhat, bank.wf, kv_all, K, bias=bank.bias)
+        big_gemm(rt, xhat, bank.wf, kv_all, K, bias=bank.bias)
         ctx.rt, ctx.bank, ctx.slots, ctx.n_share, ctx.dims = rt, bank, slots, n_share, (Bk, Nk, K)
         ctx.save_for_backward(x2d, xhat, stats)
         kv3 = kv_all.view(Bk, Nk, bank.Ntot)
@@ -944,18 +424,14 @@ class ContextKVFn(Function):
             L.check(rt.lib.jen1_sum_rows_strided(dall.data_ptr() + (Bk - 1) * Nk * Ntot * 2, ctx.n_share, Nk, Ntot, Ntot, L.BF16, s), "jen1_sum_rows_strided")
         dwf, dbias = bank.dwf[: Ntot * K], bank.dwf[Ntot * K:]
         L.check(rt.lib.jen1_memset_zero(dbias.data_ptr(), Ntot * 4, s), "jen1_memset_zero")           # (the column sums accumulate; dWf is stored)
-        L.check(rt.lib.jen1_colsum(dall.data_ptr(), dbias.data_ptr(), R, Ntot, Ntot, L.BF16, s), "jen1_colsum")
+        bias_grad(rt, dall[:R], dbias, Ntot)
         L.check(rt.lib.jen1_big_gemm_tn_store(dall.data_ptr(), xhat.data_ptr(), dwf.data_ptr(), R, Ntot, K, Ntot, K, K, 1.0, s), "jen1_big_gemm_tn_store")
         L.check(rt.lib.jen1_kv_fold_backward(bank.table().data_ptr(), len(bank.widths), Ntot, K, dwf.data_ptr(), dbias.data_ptr(), s), "jen1_kv_fold_backward")
-        if rt.stats is not None:
-            e = rt.stats.setdefault("big_gemm", [0, 0.0, 0.0])
-            e[0] += 1
-            e[1] += 2.0 * R * Ntot * K
-            e[2] += (R * Ntot + R * K) * 2 + Ntot * K * 8
+        rt.count("big_gemm", 2.0 * R * Ntot * K, (R * Ntot + R * K) * 2 + Ntot * K * 8)
         dx = None
         if ctx.needs_input_grad[0]:
             dxh = torch.empty_like(xhat)
-            _big_gemm(rt, dall[:R], bank.wft, dxh, Ntot)
+            big_gemm(rt, dall[:R], bank.wft, dxh, Ntot)
             dx = torch.empty_like(x2d)
             L.check(rt.lib.jen1_ln_backward(dxh.data_ptr(), x2d.data_ptr(), stats.data_ptr(), bank.ones.data_ptr(), dx.data_ptr(), bank.scratch[0].data_ptr(),
                                             bank.scratch[1].data_ptr(), R, K, K, L.BF16, s), "jen1_ln_backward")
@@ -1116,7 +592,7 @@ class FilmBankFn(Function):
         wall, ball = rt.packed_bank(weights, biases, smap.dtype)
         total = wall.shape[1]
         g = ConvGeom("linear", 1, 1, 0, B, B, weights[0].shape[1], total)
-        y = _conv_forward(rt, smap.view(1, B, F), wall, ball, g).view(B, total)
+        y = conv_forward(rt, smap.view(1, B, F), wall, ball, g).view(B, total)
         ctx.rt, ctx.g, ctx.wall, ctx.slots = rt, g, wall, slots
         outs, off = [], 0
         for w in weights:
@@ -1133,7 +609,7 @@ class FilmBankFn(Function):
                 slot.view.copy_(gr)            # (a gradient that did not come from GroupNormFn's in-place write)
                 slot.written()
         B = dY.shape[0]
-        dx = _conv_dgrad(rt, dY.view(1, B, dY.shape[1]), ctx.wall, ctx.g).view(B, -1) if ctx.needs_input_grad[0] else None
+        dx = conv_dgrad(rt, dY.view(1, B, dY.shape[1]), ctx.wall, ctx.g).view(B, -1) if ctx.needs_input_grad[0] else None
         return dx, None, None, None, None
 
 
@@ -1151,7 +627,7 @@ def film_bank(rt: TrainRuntime, smap: torch.Tensor, weights, biases):
 
         def written(w=w, b=b, view=view, lg=lg):
             gw, gb = rt.grad_of(w), rt.grad_of(b)
-            rt.weight_grad(lambda: _conv_wgrad(rt, xs, view, gw, lg, gb), xs, dY)
+            rt.weight_grad(lambda: conv_wgrad(rt, xs, view, gw, lg, gb), xs, dY)
         slots.append(FilmSlot(view, written))
         off += co
     outs = FilmBankFn.apply(smap, rt, tuple(weights), tuple(biases), tuple(slots))
@@ -1364,11 +840,11 @@ class AttentionCoreFn(Function):
             ctx.save_for_backward(q, kv, P)
             return O
         S = torch.empty((Z, Nq, ldS), dtype=torch.float32, device=q.device)
-        rt.gemm(_operand(qp, ldq, 1, zs0=Nq * ldq, zs1=d, zdiv=heads), _operand(kp, ldk, 1, zs0=Nk * ldk, zs1=d, zdiv=heads),
+        rt.gemm(operand(qp, ldq, 1, zs0=Nq * ldq, zs1=d, zdiv=heads), operand(kp, ldk, 1, zs0=Nk * ldk, zs1=d, zdiv=heads),
                 S.data_ptr(), Nq, Nk, d, dtype=dt, batches=Z, ldc_m=ldS, c_zs0=Nq * ldS, c_f32=True, alpha=scale)
         L.check(rt.lib.jen1_softmax_forward(S.data_ptr(), P.data_ptr(), Z * Nq, Nq, Nk, ldS, ldS, 1 if causal else 0, dt, rt.stream()),
                 "jen1_softmax_forward")
-        rt.gemm(_operand(P.data_ptr(), ldS, 1, zs0=Nq * ldS), _operand(vp, 1, ldv, zs0=Nk * ldv, zs1=d, zdiv=heads),
+        rt.gemm(operand(P.data_ptr(), ldS, 1, zs0=Nq * ldS), operand(vp, 1, ldv, zs0=Nk * ldv, zs1=d, zdiv=heads),
                 O.data_ptr(), Nq, d, Nk, dtype=dt, batches=Z, ldc_m=C, c_zs0=Nq * C, c_zs1=d, c_zdiv=heads)
         ctx.rt, ctx.heads, ctx.scale = rt, heads, scale
         ctx.save_for_backward(q, kv, P)
@@ -1422,18 +898,18 @@ class AttentionCoreFn(Function):
             return dQ, dKV, None, None, None, None, None, None
         dP = torch.empty((Z, Nq, ldS), dtype=torch.float32, device=q.device)
         dS = torch.empty((Z, Nq, ldS), dtype=q.dtype, device=q.device)
-        o_do = lambda ld_r, ld_k: _operand(dO.data_ptr(), ld_r, ld_k, zs0=Nq * C, zs1=d, zdiv=heads)
+        o_do = lambda ld_r, ld_k: operand(dO.data_ptr(), ld_r, ld_k, zs0=Nq * C, zs1=d, zdiv=heads)
         # dP = dO V^T
-        rt.gemm(o_do(C, 1), _operand(vp, ldv, 1, zs0=Nk * ldv, zs1=d, zdiv=heads), dP.data_ptr(), Nq, Nk, d, dtype=dt, batches=Z,
+        rt.gemm(o_do(C, 1), operand(vp, ldv, 1, zs0=Nk * ldv, zs1=d, zdiv=heads), dP.data_ptr(), Nq, Nk, d, dtype=dt, batches=Z,
                 ldc_m=ldS, c_zs0=Nq * ldS, c_f32=True)
         L.check(rt.lib.jen1_softmax_backward(P.data_ptr(), dP.data_ptr(), dS.data_ptr(), Z * Nq, Nk, ldS, ldS, dt, rt.stream()),
                 "jen1_softmax_backward")
         # dQ = scale dS K ; dK = scale dS^T Q ; dV = P^T dO
-        rt.gemm(_operand(dS.data_ptr(), ldS, 1, zs0=Nq * ldS), _operand(kp, 1, ldk, zs0=Nk * ldk, zs1=d, zdiv=heads),
+        rt.gemm(operand(dS.data_ptr(), ldS, 1, zs0=Nq * ldS), operand(kp, 1, ldk, zs0=Nk * ldk, zs1=d, zdiv=heads),
                 dQ.data_ptr(), Nq, d, Nk, dtype=dt, batches=Z, ldc_m=C, c_zs0=Nq * C, c_zs1=d, c_zdiv=heads, alpha=scale)
-        rt.gemm(_operand(dS.data_ptr(), 1, ldS, zs0=Nq * ldS), _operand(qp, 1, ldq, zs0=Nq * ldq, zs1=d, zdiv=heads),
+        rt.gemm(operand(dS.data_ptr(), 1, ldS, zs0=Nq * ldS), operand(qp, 1, ldq, zs0=Nq * ldq, zs1=d, zdiv=heads),
                 dKV.data_ptr(), Nk, d, Nq, dtype=dt, batches=Z, ldc_m=2 * C, c_zs0=Nk * 2 * C, c_zs1=d, c_zdiv=heads, alpha=scale)
-        rt.gemm(_operand(P.data_ptr(), 1, ldS, zs0=Nq * ldS), o_do(1, C),
+        rt.gemm(operand(P.data_ptr(), 1, ldS, zs0=Nq * ldS), o_do(1, C),
                 dKV.data_ptr() + C * esz, Nk, d, Nq, dtype=dt, batches=Z, ldc_m=2 * C, c_zs0=Nk * 2 * C, c_zs1=d, c_zdiv=heads)
         return dQ, dKV, None, None, None, None, None, None
 

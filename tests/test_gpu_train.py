@@ -121,6 +121,71 @@ def test_conv_family_forward_backward(rts, mode, case):
         assert rel_err(wd.grad.cpu().numpy(), 2 * ref["dw"]) < tol
 
 
+MANY_ROW_CASES = [
+    # (kind, B, Ci, Co, L, k, stride, causal), launches of the big kernels, launches of jen1_train_gemm: the counts of a dry run of the host
+    # code (tools/train_record.py) with the row thresholds at 64 and unpaired gradients
+    (("conv", 2, 128, 128, 96, 3, 1, False), 3, 0),
+    (("conv", 2, 128, 128, 96, 3, 1, True), 3, 0),
+    (("conv", 3, 128, 128, 96, 3, 1, [1, 0, 1]), 3, 0),      # CausalRows: the padding per batch element in shift_b
+    (("conv", 2, 128, 256, 97, 5, 2, True), 3, 0),           # strided: the data gradient divides in its row map
+    (("conv", 2, 128, 128, 96, 1, 1, False), 3, 0),
+    (("conv", 2, 257, 128, 96, 3, 1, False), 2, 1),          # Ci no multiple of 4: the data gradient stays on jen1_train_gemm
+    (("convT", 2, 128, 128, 48, 4, 2, False), 3, 0),
+    (("convT", 2, 128, 64, 48, 8, 4, False), 3, 0),
+    (("linear", 1, 128, 128, 128, 1, 1, False), 3, 0),
+]
+
+
+@pytest.mark.parametrize("case,n_big,n_gemm", MANY_ROW_CASES, ids=lambda c: "-".join(str(v) for v in c) if isinstance(c, tuple) else None)
+def test_conv_family_many_row_routes(case, n_big, n_gemm):
+    """the host's argument mapping for the many-row routes (jen1_big_gemm_conv forward and data gradient -- pad' = k - 1 - pad, the tap
+    reversal, the divisor, the shifted operand of ConvTranspose1d -- and jen1_big_gemm_tn_conv) through the autograd wrappers, bf16, with
+    the row thresholds lowered so that small shapes take them; against torch float32 as test_conv_family_forward_backward does it"""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from jen1_amd import train as TR
+    rt = TR.TrainRuntime("bf16")
+    rt.big_conv_rows = rt.big_wgrad_rows = 64
+    rt.pair_grads = False
+    rt.stats = {}
+    kind, B, Ci, Co, Lx, k, stride, causal = case
+    gen = torch.Generator().manual_seed(sum(v for v in case if isinstance(v, int) and not isinstance(v, bool)))
+    x = torch.randn((B, Ci, Lx), generator=gen).requires_grad_()
+    w = _param((Ci, Co, k) if kind == "convT" else (Co, Ci, k), gen, (Ci * k) ** -0.5)
+    b = _param((Co,), gen, 0.1)
+    if kind == "convT":
+        y_ref = F.conv_transpose1d(x, w, b, stride=stride, padding=stride // 2 + stride % 2, output_padding=stride % 2)
+    else:
+        # blocks.py:45-50 (pad then conv), per batch element where the causal flag is
+        flags = causal if isinstance(causal, list) else [causal] * B
+        pads = [((k - 1), 0) if f else ((k - 1) // 2, (k - 1) - (k - 1) // 2) for f in flags]
+        y_ref = torch.cat([F.conv1d(F.pad(x[i:i + 1], p), w, b, stride=stride) for i, p in enumerate(pads)])
+    dy = torch.randn(y_ref.shape, generator=gen)
+    y_ref.backward(dy)
+    ref = dict(y=y_ref.detach().numpy(), dx=x.grad.numpy(), dw=w.grad.numpy(), db=b.grad.numpy())
+
+    if kind == "linear":                       # (the reference's k = 1 convolution IS the linear: weight [Co, Ci])
+        w, ref["dw"] = w.detach()[:, :, 0], ref["dw"][:, :, 0]
+    wd = torch.nn.Parameter(w.detach().contiguous().cuda())
+    bd = torch.nn.Parameter(b.detach().cuda())
+    xr = _rows(x.detach(), rt.tdtype).requires_grad_()
+    if kind == "convT":
+        y = TR.conv_transpose1d(rt, xr, wd, bd, stride, stride // 2 + stride % 2, stride % 2)
+    elif kind == "linear":
+        y = TR.linear(rt, xr, wd, bd)
+    else:
+        y = TR.conv1d_same(rt, xr, wd, bd, stride, TR.CausalRows(torch.tensor(causal, device="cuda")) if isinstance(causal, list) else causal)
+    assert y.shape[1] == y_ref.shape[2]
+    y.backward(_rows(dy, rt.tdtype))
+    torch.cuda.synchronize()
+    assert rel_err(_back(y.detach(), Co), ref["y"]) < BF16_TOL
+    assert rel_err(_back(xr.grad, Ci), ref["dx"]) < BF16_TOL
+    assert float(xr.grad[:, :, Ci:].abs().max()) == 0.0 if xr.shape[-1] > Ci else True
+    assert rel_err(wd.grad.cpu().numpy(), ref["dw"]) < BF16_TOL
+    assert rel_err(bd.grad.cpu().numpy(), ref["db"]) < BF16_TOL
+    assert rt.stats["big_gemm"][0] == n_big and rt.stats.get("train_gemm", [0])[0] == n_gemm, rt.stats
+
+
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
 @pytest.mark.parametrize("rows,ci,co,bias", [(2, 129, 512, True), (48, 512, 1024, True), (258, 1024, 256, False), (5, 64, 64, True)])
 def test_linear_forward_backward(rts, mode, rows, ci, co, bias):
@@ -1260,7 +1325,7 @@ def test_weight_gradients_on_the_second_stream_equal_in_order_launches(use_graph
 def test_gemm_pair_equals_two_launches(rts, mode, skinny_second):
     """jen1_train_gemm_pair: two independent products in one launch give, bit for bit, what the two jen1_train_gemm launches give
     (64 x 64 form first; 64 x 64 or skinny form second; ragged M / N / K)"""
-    from jen1_amd.train import _operand
+    from jen1_amd.gemm_host import operand as _operand
     rt = rts[mode]
     dt = torch.float32 if mode == "f32" else torch.bfloat16
     gen = torch.Generator(device="cuda").manual_seed(5)

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "jen-1-pytorch_amd"))
 import torch  # noqa: E402
 from jen1_amd.graphs import capture as capture_graph  # noqa: E402
 
-from jen1_amd import train as T  # noqa: E402
+from jen1_amd import gemm_host as G, train as T  # noqa: E402
 
 rt = T.TrainRuntime("bf16", "cuda")
 N = 64
@@ -41,11 +41,11 @@ for rows, Lx, ci, co, k in [(16, 1, 1024, 1024, 1), (16, 1, 1024, 1024, 3), (32,
     B = rows // Lx
     kind = "linear" if k == 1 else "conv"
     x = torch.randn(B, Lx, ci, device="cuda").to(torch.bfloat16)
-    g = T.ConvGeom(kind, k, 1, (k - 1) // 2, Lx, Lx, ci, co) if k > 1 else T.ConvGeom("linear", 1, 1, 0, rows, rows, ci, co)
+    g = G.ConvGeom(kind, k, 1, (k - 1) // 2, Lx, Lx, ci, co) if k > 1 else G.ConvGeom("linear", 1, 1, 0, rows, rows, ci, co)
     if k == 1:
         x = x.view(1, rows, ci)
     wps = [torch.randn(k, co, ci, device="cuda").to(torch.bfloat16) for _ in range(N)]
     bias = torch.zeros(co, device="cuda")
-    warm = timed(lambda: [T._conv_forward(rt, x, wps[0], bias, g) for _ in range(N)])
-    cold = timed(lambda: [T._conv_forward(rt, x, wps[i], bias, g) for i in range(N)])
+    warm = timed(lambda: [G.conv_forward(rt, x, wps[0], bias, g) for _ in range(N)])
+    cold = timed(lambda: [G.conv_forward(rt, x, wps[i], bias, g) for i in range(N)])
     print(f"{rows:6d} {ci:5d} {co:5d} {k}  {warm:7.1f}  {cold:7.1f}")

@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "jen-1-pytorch_amd"))
 import torch  # noqa: E402
 from jen1_amd.graphs import capture as capture_graph  # noqa: E402
 
-from jen1_amd import train as T  # noqa: E402
+from jen1_amd import gemm_host as G, train as T  # noqa: E402
 
 rt = T.TrainRuntime("bf16", "cuda")
 rt.wgrad_group = 0
@@ -52,17 +52,17 @@ for rows, Lx, ci, co, k in SHAPES:
     gw = torch.zeros_like(w)
     gb = torch.zeros(co, device="cuda")
     bias = torch.zeros(co, device="cuda")
-    g = T.ConvGeom(kind, k, 1, (k - 1) // 2, Lx, Lx, ci, co) if k > 1 else T.ConvGeom("linear", 1, 1, 0, rows, rows, ci, co)
+    g = G.ConvGeom(kind, k, 1, (k - 1) // 2, Lx, Lx, ci, co) if k > 1 else G.ConvGeom("linear", 1, 1, 0, rows, rows, ci, co)
     if k == 1:
         x, dy = x.view(1, rows, ci), dy.view(1, rows, co)
     wp = rt.packed(w, kind, torch.bfloat16)
     wd = rt.packed(w, kind + "D", torch.bfloat16)
-    t_f = timed(lambda: T._conv_forward(rt, x, wp, bias, g))
-    t_d = timed(lambda: T._conv_dgrad(rt, dy, wp, g, wd))
-    t_w = timed(lambda: T._conv_wgrad(rt, x, dy, gw, g, gb))
+    t_f = timed(lambda: G.conv_forward(rt, x, wp, bias, g))
+    t_d = timed(lambda: G.conv_dgrad(rt, dy, wp, g, wd))
+    t_w = timed(lambda: G.conv_wgrad(rt, x, dy, gw, g, gb))
 
     def pair():
-        _, blk = T._conv_wgrad(rt, x, dy, gw, g, gb, defer=True)
-        T._conv_dgrad(rt, dy, wp, g, wd, pair_with=blk)
+        _, blk = G.conv_wgrad(rt, x, dy, gw, g, gb, defer=True)
+        G.conv_dgrad(rt, dy, wp, g, wd, pair_with=blk)
     t_p = timed(pair)
     print(f"{rows:6d} {ci:5d} {co:5d} {k}  {t_f:7.1f}  {t_d:8.1f}  {t_w:8.1f}  {t_p:7.1f}")
