@@ -414,6 +414,25 @@ class Jen1:
             scales = torch.cat([s.reshape(-1, 1).to(torch.float32) for _, s in frames], dim=1)
         return emb, [int(codes.shape[-1]) for codes, _ in frames], scales
 
+    @torch.no_grad()
+    def codec_report(self, wav: torch.Tensor, sr: Optional[int] = None) -> dict:
+        """What the codec alone costs on ``wav`` (``[C, n]`` or ``[B, C, n]`` at rate ``sr``; None: the model's own): the audio is converted as
+        ``generate`` converts ``init_audio``, encoded with ``encode_latents`` and decoded with ``decode_latents`` (segment by segment, to the
+        exact length), and the result is ``jen1_amd.spectral.audio_report(reconstruction, converted input, sample_rate)`` -- the floor
+        under every generation metric.  Not in the reference."""
+        ae = self.audio_encoder
+        if not hasattr(ae, "encode_latents"):
+            raise ValueError("codec_report needs an audio_encoder with encode_latents (jen1_amd.encodec.EncodecHIP)")
+        if not hasattr(ae, "decode_latents"):
+            raise ValueError("codec_report needs an audio_encoder with decode_latents (jen1_amd.encodec.EncodecHIP)")
+        from . import spectral
+        if wav.dim() == 2:
+            wav = wav.unsqueeze(0)
+        x = self.convert_audio(wav, sr, self.sample_rate, ae.channels).to(self.device)
+        z, seg_frames, scales = ae.encode_latents(x)
+        y = ae.decode_latents(z.to(getattr(ae, "decoder_device", "cpu")), seg_frames, scales=scales, length=x.shape[-1])
+        return spectral.audio_report(y.to(self.device), x, self.sample_rate, device=self.device)
+
     # generation.py:152-192
     def get_conditioning(self, cond):
         """as written in the reference: input-concat entries are read as ``cond[key][0]`` -- the FIRST batch element --

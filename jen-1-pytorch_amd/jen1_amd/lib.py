@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -31,6 +31,8 @@ FORM_SCALAR, FORM_VECTOR, FORM_FUSED256, FORM_FUSED1024 = 0, 1, 2, 3            
 LN_BWD_SCALAR256, LN_BWD_SCALAR512, LN_BWD_VECTOR256, LN_BWD_VECTOR512 = 0, 1, 2, 3
 GAIN_LOUDNESS, GAIN_PEAK, GAIN_RMS, GAIN_CLIP = 0, 1, 2, 3           # include/jen1_hip.h: jen1_gain_apply
 LIMIT_NONE, LIMIT_CLIP, LIMIT_TANH = 0, 1, 2
+SPEC_COMPLEX, SPEC_MAGNITUDE, SPEC_POWER = 0, 1, 2                   # include/jen1_spectral.h
+SPEC_LOG_NONE, SPEC_LOG_E, SPEC_LOG_DB = 0, 1, 2
 
 c_void_p, c_int, c_float, c_int64 = C.c_void_p, C.c_int32, C.c_float, C.c_int64
 
@@ -293,6 +295,19 @@ T5_SYMBOLS = {
     "jen1_t5_gate": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
 }
 
+# every symbol include/jen1_spectral.h declares (framed real FFT, banded filterbank, two-signal distance sums: csrc/spectral.hip)
+_SPEC_FRAMING = [c_int, c_int64, c_int, c_int, c_int, c_int]          # rows, n, n_fft, hop, win_length, center
+SPECTRAL_SYMBOLS = {
+    "jen1_stft_frames": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "jen1_stft_tile_frames": (c_int, [c_int]),
+    "jen1_stft": (c_int, [_P, c_int64, _P, _P, _P] + _SPEC_FRAMING + [c_int, _P]),
+    "jen1_mel": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64] + _SPEC_FRAMING + [c_int, c_int, c_float, _P]),
+    "jen1_spectral_distance_tile_frames": (c_int, [c_int]),
+    "jen1_spectral_distance_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int, c_int]),
+    "jen1_spectral_distance": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64] + _SPEC_FRAMING +
+                               [c_int, c_float, _P, c_int64, _P]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -306,7 +321,7 @@ def build(verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "jen1_hip.h"), os.path.join(INCLUDE, "jen1_train.h"),
-            os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h"), os.path.join(INCLUDE, "jen1_t5.h")]
+            os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h"), os.path.join(INCLUDE, "jen1_t5.h"), os.path.join(INCLUDE, "jen1_spectral.h")]
     hdrs += [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h") and h != "common.h"]
     deps = srcs + hdrs
     if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -355,7 +370,7 @@ def load() -> C.CDLL:
     # pulls in the system runtime instead, and two runtimes in one process fail with "no ROCm-capable device".
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS, **SPECTRAL_SYMBOLS}.items():
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
