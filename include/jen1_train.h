@@ -82,6 +82,25 @@ int jen1_train_gemm(const jen1_gemm_args* args, void* stream);
  * that do not allow the skinny form); second may be either.  Nothing may order the two (no common output). */
 int jen1_train_gemm_pair(const jen1_gemm_args* first, const jen1_gemm_args* second, void* stream);
 
+/* Which body of the kernel jen1_train_gemm(args) runs: a set of the bits below, or a negative value for arguments it refuses
+ * (jen1_last_error()).  Host only, launches nothing and needs no GPU; jen1_train_gemm launches by the same function.  No bit: the STAGED
+ * 64 x 64 body (both operands through LDS, any strides, any K, any alignment).
+ * What K each body needs, besides the alignment of its operands:
+ *   DIRECT (and TALL, SKINNY, LEAN with it): both operands K-contiguous, rows / taps / batches on 16-byte boundaries, and K a multiple of
+ *     the 16-byte vector: K % 8 == 0 in bf16, K % 4 == 0 in float32.  A lane's float32 fragment is two such vectors; with K % 8 == 4 the
+ *     upper one of the last fragment is masked, so nothing beyond column K - 1 of a row is read into the product.
+ *   FASTW: bf16, one matrix per tap, both operands [k][row] with contiguous rows on 16-byte boundaries; any K.
+ *   other K (and every other layout) take the staged body. */
+enum {
+  JEN1_GEMM_DIRECT = 1,      /* register-direct K loop: fragments straight from global memory */
+  JEN1_GEMM_TALL = 2,        /* ... with the four waves stacked along M (128 x 32 tiles): N <= 32 */
+  JEN1_GEMM_FASTW = 4,       /* the bf16 weight-gradient loop (hardware transpose reads, the bias gradient in registers) */
+  JEN1_GEMM_SKINNY = 8,      /* 32 x 16 tiles whose waves split K; the wave count (4, 8 or 16) is form >> JEN1_GEMM_WAVES_SHIFT */
+  JEN1_GEMM_LEAN = 16,       /* the kernel that holds the direct loop alone (no float32 read-modify-write of C) */
+  JEN1_GEMM_WAVES_SHIFT = 8
+};
+int jen1_train_gemm_form(const jen1_gemm_args* args);
+
 /* --- GroupNorm (+FiLM) (+SiLU): ConvBlock1d's prologue, blocks.py:137-143; Transformer1d's GroupNorm, :509 ---
  * sums[B][G][2] float32 = (sum x, sum x^2) over the group (zeroed by the call).  film: [B][film_ld] float32 or bf16
  * (same dtype as x) holding scale at [c] and shift at [C + c], or NULL.  flags bit0: SiLU.

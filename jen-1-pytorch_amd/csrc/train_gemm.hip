@@ -241,12 +241,15 @@ template <typename T> struct DFrag;
 template <> struct DFrag<bf16_t> { typedef bf16x8 type; static constexpr int PF = 4; };
 template <> struct DFrag<float> { typedef f32x8 type; static constexpr int PF = 2; };
 
-__device__ __forceinline__ void dload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff) {
+// ``hi_live``: elements 4 .. 7 of the fragment lie inside K.  A bf16 fragment is one 16-byte load and K a multiple of 8: always whole.  A
+// float32 fragment is two loads and K a multiple of 4: with K % 8 == 4 the fragment that starts at K - 4 has no upper half, and
+// what follows the row in memory (the pitch padding, the next head of an attention layout) must not be multiplied in.
+__device__ __forceinline__ void dload(bf16x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, bool) {
   f = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
-__device__ __forceinline__ void dload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff) {
+__device__ __forceinline__ void dload(f32x8& f, __amdgpu_buffer_rsrc_t r, unsigned voff, bool hi_live) {
   const u32x4 lo = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
-  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, voff == OOB ? OOB : voff + 16u, 0, 0);
+  const u32x4 hi = __builtin_amdgcn_raw_buffer_load_b128(r, (voff == OOB || !hi_live) ? OOB : voff + 16u, 0, 0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) { f.v[j] = __uint_as_float(lo[j]); f.v[4 + j] = __uint_as_float(hi[j]); }
 }
@@ -296,10 +299,11 @@ __device__ __forceinline__ void direct_loop(const GemmDev& g, const T* abase, co
     const int k = kidx * BK + kq;
     const bool live = s_next < s_end && k < g.K;
     const unsigned kb = (unsigned)k * ES;
+    const bool hi = k + 4 < g.K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB);
-      dload(xb[i], rb, (live && b_base[i] != OOB) ? b_base[i] + kb : OOB);
+      dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB, hi);
+      dload(xb[i], rb, (live && b_base[i] != OOB) ? b_base[i] + kb : OOB, hi);
     }
     ++s_next;
     if (++kidx >= ksteps) { kidx = 0; enter_tap(++cur_tap); }
@@ -643,9 +647,10 @@ __device__ __forceinline__ void skinny_body(const GemmDev& g, int bx, int by, in
     const int k = kidx * BK + kq;
     const bool live = s_next < s_end && k < g.K;
     const unsigned kb = (unsigned)k * ES;
+    const bool hi = k + 4 < g.K;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB);
-    dload(xb, rb, (live && b_base != OOB) ? b_base + kb : OOB);
+    for (int i = 0; i < 2; ++i) dload(xa[i], ra, (live && a_base[i] != OOB) ? a_base[i] + kb : OOB, hi);
+    dload(xb, rb, (live && b_base != OOB) ? b_base + kb : OOB, hi);
     s_next += NW;
     kidx += NW;
     if (kidx >= ksteps) {
@@ -808,7 +813,8 @@ int prepare(const jen1_gemm_args* args, GemmDev& g, dim3& grid, bool& skinny) {
   g.atomic = a.atomic ? 1 : 0; g.accumulate = a.accumulate ? 1 : 0; g.c_f32 = a.c_f32 ? 1 : 0; g.alpha = a.alpha;
   {
     // register-direct path: K-contiguous operands whose rows start on 16-byte boundaries and whose extents fit the
-    // 31-bit offsets of a buffer descriptor; the mapped axis of A may only be its rows; B is a plain matrix per tap
+    // 31-bit offsets of a buffer descriptor; the mapped axis of A may only be its rows; B is a plain matrix per tap.  K is a
+    // multiple of the 16-byte vector (8 in bf16, 4 in float32; dload masks the half fragment a float32 K % 8 == 4 leaves over)
     static const bool no_direct = getenv("JEN1_TRAIN_GEMM_NO_DIRECT") != nullptr;     // tuning / A-B switch, read once
     const long long es = a.dtype == JEN1_F32 ? 4 : 2;
     const long long vec = 16 / es;
@@ -848,7 +854,31 @@ int prepare(const jen1_gemm_args* args, GemmDev& g, dim3& grid, bool& skinny) {
   return 0;
 }
 
+// which body a prepared call runs (the JEN1_GEMM_* bits of include/jen1_train.h): the one decision jen1_train_gemm launches by and
+// jen1_train_gemm_form reports
+int form_of(const jen1_gemm_args& a, const GemmDev& g, bool skinny) {
+  int form = (g.direct ? JEN1_GEMM_DIRECT : 0) | (g.tall ? JEN1_GEMM_TALL : 0) | (g.fastw ? JEN1_GEMM_FASTW : 0);
+  if (skinny) {
+    // waves per workgroup by the length of the K walk: a wave keeps 8 (bf16) / 3 (float32) steps of loads in flight, and a tile with
+    // 96 steps (3 taps x 1024 channels) on 4 waves is three memory round trips in a row where 16 waves make it one
+    const int steps = ((a.K + BK - 1) / BK) * a.taps / a.splitk;
+    const int nw = steps >= 64 ? JEN1_SKINNY_NW96 : steps >= 48 ? 8 : 4;      // (32 steps on 8 waves measured slower than on 4: 7.1 vs 5.6 us)
+    return form | JEN1_GEMM_SKINNY | (nw << JEN1_GEMM_WAVES_SHIFT);
+  }
+  // the lean kernel has the register-direct K loop alone: no float32 read-modify-write epilogue (rowsum never meets g.direct)
+  if (g.direct && !(g.c_f32 && g.accumulate && !g.atomic) && g.rowsum == nullptr) form |= JEN1_GEMM_LEAN;
+  return form;
+}
+
 }  // namespace
+
+extern "C" int jen1_train_gemm_form(const jen1_gemm_args* args) {
+  GemmDev g;
+  dim3 grid;
+  bool skinny = false;
+  if (prepare(args, g, grid, skinny)) return -1;
+  return form_of(*args, g, skinny);
+}
 
 extern "C" int jen1_train_gemm(const jen1_gemm_args* args, void* stream) {
   GemmDev g;
@@ -857,16 +887,14 @@ extern "C" int jen1_train_gemm(const jen1_gemm_args* args, void* stream) {
   if (prepare(args, g, grid, skinny)) return 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool f32 = args->dtype == JEN1_F32;
-  if (skinny) {
-    // waves per workgroup by the length of the K walk: a wave keeps 8 (bf16) / 3 (float32) steps of loads in flight, and a tile with
-    // 96 steps (3 taps x 1024 channels) on 4 waves is three memory round trips in a row where 16 waves make it one
-    const int steps = ((args->K + BK - 1) / BK) * args->taps / args->splitk;
-    const int nw = steps >= 64 ? JEN1_SKINNY_NW96 : steps >= 48 ? 8 : 4;      // (32 steps on 8 waves measured slower than on 4: 7.1 vs 5.6 us)
+  const int form = form_of(*args, g, skinny);
+  if (form & JEN1_GEMM_SKINNY) {
+    const int nw = form >> JEN1_GEMM_WAVES_SHIFT;
 #define JEN1_SKINNY(TT, NWV) hipLaunchKernelGGL((train_gemm_skinny_kernel<TT, NWV>), grid, dim3(NWV * 64), 0, s, g)
     if (f32) { if (nw == 16) JEN1_SKINNY(float, 16); else if (nw == 8) JEN1_SKINNY(float, 8); else JEN1_SKINNY(float, 4); }
     else { if (nw == 16) JEN1_SKINNY(bf16_t, 16); else if (nw == 8) JEN1_SKINNY(bf16_t, 8); else JEN1_SKINNY(bf16_t, 4); }
 #undef JEN1_SKINNY
-  } else if (g.direct && !(g.c_f32 && g.accumulate && !g.atomic) && g.rowsum == nullptr) {
+  } else if (form & JEN1_GEMM_LEAN) {
     if (f32) hipLaunchKernelGGL(train_gemm_direct_kernel<float>, grid, dim3(NT), 0, s, g);
     else hipLaunchKernelGGL(train_gemm_direct_kernel<bf16_t>, grid, dim3(NT), 0, s, g);
   } else {

@@ -29,6 +29,7 @@ CFG_T128x64, CFG_T128x32, CFG_T128x16, CFG_T256x32, CFG_T256x16, CFG_T64x64 = 5,
 T5_ACT_GELU_NEW, T5_ACT_RELU, T5_MAX_TOKENS = 0, 1, 128      # include/jen1_t5.h
 FORM_SCALAR, FORM_VECTOR, FORM_FUSED256, FORM_FUSED1024 = 0, 1, 2, 3                 # include/jen1_train.h: the jen1_*_form queries
 LN_BWD_SCALAR256, LN_BWD_SCALAR512, LN_BWD_VECTOR256, LN_BWD_VECTOR512 = 0, 1, 2, 3
+GEMM_DIRECT, GEMM_TALL, GEMM_FASTW, GEMM_SKINNY, GEMM_LEAN, GEMM_WAVES_SHIFT = 1, 2, 4, 8, 16, 8     # jen1_train_gemm_form's bits
 GAIN_LOUDNESS, GAIN_PEAK, GAIN_RMS, GAIN_CLIP = 0, 1, 2, 3           # include/jen1_hip.h: jen1_gain_apply
 LIMIT_NONE, LIMIT_CLIP, LIMIT_TANH = 0, 1, 2
 SPEC_COMPLEX, SPEC_MAGNITUDE, SPEC_POWER = 0, 1, 2                   # include/jen1_spectral.h
@@ -188,6 +189,7 @@ SYMBOLS = {
     "jen1_kv_fixed_fill": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P]),
     "jen1_train_gemm": (c_int, [C.POINTER(GemmArgs), _P]),
     "jen1_train_gemm_pair": (c_int, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _P]),
+    "jen1_train_gemm_form": (c_int, [C.POINTER(GemmArgs)]),
     "jen1_attn_small_fits": (c_int, [c_int, c_int, c_int, c_int]),
     "jen1_attn_small_forward": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64] + [c_int] * 5 + [c_float, c_int, _P, _P, c_int, _P]),
     "jen1_attn_small_backward": (c_int, [_P, c_int64] * 8 + [c_int] * 5 + [c_float, _P, c_int, _P]),

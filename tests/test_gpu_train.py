@@ -295,7 +295,9 @@ def test_activation_forward_backward(rts, mode, fn):
 @pytest.mark.parametrize("B,Nq,Nk,C,heads,causal,strided", [
     (2, 24, 24, 64, 8, False, True), (2, 24, 24, 64, 8, True, True), (3, 6, 129, 128, 8, False, False),
     (2, 1, 129, 512, 8, False, True), (2, 150, 150, 64, 8, True, True), (2, 75, 129, 128, 8, False, False),
-    (2, 12, 130, 1024, 16, False, True), (1, 64, 64, 40, 8, True, False)])
+    (2, 12, 130, 1024, 16, False, True), (1, 64, 64, 40, 8, True, False),
+    # head widths 4, 12 and 20: in float32 the GEMM path's Q K^T and dO V^T have K = d with d % 8 == 4, the next head right behind
+    (2, 24, 24, 32, 8, False, True), (2, 24, 40, 96, 8, True, False), (2, 30, 24, 160, 8, False, True)])
 @pytest.mark.parametrize("small_attn", [True, False], ids=["one-launch", "gemm-path"])
 def test_attention_core_forward_backward(rts, mode, B, Nq, Nk, C, heads, causal, strided, small_attn, monkeypatch):
     """AttentionBase.forward math path (blocks.py:355-380) incl. the causal mask of blocks.py:315-319; short sequences both through
