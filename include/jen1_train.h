@@ -208,6 +208,7 @@ int jen1_act_form(const void* a, const void* b, const void* c, int64_t n);
  * in columns [h d, (h + 1) d); p [B H][Nq][ldp] (dtype) is the softmax output rounded to the dtype (P V uses the rounded values;
  * columns Nk .. ldp - 1 are written as 0), saved for the backward pass; causal keeps j <= i + (Nk - Nq) (blocks.py:315-319);
  * causal_b (int32 [B], may be NULL) gives the flag per batch element instead (a pass that mixes causal and non-causal clips).
+ * Causal attention with Nq > Nk is refused (causal set, or causal_b given): its first Nq - Nk queries keep no key.
  * kv_mask (float32 [B][Nk], may be NULL) multiplies the rows of K and V on the way in -- the padding mask of the text context, which
  * the reference multiplies into k and v (blocks.py:431-434) -- and the rows of dk / dv on the way out.
  * backward writes dq [B][Nq][lddq], dk [B][Nk][lddk], dv [B][Nk][lddv] (head h in the same columns).

@@ -231,6 +231,9 @@ extern "C" int jen1_attn_small_forward_rows(const void* q, int64_t ldq, const vo
   if (check_common("jen1_attn_small_forward", B, H, Nq, Nk, d, dtype)) return 1;
   JEN1_CHECK(q && k && v && o && p, "jen1_attn_small_forward: NULL argument");
   JEN1_CHECK(ldp >= Nk, "jen1_attn_small_forward: ldp must be >= Nk");
+  // causal with Nq > Nk: the first Nq - Nk queries keep no key; the reference's fill value makes such a row uniform, this kernel would
+  // write zeros.  Nothing in the model asks for it (self-attention: Nq == Nk), so it is refused, not guessed
+  JEN1_CHECK(!((causal || causal_b != nullptr) && Nq > Nk), "jen1_attn_small_forward: causal attention needs Nq <= Nk (Nq = %d, Nk = %d)", Nq, Nk);
   JEN1_CHECK(jen1_attn_small_fits(Nq, Nk, d, dtype), "jen1_attn_small_forward: Nq = %d, Nk = %d, d = %d do not fit one workgroup", Nq, Nk, d);
   AttnDev a = {};
   a.q = q; a.k = k; a.v = v; a.o = o; a.p = p;

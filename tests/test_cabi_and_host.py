@@ -106,6 +106,49 @@ def test_training_ops_validate_arguments_without_a_gpu(lib):
     assert refused(lib.jen1_sum_rows_inplace(p + 8, 2, 16, L.F32, None), b"sum_rows_inplace: bad arguments")                                            # 16-byte alignment
 
 
+def test_attn_small_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """jen1_attn_small_forward[_rows] / _backward[_rows] (csrc/train_attn.hip): every refusal comes before the launch and leaves its
+    message; all other arguments are valid ones.  jen1_attn_small_fits agrees with the refusals."""
+    p = 16                                                                    # any aligned non-NULL pointer: nothing is launched
+
+    def fwd(name, q=p, k=p, v=p, o=p, pp=p, ldp=8, Nq=5, Nk=7, d=8, causal=0, causal_b=None, dtype=L.F32):
+        args = (q, 16, k, 16, v, 16, o, 16, pp, ldp, 2, 2, Nq, Nk, d, 0.35, causal, causal_b, None)
+        return getattr(lib, name)(*args, *((None,) if name.endswith("_rows") else ()), dtype, None)
+
+    def bwd(name, q=p, k=p, v=p, pp=p, do=p, dq=p, dk=p, dv=p, ldp=8, Nq=5, Nk=7, d=8, dtype=L.F32):
+        args = (q, 16, k, 16, v, 16, pp, ldp, do, 16, dq, 16, dk, 16, dv, 16, 2, 2, Nq, Nk, d, 0.35, None)
+        return getattr(lib, name)(*args, *((None,) if name.endswith("_rows") else ()), dtype, None)
+
+    def refused(rc, what):
+        return rc != 0 and what in lib.jen1_last_error()
+
+    for call, names, operands in ((fwd, ("jen1_attn_small_forward", "jen1_attn_small_forward_rows"), ("q", "k", "v", "o", "pp")),
+                                  (bwd, ("jen1_attn_small_backward", "jen1_attn_small_backward_rows"), ("q", "k", "v", "pp", "do", "dq", "dk", "dv"))):
+        for name in names:
+            assert refused(call(name, dtype=7), b"dtype must be"), name
+            for op in operands:
+                assert refused(call(name, **{op: None}), b"NULL argument"), (name, op)
+            assert refused(call(name, ldp=6), b"ldp must be >= Nk"), name
+            assert refused(call(name, Nq=0), b"must be >= 1"), name
+            for shape in (dict(d=6), dict(Nq=65, Nk=65, ldp=72), dict(Nk=513, ldp=520), dict(d=132),
+                          dict(Nq=24, Nk=111, d=128, ldp=112), dict(Nq=64, Nk=122, d=64, ldp=128)):        # the last two: one key past the LDS limit
+                assert refused(call(name, **shape), b"do not fit one workgroup"), (name, shape)
+                assert lib.jen1_attn_small_fits(shape.get("Nq", 5), shape.get("Nk", 7), shape.get("d", 8), L.F32) == 0
+    # causal with Nq > Nk: the first Nq - Nk rows keep no key (the reference's fill value makes them uniform, the kernel would write
+    # zeros): refused, with the scalar flag and with flags per batch element, whatever those say
+    for name in ("jen1_attn_small_forward", "jen1_attn_small_forward_rows"):
+        assert refused(fwd(name, Nq=7, Nk=5, causal=1), b"causal attention needs Nq <= Nk"), name
+        assert refused(fwd(name, Nq=7, Nk=5, causal_b=p), b"causal attention needs Nq <= Nk"), name
+    # fits on a small grid: the limits on Nq, Nk, d, d % 4 and bytes of LDS ((2 Nq + 2 Nk)(d + 4) + 2 Nq (Nk | 1) floats <= 160 KB)
+    for Nq in (1, 24, 64, 65):
+        for Nk in (1, 110, 111, 121, 122, 512, 513):
+            for d in (4, 6, 64, 128, 132):
+                want = Nq <= 64 and Nk <= 512 and d <= 128 and d % 4 == 0 and ((2 * Nq + 2 * Nk) * (d + 4) + 2 * Nq * (Nk | 1)) * 4 <= 160 * 1024
+                for dt in (L.F32, L.BF16):
+                    assert lib.jen1_attn_small_fits(Nq, Nk, d, dt) == int(want), (Nq, Nk, d)
+    assert lib.jen1_attn_small_fits(24, 110, 128, L.F32) == 1 and lib.jen1_attn_small_fits(64, 121, 64, L.BF16) == 1
+
+
 def test_argument_validation_reports_errors_without_a_gpu(lib):
     a = L.ConvArgs()
     assert lib.jen1_conv_gemm(None, None) != 0 and b"null args" in lib.jen1_last_error()
