@@ -2,6 +2,7 @@
 // Channel-last rows x[row][c]; consecutive threads take consecutive channels, so every access is coalesced.
 // All of these are HBM-bound streaming kernels: one read of each input, one write of each output, float32 math.
 #include <cstdlib>
+#include <initializer_list>
 #include "common.h"
 #include "jen1_train.h"
 
@@ -9,8 +10,17 @@ namespace {
 
 constexpr int NT = 256;
 
-template <typename T> __device__ __forceinline__ float ldf(const T* p, long long i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ void stf(T* p, long long i, float v) { p[i] = (T)v; }
+// W elements per access: 8 is load8 / store8 (16 bytes in bf16, 2 x 16 in float32), 1 a plain converting load / store.  The streaming
+// kernels below are pure HBM traffic, so bytes per instruction is what sets their speed; the scalar forms take what the 8-wide ones
+// cannot: padded rows, groups or lengths that are no multiple of 8, tensors off a 16-byte boundary.
+template <int W, typename T> __device__ __forceinline__ void loadw(const T* p, float (&o)[W]) {
+  if constexpr (W == 8) load8(p, o);
+  else o[0] = (float)p[0];
+}
+template <int W, typename T> __device__ __forceinline__ void storew(T* p, const float (&o)[W]) {
+  if constexpr (W == 8) store8(p, o);
+  else p[0] = (T)o[0];
+}
 
 __device__ __forceinline__ float silu_grad(float f) {
   const float s = 1.0f / (1.0f + expf(-f));
@@ -40,39 +50,39 @@ __device__ __forceinline__ float gelu_grad(float x) {
   return cdf + x * pdf;
 }
 
-// thread layout for per-(b, c) reductions over t: CT channels x (NT / CT) rows per block
-struct RedGeom {
-  int CT, RT;      // channels per block, rows in flight per block
-  int rows_per_block;
-};
-
 // ---------------------------------------------------------------- GroupNorm
-template <typename T>
+// The two-pass kernels come in two widths W.  W = 8 needs rows without padding (ld == C) and groups of a multiple of 8 channels, so
+// it indexes rows by C and reads a group's moments once per 8 channels; W = 1 indexes rows by ld and reads them once per element.
+// Thread layout of the per-(b, c) reductions over t: CT columns of W channels x (NT / CT) rows per block.
+template <typename T, int W>
 __global__ __launch_bounds__(NT) void gn_sums_kernel(const void* x_, float* __restrict__ sums, int L, int C, int ld,
                                                       int groups, int cpg, int CT, int rows_per_block) {
   const T* x = reinterpret_cast<const T*>(x_);
   const int b = blockIdx.z;
-  const int c = blockIdx.y * CT + threadIdx.x % CT;
+  const int VPR = W == 8 ? C >> 3 : C;                      // accesses per row
+  const int rs = W == 8 ? C : ld;                           // row stride
+  const int vc = blockIdx.y * CT + threadIdx.x % CT;        // which access of the row
   const int ty = threadIdx.x / CT, RT = NT / CT;
   const int t0 = blockIdx.x * rows_per_block, t1 = min(L, t0 + rows_per_block);
   float s = 0.f, ss = 0.f;
-  if (c < C) {
-    const T* xp = x + (long long)b * L * ld + c;
+  if (vc < VPR) {
+    const T* xp = x + (long long)b * L * rs + vc * W;
     for (int t = t0 + ty; t < t1; t += RT) {
-      const float v = (float)xp[(long long)t * ld];
-      s += v;
-      ss += v * v;
+      float v[W];
+      loadw<W>(xp + (long long)t * rs, v);
+#pragma unroll
+      for (int j = 0; j < W; ++j) { s += v[j]; ss += v[j] * v[j]; }
     }
   }
   __shared__ float acc[64];   // [groups touched by this block][2]; at most 32 groups
-  // groups covered by this block: c range [blockIdx.y*CT, +CT)
-  const int g_lo = (blockIdx.y * CT) / cpg;
+  // groups covered by this block: c range [blockIdx.y*CT*W, +CT*W)
+  const int g_lo = (blockIdx.y * CT * W) / cpg;
   for (int i = threadIdx.x; i < 64; i += NT) acc[i] = 0.f;
   __syncthreads();
-  if (c < C) {
-    const int gi = c / cpg - g_lo;
+  if (vc < VPR) {
+    const int g = (vc * W) / cpg, gi = g - g_lo;
     if (gi < 32) { atomicAdd(&acc[2 * gi], s); atomicAdd(&acc[2 * gi + 1], ss); }
-    else { atomicAdd(&sums[((long long)b * groups + c / cpg) * 2], s); atomicAdd(&sums[((long long)b * groups + c / cpg) * 2 + 1], ss); }
+    else { atomicAdd(&sums[((long long)b * groups + g) * 2], s); atomicAdd(&sums[((long long)b * groups + g) * 2 + 1], ss); }
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 32; i += NT) {
@@ -116,22 +126,45 @@ __device__ __forceinline__ void gn_moments(const GnDev& g, int b, int c, float& 
   rstd = 1.0f / sqrtf(var + g.eps);
 }
 
-template <typename T>
+// FiLM (scale, shift) of the W channels from c0
+template <int W, typename T>
+__device__ __forceinline__ void gn_film(const GnDev& g, const T* film, int b, int c0, float (&sc)[W], float (&sh)[W]) {
+  loadw<W>(film + (long long)b * g.film_ld + c0, sc);
+  loadw<W>(film + (long long)b * g.film_ld + g.C + c0, sh);
+}
+
+template <typename T, int W>
 __global__ __launch_bounds__(NT) void gn_apply_kernel(const GnDev g) {
-  const long long total = (long long)g.B * g.L * g.C;
+  const int VPR = W == 8 ? g.C >> 3 : g.C;                  // accesses per row
+  const int rs = W == 8 ? g.C : g.ld;                       // row stride
+  const long long total = (long long)g.B * g.L * VPR;
   const T* x = reinterpret_cast<const T*>(g.x);
   const T* film = reinterpret_cast<const T*>(g.film);
   T* y = reinterpret_cast<T*>(g.y);
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
-    const int c = (int)(i % g.C);
-    const long long row = i / g.C;
+    const int c0 = (int)(i % VPR) * W;
+    const long long row = i / VPR;
     const int b = (int)(row / g.L);
     float mean, rstd;
-    gn_moments(g, b, c, mean, rstd);
-    float n = ((float)x[row * g.ld + c] - mean) * rstd * g.gamma[c] + g.beta[c];
-    if (film != nullptr) n = n * ((float)film[(long long)b * g.film_ld + c] + 1.0f) + (float)film[(long long)b * g.film_ld + g.C + c];
-    if (g.flags & 1) n = silu_precise(n);
-    y[row * g.ld + c] = (T)n;
+    gn_moments(g, b, c0, mean, rstd);
+    float v[W], ga[W], be[W], sc[W], sh[W];
+    loadw<W>(x + row * rs + c0, v);
+    loadw<W>(g.gamma + c0, ga);
+    loadw<W>(g.beta + c0, be);
+    // (beside the row stride, the one place where the widths part: the 8-wide form has FiLM's loads in flight with the row's, the
+    // scalar form reads FiLM where it uses it and holds two registers less)
+    if (W == 8 && film != nullptr) gn_film<W>(g, film, b, c0, sc, sh);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      float n = (v[j] - mean) * rstd * ga[j] + be[j];
+      if (film != nullptr) {
+        if (W == 1) gn_film<W>(g, film, b, c0, sc, sh);
+        n = n * (sc[j] + 1.0f) + sh[j];
+      }
+      if (g.flags & 1) n = silu_precise(n);
+      v[j] = n;
+    }
+    storew<W>(y + row * rs + c0, v);
   }
 }
 
@@ -199,31 +232,55 @@ __global__ __launch_bounds__(64) void gn_bwd_finish_kernel(const GnDev g) {
   g.dbeta[c] += db;
 }
 
-template <typename T>
+template <typename T, int W>
 __global__ __launch_bounds__(NT) void gn_bwd_dx_kernel(const GnDev g, void* dx_) {
   T* dx = reinterpret_cast<T*>(dx_);
-  const long long total = (long long)g.B * g.L * g.C;
+  const int VPR = W == 8 ? g.C >> 3 : g.C;                  // accesses per row
+  const int rs = W == 8 ? g.C : g.ld;                       // row stride
+  const long long total = (long long)g.B * g.L * VPR;
   const T* x = reinterpret_cast<const T*>(g.x);
   const T* dy = reinterpret_cast<const T*>(g.dy);
   const T* film = reinterpret_cast<const T*>(g.film);
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
-    const int c = (int)(i % g.C);
-    const long long row = i / g.C;
+    const int c0 = (int)(i % VPR) * W;
+    const long long row = i / VPR;
     const int b = (int)(row / g.L);
     float mean, rstd;
-    gn_moments(g, b, c, mean, rstd);
-    const float ga = g.gamma[c];
-    const float xh = ((float)x[row * g.ld + c] - mean) * rstd;
-    float sc1 = 1.0f, sh = 0.f;
-    if (film != nullptr) { sc1 = (float)film[(long long)b * g.film_ld + c] + 1.0f; sh = (float)film[(long long)b * g.film_ld + g.C + c]; }
-    float df = (float)dy[row * g.ld + c];
-    if (g.flags & 1) df *= silu_grad((xh * ga + g.beta[c]) * sc1 + sh);
-    const float dxh = df * sc1 * ga;
-    const float* gm = g.Gm + ((long long)b * g.groups + c / g.cpg) * 2;
-    float o = rstd * (dxh - gm[0] - xh * gm[1]);
-    if (g.dx_add != nullptr) o += (float)reinterpret_cast<const T*>(g.dx_add)[row * g.ld + c];
-    if (g.dx_add2 != nullptr) o += (float)reinterpret_cast<const T*>(g.dx_add2)[row * g.ld + c];
-    dx[row * g.ld + c] = (T)o;
+    gn_moments(g, b, c0, mean, rstd);
+    const float* gm = g.Gm + ((long long)b * g.groups + c0 / g.cpg) * 2;
+    const float m1 = gm[0], m2 = gm[1];
+    float v[W], d[W], ga[W], be[W], s1[W], s0[W];
+    loadw<W>(x + row * rs + c0, v);
+    loadw<W>(dy + row * rs + c0, d);
+    loadw<W>(g.gamma + c0, ga);
+    loadw<W>(g.beta + c0, be);
+#pragma unroll
+    for (int j = 0; j < W; ++j) { s1[j] = 1.0f; s0[j] = 0.f; }
+    if (film != nullptr) {
+      gn_film<W>(g, film, b, c0, s1, s0);
+#pragma unroll
+      for (int j = 0; j < W; ++j) s1[j] += 1.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const float xh = (v[j] - mean) * rstd;
+      float df = d[j];
+      if (g.flags & 1) df *= silu_grad((xh * ga[j] + be[j]) * s1[j] + s0[j]);
+      v[j] = rstd * (df * s1[j] * ga[j] - m1 - xh * m2);
+    }
+    if (g.dx_add != nullptr) {
+      float ad[W];
+      loadw<W>(reinterpret_cast<const T*>(g.dx_add) + row * rs + c0, ad);
+#pragma unroll
+      for (int j = 0; j < W; ++j) v[j] += ad[j];
+    }
+    if (g.dx_add2 != nullptr) {
+      float ad[W];
+      loadw<W>(reinterpret_cast<const T*>(g.dx_add2) + row * rs + c0, ad);
+#pragma unroll
+      for (int j = 0; j < W; ++j) v[j] += ad[j];
+    }
+    storew<W>(dx + row * rs + c0, v);
   }
 }
 
@@ -238,128 +295,6 @@ int zero2(float* a, int na, float* b, int nb, hipStream_t s) {
   hipLaunchKernelGGL(zero2_kernel, dim3((n + NT - 1) / NT), dim3(NT), 0, s, a, na, b, nb);
   JEN1_HIP(hipGetLastError());
   return 0;
-}
-
-// ---------------------------------------------------------------- 8-wide variants (rows without padding, groups of a
-// multiple of 8 channels): every thread moves 8 consecutive channels per access (16 bytes in bf16, 2 x 16 in float32)
-// instead of one element -- these kernels are pure streaming, so bytes per instruction is what sets their speed.
-template <typename T>
-__global__ __launch_bounds__(NT) void gn_sums_vec_kernel(const void* x_, float* __restrict__ sums, int L, int C, int groups, int cpg,
-                                                          int CT, int rows_per_block) {
-  const T* x = reinterpret_cast<const T*>(x_);
-  const int b = blockIdx.z, VPR = C >> 3;
-  const int vc = blockIdx.y * CT + threadIdx.x % CT;          // which 8-channel vector of the row
-  const int ty = threadIdx.x / CT, RT = NT / CT;
-  const int t0 = blockIdx.x * rows_per_block, t1 = min(L, t0 + rows_per_block);
-  float s = 0.f, ss = 0.f;
-  if (vc < VPR) {
-    const T* xp = x + (long long)b * L * C + vc * 8;
-    for (int t = t0 + ty; t < t1; t += RT) {
-      float v[8];
-      load8(xp + (long long)t * C, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { s += v[j]; ss += v[j] * v[j]; }
-    }
-  }
-  __shared__ float acc[64];
-  const int g_lo = (blockIdx.y * CT * 8) / cpg;
-  for (int i = threadIdx.x; i < 64; i += NT) acc[i] = 0.f;
-  __syncthreads();
-  if (vc < VPR) {
-    const int g = (vc * 8) / cpg, gi = g - g_lo;
-    if (gi < 32) { atomicAdd(&acc[2 * gi], s); atomicAdd(&acc[2 * gi + 1], ss); }
-    else { atomicAdd(&sums[((long long)b * groups + g) * 2], s); atomicAdd(&sums[((long long)b * groups + g) * 2 + 1], ss); }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 32; i += NT) {
-    const int g = g_lo + i;
-    if (g < groups && (acc[2 * i] != 0.f || acc[2 * i + 1] != 0.f)) {
-      atomicAdd(&sums[((long long)b * groups + g) * 2], acc[2 * i]);
-      atomicAdd(&sums[((long long)b * groups + g) * 2 + 1], acc[2 * i + 1]);
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(NT) void gn_apply_vec_kernel(const GnDev g) {
-  const int VPR = g.C >> 3;
-  const long long total = (long long)g.B * g.L * VPR;
-  const T* x = reinterpret_cast<const T*>(g.x);
-  const T* film = reinterpret_cast<const T*>(g.film);
-  T* y = reinterpret_cast<T*>(g.y);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
-    const int c0 = (int)(i % VPR) * 8;
-    const long long row = i / VPR;
-    const int b = (int)(row / g.L);
-    float mean, rstd;
-    gn_moments(g, b, c0, mean, rstd);
-    float v[8], ga[8], be[8];
-    load8(x + row * g.C + c0, v);
-    load8(g.gamma + c0, ga);
-    load8(g.beta + c0, be);
-    float sc[8], sh[8];
-    if (film != nullptr) {
-      load8(film + (long long)b * g.film_ld + c0, sc);
-      load8(film + (long long)b * g.film_ld + g.C + c0, sh);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float n = (v[j] - mean) * rstd * ga[j] + be[j];
-      if (film != nullptr) n = n * (sc[j] + 1.0f) + sh[j];
-      if (g.flags & 1) n = silu_precise(n);
-      v[j] = n;
-    }
-    store8(y + row * g.C + c0, v);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(NT) void gn_bwd_dx_vec_kernel(const GnDev g, void* dx_) {
-  T* dx = reinterpret_cast<T*>(dx_);
-  const int VPR = g.C >> 3;
-  const long long total = (long long)g.B * g.L * VPR;
-  const T* x = reinterpret_cast<const T*>(g.x);
-  const T* dy = reinterpret_cast<const T*>(g.dy);
-  const T* film = reinterpret_cast<const T*>(g.film);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
-    const int c0 = (int)(i % VPR) * 8;
-    const long long row = i / VPR;
-    const int b = (int)(row / g.L);
-    float mean, rstd;
-    gn_moments(g, b, c0, mean, rstd);
-    const float* gm = g.Gm + ((long long)b * g.groups + c0 / g.cpg) * 2;
-    const float m1 = gm[0], m2 = gm[1];
-    float v[8], d[8], ga[8], be[8], sc[8], sh[8];
-    load8(x + row * g.C + c0, v);
-    load8(dy + row * g.C + c0, d);
-    load8(g.gamma + c0, ga);
-    load8(g.beta + c0, be);
-    if (film != nullptr) {
-      load8(film + (long long)b * g.film_ld + c0, sc);
-      load8(film + (long long)b * g.film_ld + g.C + c0, sh);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (v[j] - mean) * rstd;
-      const float s1 = film != nullptr ? sc[j] + 1.0f : 1.0f, s0 = film != nullptr ? sh[j] : 0.f;
-      float df = d[j];
-      if (g.flags & 1) df *= silu_grad((xh * ga[j] + be[j]) * s1 + s0);
-      v[j] = rstd * (df * s1 * ga[j] - m1 - xh * m2);
-    }
-    if (g.dx_add != nullptr) {
-      float ad[8];
-      load8(reinterpret_cast<const T*>(g.dx_add) + row * g.C + c0, ad);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += ad[j];
-    }
-    if (g.dx_add2 != nullptr) {
-      float ad[8];
-      load8(reinterpret_cast<const T*>(g.dx_add2) + row * g.C + c0, ad);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] += ad[j];
-    }
-    store8(dx + row * g.C + c0, v);
-  }
 }
 
 // ---------------------------------------------------------------- one launch per GroupNorm: a workgroup owns one (batch element, group).
@@ -600,33 +535,6 @@ __global__ __launch_bounds__(NTB) void gn_bwd_fused_kernel(const GnDev g, void* 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void act_fwd_vec_kernel(const void* x_, void* y_, long long n8, int mode) {
-  const T* x = reinterpret_cast<const T*>(x_);
-  T* y = reinterpret_cast<T*>(y_);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n8; i += (long long)gridDim.x * NT) {
-    float v[8];
-    load8(x + 8 * i, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = mode == 0 ? gelu_erf(v[j]) : mode == 1 ? silu_precise(v[j]) : (v[j] > 0.f ? v[j] : expm1f(v[j]));
-    store8(y + 8 * i, v);
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(NT) void act_bwd_vec_kernel(const void* dy_, const void* x_, void* dx_, long long n8, int mode) {
-  const T* dy = reinterpret_cast<const T*>(dy_);
-  const T* x = reinterpret_cast<const T*>(x_);
-  T* dx = reinterpret_cast<T*>(dx_);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n8; i += (long long)gridDim.x * NT) {
-    float v[8], d[8];
-    load8(x + 8 * i, v);
-    load8(dy + 8 * i, d);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] *= mode == 0 ? gelu_grad(v[j]) : mode == 1 ? silu_grad(v[j]) : (v[j] > 0.f ? 1.f : expf(v[j]));
-    store8(dx + 8 * i, d);
-  }
-}
-
 __host__ bool vec_ok(const void* p0, const void* p1, const void* p2, int C, int ld, int cpg) {
   return ld == C && (C & 7) == 0 && (cpg & 7) == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0;
 }
@@ -650,6 +558,10 @@ int ew_grid(long long total) {
 // ---------------------------------------------------------------- LayerNorm (one wave per row, C <= 64 * 32)
 constexpr int LN_MAXPL = 32;
 
+// The scalar forms (this kernel and ln_bwd_kernel: any C, any alignment) stay kernels of their own with rolled loops over the lane's
+// channels.  As one-channel instances of the 8-wide templates below they cost registers: the forward 47 -> 64 (bf16) / 76 (float32)
+// VGPRs, the backward spills its 32 x 3 per-lane column values to scratch.  ln_bwd_kernel also divides the row sums by C where the
+// 8-wide form multiplies by 1 / C; the bits of both are what the parity gates were set against.
 template <typename T>
 __global__ __launch_bounds__(NT) void ln_fwd_kernel(const void* x_, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      void* y_, float* __restrict__ stats, int rows, int C, int ld, float eps) {
@@ -675,21 +587,29 @@ __global__ __launch_bounds__(NT) void ln_fwd_kernel(const void* x_, const float*
   if (lane == 0) { stats[2 * (long long)row] = mean; stats[2 * (long long)row + 1] = rstd; }
 }
 
-// the same with 8 channels (16 bytes in bf16) per lane and access: rows of a multiple of 8 channels, C <= 2048
-template <typename T>
-__global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const void* x_, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         void* y_, float* __restrict__ stats, int rows, int C, int ld, float eps) {
+constexpr int LN_MAXV = 4;        // 8-channel vectors per lane: C <= 2048
+constexpr int LN2_MAXV = 2;       // ... of the dual form: C <= 1024
+
+// NB LayerNorms of ONE input in one launch.  NB = 2: self-attention normalises x twice, ``norm`` for to_q and ``norm_context`` for to_kv
+// (blocks.py:427-429 with context = x): the statistics are shared, only (gamma, beta) differ.  Backward: the branches are linear in
+// the standardised row, so dx is ONE LayerNorm backward of the upstream sum g = dy1 gamma1 + dy2 gamma2; 2 NB column sums.
+template <int NB> struct LnFwdBranches { const float* gamma[NB]; const float* beta[NB]; void* y[NB]; };
+template <int NB> struct LnBwdBranches { const void* dy[NB]; const float* gamma[NB]; float* dgamma[NB]; float* dbeta[NB]; };
+
+// the forward with 8 channels (16 bytes in bf16) per lane and access, up to MAXV of them: rows of a multiple of 8 channels
+template <typename T, int MAXV, int NB>
+__global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const void* x_, const LnFwdBranches<NB> br, float* __restrict__ stats, int rows, int C,
+                                                     int ld, float eps) {
   const T* x = reinterpret_cast<const T*>(x_);
-  T* y = reinterpret_cast<T*>(y_);
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int nvec = C >> 3;
   const T* xr = x + (long long)row * ld;
-  float v[4][8];
+  float v[MAXV][8];
   float s = 0.f;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < MAXV; ++j) {
     const int vi = lane + 64 * j;
     if (vi < nvec) {
       load8(xr + vi * 8, v[j]);
@@ -701,7 +621,7 @@ __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const void* x_, const fl
   const float mean = s / C;
   float q = 0.f;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < MAXV; ++j) {
     if (lane + 64 * j < nvec) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { const float d = v[j][e] - mean; q += d * d; }
@@ -709,17 +629,21 @@ __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const void* x_, const fl
   }
   q = wave_sum(q);
   const float rstd = 1.0f / sqrtf(q / C + eps);
-  T* yr = y + (long long)row * ld;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < MAXV; ++j) {
     const int vi = lane + 64 * j;
     if (vi < nvec) {
-      float g8[8], b8[8];
-      load8(gamma + vi * 8, g8);
-      load8(beta + vi * 8, b8);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[j][e] = (v[j][e] - mean) * rstd * g8[e] + b8[e];
-      store8(yr + vi * 8, v[j]);
+      for (int e = 0; e < 8; ++e) v[j][e] = (v[j][e] - mean) * rstd;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float ga[8], be[8], o[8];
+        load8(br.gamma[b] + vi * 8, ga);
+        load8(br.beta[b] + vi * 8, be);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = v[j][e] * ga[e] + be[e];
+        store8(reinterpret_cast<T*>(br.y[b]) + (long long)row * ld + vi * 8, o);
+      }
     }
   }
   if (lane == 0) { stats[2 * (long long)row] = mean; stats[2 * (long long)row + 1] = rstd; }
@@ -789,213 +713,62 @@ __global__ __launch_bounds__(NTB) void ln_bwd_kernel(const void* dy_, const void
 
 // 8 channels per lane and access (rows of a multiple of 8 channels): the scalar form above moves two bytes per lane and load -- 43 us for
 // the 2 064 x 1 024 rows of the text context, ten times its traffic at HBM speed
-constexpr int LN_MAXV = 4;        // 8-channel vectors per lane: C <= 2048
-template <typename T, int NTB>
-__global__ __launch_bounds__(NTB) void ln_bwd_vec_kernel(const void* dy_, const void* x_, const float* __restrict__ stats,
-                                                          const float* __restrict__ gamma, void* dx_, const void* add_,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int C, int ld) {
-  extern __shared__ float ln_col[];            // [NTB / 64 - 1][2][C]
-  const T* dy = reinterpret_cast<const T*>(dy_);
+template <typename T, int NTB, int MAXV, int NB>
+__global__ __launch_bounds__(NTB) void ln_bwd_vec_kernel(const LnBwdBranches<NB> br, const void* x_, const float* __restrict__ stats, void* dx_,
+                                                          const void* add_, int rows, int C, int ld) {
+  extern __shared__ float ln_col[];            // [NTB / 64 - 1][2 NB][C]
   const T* x = reinterpret_cast<const T*>(x_);
   T* dx = reinterpret_cast<T*>(dx_);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wid = blockIdx.x * (NTB / 64) + w, nw = gridDim.x * (NTB / 64);
   const int nvec = C >> 3;
-  float ag[LN_MAXV][8], ab[LN_MAXV][8], gv[LN_MAXV][8];
+  float ac[2 * NB][MAXV][8], gv[NB][MAXV][8];          // column sums: (dgamma, dbeta) of each branch
 #pragma unroll
-  for (int j = 0; j < LN_MAXV; ++j) {
+  for (int j = 0; j < MAXV; ++j) {
     const int v = lane + 64 * j;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { ag[j][e] = 0.f; ab[j][e] = 0.f; gv[j][e] = 0.f; }
-    if (v < nvec) load8(gamma + v * 8, gv[j]);
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { ac[2 * b][j][e] = 0.f; ac[2 * b + 1][j][e] = 0.f; gv[b][j][e] = 0.f; }
+    }
+    if (v < nvec) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) load8(br.gamma[b] + v * 8, gv[b][j]);
+    }
   }
   const float inv_C = 1.0f / (float)C;
   for (int row = wid; row < rows; row += nw) {
     const float mean = stats[2 * (long long)row], rstd = stats[2 * (long long)row + 1];
-    const T* xr = x + (long long)row * ld;
-    const T* dr = dy + (long long)row * ld;
-    float xh[LN_MAXV][8], dh[LN_MAXV][8];
+    const long long ro = (long long)row * ld;
+    float xh[MAXV][8], dh[MAXV][8];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
+    for (int j = 0; j < MAXV; ++j) {
       const int v = lane + 64 * j;
       if (v < nvec) {
-        float d[8];
-        load8(xr + v * 8, xh[j]);
-        load8(dr + v * 8, d);
+        float d[NB][8];
+        load8(x + ro + v * 8, xh[j]);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) load8(reinterpret_cast<const T*>(br.dy[b]) + ro + v * 8, d[b]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           xh[j][e] = (xh[j][e] - mean) * rstd;
-          dh[j][e] = d[e] * gv[j][e];
-          s1 += dh[j][e];
-          s2 += dh[j][e] * xh[j][e];
-          ag[j][e] += d[e] * xh[j][e];
-          ab[j][e] += d[e];
+          float h = d[0][e] * gv[0][j][e];
+#pragma unroll
+          for (int b = 1; b < NB; ++b) h += d[b][e] * gv[b][j][e];
+          dh[j][e] = h;
+          s1 += h;
+          s2 += h * xh[j][e];
+#pragma unroll
+          for (int b = 0; b < NB; ++b) { ac[2 * b][j][e] += d[b][e] * xh[j][e]; ac[2 * b + 1][j][e] += d[b][e]; }
         }
       }
     }
     if (dx_ == nullptr) continue;            // (the input needs no gradient -- the text context: only the column sums are wanted)
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     s1 *= inv_C; s2 *= inv_C;
-    T* xo = dx + (long long)row * ld;
 #pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int v = lane + 64 * j;
-      if (v < nvec) {
-        float o8[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o8[e] = rstd * (dh[j][e] - s1 - xh[j][e] * s2);
-        if (add_ != nullptr) {
-          float ad[8];
-          load8(reinterpret_cast<const T*>(add_) + (long long)row * ld + v * 8, ad);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o8[e] += ad[e];
-        }
-        store8(xo + v * 8, o8);
-      }
-    }
-  }
-  if (w > 0) {
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int v = lane + 64 * j;
-      if (v < nvec) {
-        store8(ln_col + ((w - 1) * 2) * C + v * 8, ag[j]);
-        store8(ln_col + ((w - 1) * 2 + 1) * C + v * 8, ab[j]);
-      }
-    }
-  }
-  __syncthreads();
-  if (w == 0) {
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int v = lane + 64 * j;
-      if (v < nvec) {
-        for (int k = 0; k < NTB / 64 - 1; ++k) {
-          float a8[8], b8[8];
-          load8(ln_col + (k * 2) * C + v * 8, a8);
-          load8(ln_col + (k * 2 + 1) * C + v * 8, b8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { ag[j][e] += a8[e]; ab[j][e] += b8[e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { atomicAdd(dgamma + v * 8 + e, ag[j][e]); atomicAdd(dbeta + v * 8 + e, ab[j][e]); }
-      }
-    }
-  }
-}
-
-// ---- two LayerNorms of ONE input in one launch: self-attention normalises x twice, ``norm`` for to_q and ``norm_context`` for to_kv
-// (blocks.py:427-429 with context = x): the statistics are shared, only (gamma, beta) differ.  Backward: both branches are linear in
-// the standardised row, so dx is ONE LayerNorm backward of the upstream sum g = dy1 gamma1 + dy2 gamma2; four column sums.
-constexpr int LN2_MAXV = 2;       // 8-channel vectors per lane: C <= 1024
-template <typename T>
-__global__ __launch_bounds__(NT) void ln2_fwd_vec_kernel(const void* x_, const float* __restrict__ g1, const float* __restrict__ b1,
-                                                          const float* __restrict__ g2, const float* __restrict__ b2, void* y1_, void* y2_,
-                                                          float* __restrict__ stats, int rows, int C, int ld, float eps) {
-  const T* x = reinterpret_cast<const T*>(x_);
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nvec = C >> 3;
-  const T* xr = x + (long long)row * ld;
-  float v[LN2_MAXV][8];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < LN2_MAXV; ++j) {
-    const int vi = lane + 64 * j;
-    if (vi < nvec) {
-      load8(xr + vi * 8, v[j]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += v[j][e];
-    }
-  }
-  s = wave_sum(s);
-  const float mean = s / C;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < LN2_MAXV; ++j) {
-    if (lane + 64 * j < nvec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[j][e] - mean; q += d * d; }
-    }
-  }
-  q = wave_sum(q);
-  const float rstd = 1.0f / sqrtf(q / C + eps);
-  T* y1 = reinterpret_cast<T*>(y1_) + (long long)row * ld;
-  T* y2 = reinterpret_cast<T*>(y2_) + (long long)row * ld;
-#pragma unroll
-  for (int j = 0; j < LN2_MAXV; ++j) {
-    const int vi = lane + 64 * j;
-    if (vi < nvec) {
-      float ga[8], be[8], o[8];
-      load8(g1 + vi * 8, ga);
-      load8(b1 + vi * 8, be);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { v[j][e] = (v[j][e] - mean) * rstd; o[e] = v[j][e] * ga[e] + be[e]; }
-      store8(y1 + vi * 8, o);
-      load8(g2 + vi * 8, ga);
-      load8(b2 + vi * 8, be);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = v[j][e] * ga[e] + be[e];
-      store8(y2 + vi * 8, o);
-    }
-  }
-  if (lane == 0) { stats[2 * (long long)row] = mean; stats[2 * (long long)row + 1] = rstd; }
-}
-
-template <typename T, int NTB>
-__global__ __launch_bounds__(NTB) void ln2_bwd_vec_kernel(const void* dy1_, const void* dy2_, const void* x_, const float* __restrict__ stats,
-                                                           const float* __restrict__ gamma1, const float* __restrict__ gamma2, void* dx_,
-                                                           const void* add_, float* __restrict__ dgamma1, float* __restrict__ dbeta1,
-                                                           float* __restrict__ dgamma2, float* __restrict__ dbeta2, int rows, int C, int ld) {
-  extern __shared__ float ln_col[];            // [NTB / 64 - 1][4][C]
-  const T* dy1 = reinterpret_cast<const T*>(dy1_);
-  const T* dy2 = reinterpret_cast<const T*>(dy2_);
-  const T* x = reinterpret_cast<const T*>(x_);
-  T* dx = reinterpret_cast<T*>(dx_);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wid = blockIdx.x * (NTB / 64) + w, nw = gridDim.x * (NTB / 64);
-  const int nvec = C >> 3;
-  float ac[4][LN2_MAXV][8], gv1[LN2_MAXV][8], gv2[LN2_MAXV][8];      // column sums: dgamma1, dbeta1, dgamma2, dbeta2
-#pragma unroll
-  for (int j = 0; j < LN2_MAXV; ++j) {
-    const int v = lane + 64 * j;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ac[0][j][e] = ac[1][j][e] = ac[2][j][e] = ac[3][j][e] = 0.f; gv1[j][e] = gv2[j][e] = 0.f; }
-    if (v < nvec) { load8(gamma1 + v * 8, gv1[j]); load8(gamma2 + v * 8, gv2[j]); }
-  }
-  const float inv_C = 1.0f / (float)C;
-  for (int row = wid; row < rows; row += nw) {
-    const float mean = stats[2 * (long long)row], rstd = stats[2 * (long long)row + 1];
-    const long long ro = (long long)row * ld;
-    float xh[LN2_MAXV][8], dh[LN2_MAXV][8];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN2_MAXV; ++j) {
-      const int v = lane + 64 * j;
-      if (v < nvec) {
-        float d1[8], d2[8];
-        load8(x + ro + v * 8, xh[j]);
-        load8(dy1 + ro + v * 8, d1);
-        load8(dy2 + ro + v * 8, d2);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          xh[j][e] = (xh[j][e] - mean) * rstd;
-          dh[j][e] = d1[e] * gv1[j][e] + d2[e] * gv2[j][e];
-          s1 += dh[j][e];
-          s2 += dh[j][e] * xh[j][e];
-          ac[0][j][e] += d1[e] * xh[j][e];
-          ac[1][j][e] += d1[e];
-          ac[2][j][e] += d2[e] * xh[j][e];
-          ac[3][j][e] += d2[e];
-        }
-      }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    s1 *= inv_C; s2 *= inv_C;
-#pragma unroll
-    for (int j = 0; j < LN2_MAXV; ++j) {
+    for (int j = 0; j < MAXV; ++j) {
       const int v = lane + 64 * j;
       if (v < nvec) {
         float o8[8];
@@ -1011,33 +784,34 @@ __global__ __launch_bounds__(NTB) void ln2_bwd_vec_kernel(const void* dy1_, cons
       }
     }
   }
+  // the waves of the block meet in LDS, then ONE atomic per column and block
   if (w > 0) {
 #pragma unroll
-    for (int j = 0; j < LN2_MAXV; ++j) {
+    for (int j = 0; j < MAXV; ++j) {
       const int v = lane + 64 * j;
       if (v < nvec) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) store8(ln_col + ((w - 1) * 4 + k) * C + v * 8, ac[k][j]);
+        for (int k = 0; k < 2 * NB; ++k) store8(ln_col + ((w - 1) * 2 * NB + k) * C + v * 8, ac[k][j]);
       }
     }
   }
   __syncthreads();
   if (w == 0) {
-    float* outs[4] = {dgamma1, dbeta1, dgamma2, dbeta2};
 #pragma unroll
-    for (int j = 0; j < LN2_MAXV; ++j) {
+    for (int j = 0; j < MAXV; ++j) {
       const int v = lane + 64 * j;
       if (v < nvec) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < 2 * NB; ++k) {
           for (int ww = 0; ww < NTB / 64 - 1; ++ww) {
             float a8[8];
-            load8(ln_col + (ww * 4 + k) * C + v * 8, a8);
+            load8(ln_col + (ww * 2 * NB + k) * C + v * 8, a8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) ac[k][j][e] += a8[e];
           }
+          float* out = (k & 1 ? br.dbeta : br.dgamma)[k >> 1] + v * 8;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) atomicAdd(outs[k] + v * 8 + e, ac[k][j][e]);
+          for (int e = 0; e < 8; ++e) atomicAdd(out + e, ac[k][j][e]);
         }
       }
     }
@@ -1045,23 +819,30 @@ __global__ __launch_bounds__(NTB) void ln2_bwd_vec_kernel(const void* dy1_, cons
 }
 
 // ---------------------------------------------------------------- pointwise
-template <typename T>
-__global__ __launch_bounds__(NT) void act_fwd_kernel(const void* x_, void* y_, long long n, int mode) {
+template <typename T, int W>
+__global__ __launch_bounds__(NT) void act_fwd_kernel(const void* x_, void* y_, long long nw, int mode) {     // nw accesses of W elements
   const T* x = reinterpret_cast<const T*>(x_);
   T* y = reinterpret_cast<T*>(y_);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
-    const float v = (float)x[i];
-    y[i] = (T)(mode == 0 ? gelu_erf(v) : mode == 1 ? silu_precise(v) : (v > 0.f ? v : expm1f(v)));
+  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < nw; i += (long long)gridDim.x * NT) {
+    float v[W];
+    loadw<W>(x + W * i, v);
+#pragma unroll
+    for (int j = 0; j < W; ++j) v[j] = mode == 0 ? gelu_erf(v[j]) : mode == 1 ? silu_precise(v[j]) : (v[j] > 0.f ? v[j] : expm1f(v[j]));
+    storew<W>(y + W * i, v);
   }
 }
-template <typename T>
-__global__ __launch_bounds__(NT) void act_bwd_kernel(const void* dy_, const void* x_, void* dx_, long long n, int mode) {
+template <typename T, int W>
+__global__ __launch_bounds__(NT) void act_bwd_kernel(const void* dy_, const void* x_, void* dx_, long long nw, int mode) {
   const T* dy = reinterpret_cast<const T*>(dy_);
   const T* x = reinterpret_cast<const T*>(x_);
   T* dx = reinterpret_cast<T*>(dx_);
-  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n; i += (long long)gridDim.x * NT) {
-    const float v = (float)x[i];
-    dx[i] = (T)((float)dy[i] * (mode == 0 ? gelu_grad(v) : mode == 1 ? silu_grad(v) : (v > 0.f ? 1.f : expf(v))));
+  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < nw; i += (long long)gridDim.x * NT) {
+    float v[W], d[W];
+    loadw<W>(x + W * i, v);
+    loadw<W>(dy + W * i, d);
+#pragma unroll
+    for (int j = 0; j < W; ++j) v[j] = d[j] * (mode == 0 ? gelu_grad(v[j]) : mode == 1 ? silu_grad(v[j]) : (v[j] > 0.f ? 1.f : expf(v[j])));
+    storew<W>(dx + W * i, v);
   }
 }
 
@@ -1186,11 +967,13 @@ __global__ __launch_bounds__(NT) void convert_clear_add_kernel(float* __restrict
   }
 }
 
-#define DISPATCH(dtype, KERNEL, grid, ...)                                                        \
-  do {                                                                                            \
-    if ((dtype) == JEN1_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(NT), 0, s, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(NT), 0, s, __VA_ARGS__);                    \
-    JEN1_HIP(hipGetLastError());                                                                  \
+// The one launch helper.  KERNEL names the element type T, e.g. (ln_bwd_kernel<T, 512>) -- in parentheses where it holds a comma: it
+// is instantiated for float and bf16_t, and dtype picks the one that runs.
+#define LAUNCH(dtype, KERNEL, grid, block, lds, stream, ...)                                                        \
+  do {                                                                                                              \
+    if ((dtype) == JEN1_F32) { using T = float; hipLaunchKernelGGL(KERNEL, grid, block, lds, stream, __VA_ARGS__); } \
+    else { using T = bf16_t; hipLaunchKernelGGL(KERNEL, grid, block, lds, stream, __VA_ARGS__); }                   \
+    JEN1_HIP(hipGetLastError());                                                                                    \
   } while (0)
 
 int check_dtype(int dtype, const char* who) {
@@ -1198,11 +981,30 @@ int check_dtype(int dtype, const char* who) {
   return 0;
 }
 
+// the shape conditions, each in one place: the _form queries answer -1 where an entry point fails with the message
+bool gn_dims_ok(int B, int L, int C, int ld) { return B >= 1 && L >= 1 && C >= 1 && ld >= C; }
+bool gn_groups_ok(int C, int groups) { return groups >= 1 && C % groups == 0; }          // torch GroupNorm's check
+bool gn_shape_ok(int B, int L, int C, int ld, int groups) { return gn_dims_ok(B, L, C, ld) && gn_groups_ok(C, groups); }
+int gn_check_shape(const char* who, int B, int L, int C, int ld, int groups) {
+  JEN1_CHECK(gn_dims_ok(B, L, C, ld), "%s: bad shape B=%d L=%d C=%d ld=%d", who, B, L, C, ld);
+  JEN1_CHECK(gn_groups_ok(C, groups), "%s: num_channels must be divisible by num_groups", who);
+  return 0;
+}
+bool ln_shape_ok(int rows, int C, int ld) { return rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL; }
+// the dual LayerNorm has the 8-wide form only: both entry points ask for its shape and for every tensor on a 16-byte boundary
+int ln2_check(const char* who, int rows, int C, int ld, std::initializer_list<const void*> tensors) {
+  JEN1_CHECK(rows >= 1 && C >= 8 && ld >= C && (C & 7) == 0 && (ld & 7) == 0 && C <= 512 * LN2_MAXV,
+             "%s: rows of a multiple of 8 channels, C <= %d (rows=%d C=%d ld=%d)", who, 512 * LN2_MAXV, rows, C, ld);
+  uintptr_t bits = 0;
+  for (const void* p : tensors) bits |= (uintptr_t)p;
+  JEN1_CHECK((bits & 15) == 0, "%s: 16-byte aligned tensors", who);
+  return 0;
+}
+
 int gn_fill(GnDev& g, const char* who, const void* x, const float* sums, const float* gamma, const float* beta, const void* film,
             int film_ld, int B, int L, int C, int ld, int groups, float eps, int flags) {
   JEN1_CHECK(x && sums && gamma && beta, "%s: NULL argument", who);
-  JEN1_CHECK(B >= 1 && L >= 1 && C >= 1 && ld >= C, "%s: bad shape B=%d L=%d C=%d ld=%d", who, B, L, C, ld);
-  JEN1_CHECK(groups >= 1 && C % groups == 0, "%s: num_channels must be divisible by num_groups", who);   // torch GroupNorm's check
+  if (gn_check_shape(who, B, L, C, ld, groups)) return 1;
   JEN1_CHECK(film == nullptr || film_ld >= 2 * C, "%s: film_ld must be >= 2 C", who);
   memset(&g, 0, sizeof(g));
   g.x = x; g.sums = sums; g.gamma = gamma; g.beta = beta; g.film = film; g.film_ld = film_ld;
@@ -1218,7 +1020,6 @@ constexpr size_t lds_cap = 160 * 1024;           // what JEN1_MAX_LDS_ONCE asks 
 constexpr size_t lds_default = 64 * 1024;        // dynamic LDS of a launch without that attribute
 
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool gn_shape_ok(int B, int L, int C, int ld, int groups) { return B >= 1 && L >= 1 && C >= 1 && ld >= C && groups >= 1 && C % groups == 0; }
 
 int gn_sums_form(const void* x, int C, int ld, int groups) {
   return vec_ok(x, nullptr, nullptr, C, ld, C / groups) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
@@ -1265,8 +1066,6 @@ int gn_backward_form(const void* dy, const void* x, const float* gamma, const fl
   }
   return gn_ew_form(x, dy, dx, gamma, beta, film, film_ld, C, ld, groups);
 }
-
-bool ln_shape_ok(int rows, int C, int ld) { return rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL; }
 
 int ln_forward_form(const void* x, const float* gamma, const float* beta, const void* y, int C, int ld) {
   return (C & 7) == 0 && (ld & 7) == 0 && C <= 2048 && al16(x) && al16(y) && al16(gamma) && al16(beta) ? JEN1_FORM_VECTOR : JEN1_FORM_SCALAR;
@@ -1317,18 +1116,17 @@ extern "C" int jen1_act_form(const void* a, const void* b, const void* c, int64_
 extern "C" int jen1_gn_sums(const void* x, float* sums, int B, int L, int C, int ld, int groups, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_gn_sums")) return 1;
   JEN1_CHECK(x && sums, "jen1_gn_sums: NULL argument");
-  JEN1_CHECK(B >= 1 && L >= 1 && C >= 1 && ld >= C, "jen1_gn_sums: bad shape B=%d L=%d C=%d ld=%d", B, L, C, ld);
-  JEN1_CHECK(groups >= 1 && C % groups == 0, "jen1_gn_sums: num_channels must be divisible by num_groups");
+  if (gn_check_shape("jen1_gn_sums", B, L, C, ld, groups)) return 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (zero2(sums, 2 * B * groups, nullptr, 0, s)) return 1;
   int CT, rpb, gx, gy;
   if (gn_sums_form(x, C, ld, groups) == JEN1_FORM_VECTOR) {
     red_geom(C / 8, L, CT, rpb, gx, gy);
-    DISPATCH(dtype, gn_sums_vec_kernel, dim3(gx, gy, B), x, sums, L, C, groups, C / groups, CT, rpb);
+    LAUNCH(dtype, (gn_sums_kernel<T, 8>), dim3(gx, gy, B), dim3(NT), 0, s, x, sums, L, C, ld, groups, C / groups, CT, rpb);
     return 0;
   }
   red_geom(C, L, CT, rpb, gx, gy);
-  DISPATCH(dtype, gn_sums_kernel, dim3(gx, gy, B), x, sums, L, C, ld, groups, C / groups, CT, rpb);
+  LAUNCH(dtype, (gn_sums_kernel<T, 1>), dim3(gx, gy, B), dim3(NT), 0, s, x, sums, L, C, ld, groups, C / groups, CT, rpb);
   return 0;
 }
 
@@ -1346,14 +1144,8 @@ extern "C" int jen1_gn_forward(const void* x, float* sums, const float* gamma, c
   }
   g.y = y;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (form == JEN1_FORM_FUSED1024) {
-    if (dtype == JEN1_F32) hipLaunchKernelGGL((gn_fwd_fused_kernel<float, 1024>), dim3(B * groups), dim3(1024), 0, s, g, sums, lvpg);
-    else hipLaunchKernelGGL((gn_fwd_fused_kernel<bf16_t, 1024>), dim3(B * groups), dim3(1024), 0, s, g, sums, lvpg);
-  } else {
-    if (dtype == JEN1_F32) hipLaunchKernelGGL((gn_fwd_fused_kernel<float, 256>), dim3(B * groups), dim3(256), 0, s, g, sums, lvpg);
-    else hipLaunchKernelGGL((gn_fwd_fused_kernel<bf16_t, 256>), dim3(B * groups), dim3(256), 0, s, g, sums, lvpg);
-  }
-  JEN1_HIP(hipGetLastError());
+  if (form == JEN1_FORM_FUSED1024) LAUNCH(dtype, (gn_fwd_fused_kernel<T, 1024>), dim3(B * groups), dim3(1024), 0, s, g, sums, lvpg);
+  else LAUNCH(dtype, (gn_fwd_fused_kernel<T, 256>), dim3(B * groups), dim3(256), 0, s, g, sums, lvpg);
   return 0;
 }
 
@@ -1366,10 +1158,10 @@ extern "C" int jen1_gn_apply(const void* x, const float* sums, const float* gamm
   g.y = y;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (gn_ew_form(x, y, nullptr, gamma, beta, film, film_ld, C, ld, groups) == JEN1_FORM_VECTOR) {
-    DISPATCH(dtype, gn_apply_vec_kernel, dim3(ew_grid((long long)B * L * C / 8)), g);
+    LAUNCH(dtype, (gn_apply_kernel<T, 8>), dim3(ew_grid((long long)B * L * C / 8)), dim3(NT), 0, s, g);
     return 0;
   }
-  DISPATCH(dtype, gn_apply_kernel, dim3(ew_grid((long long)B * L * C)), g);
+  LAUNCH(dtype, (gn_apply_kernel<T, 1>), dim3(ew_grid((long long)B * L * C)), dim3(NT), 0, s, g);
   return 0;
 }
 
@@ -1407,33 +1199,25 @@ extern "C" int jen1_gn_backward_add2(const void* dy, const void* x, const float*
   const int form = gn_backward_form(dy, x, gamma, beta, film, film_ld, dx, B, L, C, ld, groups, lvpg);
   if (form == JEN1_FORM_FUSED256 || form == JEN1_FORM_FUSED1024) {
     if (form == JEN1_FORM_FUSED1024) {
-      const size_t lds = gn_bwd_fused_lds(1024, C / groups);
-      if (dtype == JEN1_F32) {
-        JEN1_MAX_LDS_ONCE((gn_bwd_fused_kernel<float, 1024>), (int)lds_cap);
-        hipLaunchKernelGGL((gn_bwd_fused_kernel<float, 1024>), dim3(B * groups), dim3(1024), lds, s, g, dx, lvpg);
-      } else {
-        JEN1_MAX_LDS_ONCE((gn_bwd_fused_kernel<bf16_t, 1024>), (int)lds_cap);
-        hipLaunchKernelGGL((gn_bwd_fused_kernel<bf16_t, 1024>), dim3(B * groups), dim3(1024), lds, s, g, dx, lvpg);
-      }
+      if (dtype == JEN1_F32) JEN1_MAX_LDS_ONCE((gn_bwd_fused_kernel<float, 1024>), (int)lds_cap);
+      else JEN1_MAX_LDS_ONCE((gn_bwd_fused_kernel<bf16_t, 1024>), (int)lds_cap);
+      LAUNCH(dtype, (gn_bwd_fused_kernel<T, 1024>), dim3(B * groups), dim3(1024), gn_bwd_fused_lds(1024, C / groups), s, g, dx, lvpg);
     } else {
-      const size_t lds = gn_bwd_fused_lds(256, C / groups);
-      if (dtype == JEN1_F32) hipLaunchKernelGGL((gn_bwd_fused_kernel<float, 256>), dim3(B * groups), dim3(256), lds, s, g, dx, lvpg);
-      else hipLaunchKernelGGL((gn_bwd_fused_kernel<bf16_t, 256>), dim3(B * groups), dim3(256), lds, s, g, dx, lvpg);
+      LAUNCH(dtype, (gn_bwd_fused_kernel<T, 256>), dim3(B * groups), dim3(256), gn_bwd_fused_lds(256, C / groups), s, g, dx, lvpg);
     }
-    JEN1_HIP(hipGetLastError());
     return 0;
   }
   if (zero2(P, 4 * B * C, nullptr, 0, s)) return 1;
   int CT, rpb, gx, gy;
   red_geom(C, L, CT, rpb, gx, gy);
-  DISPATCH(dtype, gn_bwd_sums_kernel, dim3(gx, gy, B), g, CT, rpb);
+  LAUNCH(dtype, gn_bwd_sums_kernel<T>, dim3(gx, gy, B), dim3(NT), 0, s, g, CT, rpb);
   hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3(B * groups + (C + 63) / 64), dim3(64), 0, s, g);
   JEN1_HIP(hipGetLastError());
   if (form == JEN1_FORM_VECTOR) {
-    DISPATCH(dtype, gn_bwd_dx_vec_kernel, dim3(ew_grid((long long)B * L * C / 8)), g, dx);
+    LAUNCH(dtype, (gn_bwd_dx_kernel<T, 8>), dim3(ew_grid((long long)B * L * C / 8)), dim3(NT), 0, s, g, dx);
     return 0;
   }
-  DISPATCH(dtype, gn_bwd_dx_kernel, dim3(ew_grid((long long)B * L * C)), g, dx);
+  LAUNCH(dtype, (gn_bwd_dx_kernel<T, 1>), dim3(ew_grid((long long)B * L * C)), dim3(NT), 0, s, g, dx);
   return 0;
 }
 
@@ -1441,13 +1225,14 @@ extern "C" int jen1_ln_forward(const void* x, const float* gamma, const float* b
                                float eps, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_ln_forward")) return 1;
   JEN1_CHECK(x && gamma && beta && y && stats, "jen1_ln_forward: NULL argument");
-  JEN1_CHECK(rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL, "jen1_ln_forward: bad shape rows=%d C=%d ld=%d (C <= %d)", rows, C, ld, 64 * LN_MAXPL);
+  JEN1_CHECK(ln_shape_ok(rows, C, ld), "jen1_ln_forward: bad shape rows=%d C=%d ld=%d (C <= %d)", rows, C, ld, 64 * LN_MAXPL);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (ln_forward_form(x, gamma, beta, y, C, ld) == JEN1_FORM_VECTOR) {
-    DISPATCH(dtype, ln_fwd_vec_kernel, dim3((rows + 3) / 4), x, gamma, beta, y, stats, rows, C, ld, eps);
+    const LnFwdBranches<1> br = {{gamma}, {beta}, {y}};
+    LAUNCH(dtype, (ln_fwd_vec_kernel<T, LN_MAXV, 1>), dim3((rows + 3) / 4), dim3(NT), 0, s, x, br, stats, rows, C, ld, eps);
     return 0;
   }
-  DISPATCH(dtype, ln_fwd_kernel, dim3((rows + 3) / 4), x, gamma, beta, y, stats, rows, C, ld, eps);
+  LAUNCH(dtype, ln_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(NT), 0, s, x, gamma, beta, y, stats, rows, C, ld, eps);
   return 0;
 }
 
@@ -1461,7 +1246,7 @@ extern "C" int jen1_ln_backward_add(const void* dy, const void* x, const float* 
   if (check_dtype(dtype, "jen1_ln_backward")) return 1;
   JEN1_CHECK(dy && x && stats && gamma && dgamma && dbeta, "jen1_ln_backward: NULL argument");
   JEN1_CHECK(dx != nullptr || dx_add == nullptr, "jen1_ln_backward_add: dx_add without dx");
-  JEN1_CHECK(rows >= 1 && C >= 1 && ld >= C && C <= 64 * LN_MAXPL, "jen1_ln_backward: bad shape rows=%d C=%d ld=%d", rows, C, ld);
+  JEN1_CHECK(ln_shape_ok(rows, C, ld), "jen1_ln_backward: bad shape rows=%d C=%d ld=%d", rows, C, ld);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int form = ln_backward_form(dy, x, gamma, dx, dx_add, rows, C, ld);
   if (form == JEN1_LN_BWD_VECTOR512 || form == JEN1_LN_BWD_VECTOR256) {
@@ -1471,31 +1256,22 @@ extern "C" int jen1_ln_backward_add(const void* dy, const void* x, const float* 
     int blocks = (rows + wpb - 1) / wpb;
     if (blocks > 32) blocks = 32;
     const size_t lds = (size_t)(wpb - 1) * 2 * C * sizeof(float);
-    if (big8) {
-      if (dtype == JEN1_F32) hipLaunchKernelGGL((ln_bwd_vec_kernel<float, 512>), dim3(blocks), dim3(512), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-      else hipLaunchKernelGGL((ln_bwd_vec_kernel<bf16_t, 512>), dim3(blocks), dim3(512), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-    } else {
-      if (dtype == JEN1_F32) hipLaunchKernelGGL((ln_bwd_vec_kernel<float, 256>), dim3(blocks), dim3(256), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-      else hipLaunchKernelGGL((ln_bwd_vec_kernel<bf16_t, 256>), dim3(blocks), dim3(256), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-    }
-    JEN1_HIP(hipGetLastError());
+    const LnBwdBranches<1> br = {{dy}, {gamma}, {dgamma}, {dbeta}};
+    if (big8) LAUNCH(dtype, (ln_bwd_vec_kernel<T, 512, LN_MAXV, 1>), dim3(blocks), dim3(512), lds, s, br, x, stats, dx, dx_add, rows, C, ld);
+    else LAUNCH(dtype, (ln_bwd_vec_kernel<T, 256, LN_MAXV, 1>), dim3(blocks), dim3(256), lds, s, br, x, stats, dx, dx_add, rows, C, ld);
     return 0;
   }
   if (form == JEN1_LN_BWD_SCALAR512) {
     int blocks = (rows + 31) / 32;
     if (blocks > 32) blocks = 32;
     const size_t lds = (size_t)7 * 2 * C * sizeof(float);
-    if (dtype == JEN1_F32) hipLaunchKernelGGL((ln_bwd_kernel<float, 512>), dim3(blocks), dim3(512), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-    else hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 512>), dim3(blocks), dim3(512), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-    JEN1_HIP(hipGetLastError());
+    LAUNCH(dtype, (ln_bwd_kernel<T, 512>), dim3(blocks), dim3(512), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
     return 0;
   }
   int blocks = (rows + 3) / 4;
   if (blocks > 64) blocks = 64;             // each wave keeps column sums over many rows: few atomics
   const size_t lds = (size_t)3 * 2 * C * sizeof(float);
-  if (dtype == JEN1_F32) hipLaunchKernelGGL((ln_bwd_kernel<float, 256>), dim3(blocks), dim3(256), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-  else hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 256>), dim3(blocks), dim3(256), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
-  JEN1_HIP(hipGetLastError());
+  LAUNCH(dtype, (ln_bwd_kernel<T, 256>), dim3(blocks), dim3(256), lds, s, dy, x, stats, gamma, dx, dx_add, dgamma, dbeta, rows, C, ld);
   return 0;
 }
 
@@ -1503,12 +1279,10 @@ extern "C" int jen1_ln2_forward(const void* x, const float* gamma1, const float*
                                 void* y2, float* stats, int rows, int C, int ld, float eps, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_ln2_forward")) return 1;
   JEN1_CHECK(x && gamma1 && beta1 && gamma2 && beta2 && y1 && y2 && stats, "jen1_ln2_forward: NULL argument");
-  JEN1_CHECK(rows >= 1 && C >= 8 && ld >= C && (C & 7) == 0 && (ld & 7) == 0 && C <= 512 * LN2_MAXV,
-             "jen1_ln2_forward: rows of a multiple of 8 channels, C <= %d (rows=%d C=%d ld=%d)", 512 * LN2_MAXV, rows, C, ld);
-  JEN1_CHECK((((uintptr_t)x | (uintptr_t)y1 | (uintptr_t)y2 | (uintptr_t)gamma1 | (uintptr_t)beta1 | (uintptr_t)gamma2 | (uintptr_t)beta2) & 15) == 0,
-             "jen1_ln2_forward: 16-byte aligned tensors");
+  if (ln2_check("jen1_ln2_forward", rows, C, ld, {x, y1, y2, gamma1, beta1, gamma2, beta2})) return 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, ln2_fwd_vec_kernel, dim3((rows + 3) / 4), x, gamma1, beta1, gamma2, beta2, y1, y2, stats, rows, C, ld, eps);
+  const LnFwdBranches<2> br = {{gamma1, gamma2}, {beta1, beta2}, {y1, y2}};
+  LAUNCH(dtype, (ln_fwd_vec_kernel<T, LN2_MAXV, 2>), dim3((rows + 3) / 4), dim3(NT), 0, s, x, br, stats, rows, C, ld, eps);
   return 0;
 }
 
@@ -1517,17 +1291,13 @@ extern "C" int jen1_ln2_backward_add(const void* dy1, const void* dy2, const voi
                                      float* dbeta2, int rows, int C, int ld, int dtype, void* stream) {
   if (check_dtype(dtype, "jen1_ln2_backward_add")) return 1;
   JEN1_CHECK(dy1 && dy2 && x && stats && gamma1 && gamma2 && dx && dgamma1 && dbeta1 && dgamma2 && dbeta2, "jen1_ln2_backward_add: NULL argument");
-  JEN1_CHECK(rows >= 1 && C >= 8 && ld >= C && (C & 7) == 0 && (ld & 7) == 0 && C <= 512 * LN2_MAXV,
-             "jen1_ln2_backward_add: rows of a multiple of 8 channels, C <= %d (rows=%d C=%d ld=%d)", 512 * LN2_MAXV, rows, C, ld);
-  JEN1_CHECK((((uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)dx_add | (uintptr_t)gamma1 | (uintptr_t)gamma2) & 15) == 0,
-             "jen1_ln2_backward_add: 16-byte aligned tensors");
+  if (ln2_check("jen1_ln2_backward_add", rows, C, ld, {dy1, dy2, x, dx, dx_add, gamma1, gamma2})) return 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int blocks = (rows + 3) / 4;
   if (blocks > 32) blocks = 32;
   const size_t lds = (size_t)3 * 4 * C * sizeof(float);
-  if (dtype == JEN1_F32) hipLaunchKernelGGL((ln2_bwd_vec_kernel<float, 256>), dim3(blocks), dim3(256), lds, s, dy1, dy2, x, stats, gamma1, gamma2, dx, dx_add, dgamma1, dbeta1, dgamma2, dbeta2, rows, C, ld);
-  else hipLaunchKernelGGL((ln2_bwd_vec_kernel<bf16_t, 256>), dim3(blocks), dim3(256), lds, s, dy1, dy2, x, stats, gamma1, gamma2, dx, dx_add, dgamma1, dbeta1, dgamma2, dbeta2, rows, C, ld);
-  JEN1_HIP(hipGetLastError());
+  const LnBwdBranches<2> br = {{dy1, dy2}, {gamma1, gamma2}, {dgamma1, dgamma2}, {dbeta1, dbeta2}};
+  LAUNCH(dtype, (ln_bwd_vec_kernel<T, 256, LN2_MAXV, 2>), dim3(blocks), dim3(256), lds, s, br, x, stats, dx, dx_add, rows, C, ld);
   return 0;
 }
 
@@ -1536,10 +1306,10 @@ extern "C" int jen1_act_forward(const void* x, void* y, int64_t n, int mode, int
   JEN1_CHECK(x && y && n >= 1 && mode >= 0 && mode <= 2, "jen1_act_forward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (act_form(x, y, nullptr, n) == JEN1_FORM_VECTOR) {
-    DISPATCH(dtype, act_fwd_vec_kernel, dim3(ew_grid(n / 8)), x, y, (long long)(n / 8), mode);
+    LAUNCH(dtype, (act_fwd_kernel<T, 8>), dim3(ew_grid(n / 8)), dim3(NT), 0, s, x, y, (long long)(n / 8), mode);
     return 0;
   }
-  DISPATCH(dtype, act_fwd_kernel, dim3(ew_grid(n)), x, y, (long long)n, mode);
+  LAUNCH(dtype, (act_fwd_kernel<T, 1>), dim3(ew_grid(n)), dim3(NT), 0, s, x, y, (long long)n, mode);
   return 0;
 }
 
@@ -1548,10 +1318,10 @@ extern "C" int jen1_act_backward(const void* dy, const void* x, void* dx, int64_
   JEN1_CHECK(dy && x && dx && n >= 1 && mode >= 0 && mode <= 2, "jen1_act_backward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (act_form(dy, x, dx, n) == JEN1_FORM_VECTOR) {
-    DISPATCH(dtype, act_bwd_vec_kernel, dim3(ew_grid(n / 8)), dy, x, dx, (long long)(n / 8), mode);
+    LAUNCH(dtype, (act_bwd_kernel<T, 8>), dim3(ew_grid(n / 8)), dim3(NT), 0, s, dy, x, dx, (long long)(n / 8), mode);
     return 0;
   }
-  DISPATCH(dtype, act_bwd_kernel, dim3(ew_grid(n)), dy, x, dx, (long long)n, mode);
+  LAUNCH(dtype, (act_bwd_kernel<T, 1>), dim3(ew_grid(n)), dim3(NT), 0, s, dy, x, dx, (long long)n, mode);
   return 0;
 }
 
@@ -1560,7 +1330,7 @@ extern "C" int jen1_softmax_forward(const float* sc, void* p, int rows, int Nq, 
   if (check_dtype(dtype, "jen1_softmax_forward")) return 1;
   JEN1_CHECK(sc && p && rows >= 1 && Nq >= 1 && Nk >= 1 && ld_s >= Nk && ld_p >= Nk && rows % Nq == 0, "jen1_softmax_forward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, softmax_fwd_kernel, dim3((rows + 3) / 4), sc, p, rows, Nq, Nk, ld_s, ld_p, causal);
+  LAUNCH(dtype, softmax_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(NT), 0, s, sc, p, rows, Nq, Nk, ld_s, ld_p, causal);
   return 0;
 }
 
@@ -1569,7 +1339,7 @@ extern "C" int jen1_softmax_backward(const void* p, const float* dp, void* ds, i
   if (check_dtype(dtype, "jen1_softmax_backward")) return 1;
   JEN1_CHECK(p && dp && ds && rows >= 1 && Nk >= 1 && ld_s >= Nk && ld_p >= Nk, "jen1_softmax_backward: bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, softmax_bwd_kernel, dim3((rows + 3) / 4), p, dp, ds, rows, Nk, ld_s, ld_p);
+  LAUNCH(dtype, softmax_bwd_kernel<T>, dim3((rows + 3) / 4), dim3(NT), 0, s, p, dp, ds, rows, Nk, ld_s, ld_p);
   return 0;
 }
 
@@ -1582,12 +1352,12 @@ extern "C" int jen1_colsum(const void* x, float* out, int rows, int C, int ld, i
     int blocks = rows / 1024;
     blocks = blocks < 1 ? 1 : (blocks > 32 ? 32 : blocks);
     const int rpb = (rows + blocks - 1) / blocks;
-    DISPATCH(dtype, colsum_rows_kernel, dim3((rows + rpb - 1) / rpb), x, out, rows, C, ld, rpb);
+    LAUNCH(dtype, colsum_rows_kernel<T>, dim3((rows + rpb - 1) / rpb), dim3(NT), 0, s, x, out, rows, C, ld, rpb);
     return 0;
   }
   int CT, rpb, gx, gy;
   red_geom(C, rows, CT, rpb, gx, gy);
-  DISPATCH(dtype, colsum_kernel, dim3(gx, gy), x, out, rows, C, ld, CT, rpb);
+  LAUNCH(dtype, colsum_kernel<T>, dim3(gx, gy), dim3(NT), 0, s, x, out, rows, C, ld, CT, rpb);
   return 0;
 }
 
@@ -1657,7 +1427,7 @@ extern "C" int jen1_repack(const jen1_repack_entry* entries_dev, int n, int tota
   if (check_dtype(dtype, "jen1_repack")) return 1;
   JEN1_CHECK(entries_dev && n >= 1 && total_tiles >= 1, "jen1_repack: bad arguments");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, repack_kernel, dim3(total_tiles), entries_dev, n, total_tiles);
+  LAUNCH(dtype, repack_kernel<T>, dim3(total_tiles), dim3(NT), 0, s, entries_dev, n, total_tiles);
   return 0;
 }
 
@@ -1665,7 +1435,7 @@ extern "C" int jen1_convert_clear_add(float* src, void* dst, const void* res, in
   if (check_dtype(dtype, "jen1_convert_clear_add")) return 1;
   JEN1_CHECK(src && dst && res && n >= 4 && (n & 3) == 0, "jen1_convert_clear_add: n must be a positive multiple of 4");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, convert_clear_add_kernel, dim3(ew_grid(n / 4)), src, dst, res, (long long)(n / 4));
+  LAUNCH(dtype, convert_clear_add_kernel<T>, dim3(ew_grid(n / 4)), dim3(NT), 0, s, src, dst, res, (long long)(n / 4));
   return 0;
 }
 
@@ -1721,7 +1491,7 @@ extern "C" int jen1_concat2(const void* a, const void* b, void* out, int64_t row
   JEN1_CHECK(a && b && out && rows >= 1 && Ca >= 8 && Cb >= 8 && (Ca & 7) == 0 && (Cb & 7) == 0, "jen1_concat2: channel counts must be positive multiples of 8");
   JEN1_CHECK((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0, "jen1_concat2: pointers must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, concat2_kernel, dim3(ew_grid(rows * ((Ca + Cb) / 8))), a, b, out, (long long)rows, Ca, Cb, scale_b);
+  LAUNCH(dtype, concat2_kernel<T>, dim3(ew_grid(rows * ((Ca + Cb) / 8))), dim3(NT), 0, s, a, b, out, (long long)rows, Ca, Cb, scale_b);
   return 0;
 }
 
@@ -1730,7 +1500,7 @@ extern "C" int jen1_split2(const void* d, void* da, void* db, int64_t rows, int 
   JEN1_CHECK(d && da && db && rows >= 1 && Ca >= 8 && Cb >= 8 && (Ca & 7) == 0 && (Cb & 7) == 0, "jen1_split2: channel counts must be positive multiples of 8");
   JEN1_CHECK((((uintptr_t)d | (uintptr_t)da | (uintptr_t)db) & 15) == 0, "jen1_split2: pointers must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, split2_kernel, dim3(ew_grid(rows * ((Ca + Cb) / 8))), d, da, db, (long long)rows, Ca, Cb, scale_b);
+  LAUNCH(dtype, split2_kernel<T>, dim3(ew_grid(rows * ((Ca + Cb) / 8))), dim3(NT), 0, s, d, da, db, (long long)rows, Ca, Cb, scale_b);
   return 0;
 }
 
@@ -1738,6 +1508,6 @@ extern "C" int jen1_convert_clear(float* src, void* dst, int64_t n, int dtype, v
   if (check_dtype(dtype, "jen1_convert_clear")) return 1;
   JEN1_CHECK(src && dst && n >= 4 && (n & 3) == 0, "jen1_convert_clear: n must be a positive multiple of 4");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DISPATCH(dtype, convert_clear_kernel, dim3(ew_grid(n / 4)), src, dst, (long long)(n / 4));
+  LAUNCH(dtype, convert_clear_kernel<T>, dim3(ew_grid(n / 4)), dim3(NT), 0, s, src, dst, (long long)(n / 4));
   return 0;
 }

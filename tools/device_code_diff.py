@@ -14,7 +14,7 @@ A and B are source trees (a directory that holds include/ and jen-1-pytorch_amd/
 
 and, per file, everything else the assembler reads (device variables, sections), without the .file and .ident lines and the
 __hip_cuid_* symbol of the compile unit, as a bag of lines: where the device variables stand among each other follows the hash in that
-symbol's name.  The figures printed are side A's.  Exit status 0: same set of symbols and all of it identical.
+symbol's name.  The figures printed are side A's; a symbol that only one side has is listed with its own.  Exit status 0: same set of symbols and all of it identical.
 """
 import argparse
 import os
@@ -139,18 +139,21 @@ def main():
         print(f"{f}  {args.flags or '(default flags)'}: {len(texts[2 * k])} lines of assembly")
         same_set = sorted(sa) == sorted(sb)
         n_same = 0
+        def figures(sym):
+            m = sym.get("meta")
+            return (f"{len(sym.get('instr', []))} lines, vgpr {figure(m, 'vgpr_count')} sgpr {figure(m, 'sgpr_count')} agpr {figure(m, 'agpr_count')} "
+                    f"lds(static) {figure(m, 'group_segment_fixed_size')} scratch {figure(m, 'private_segment_fixed_size')} "
+                    f"spills {figure(m, 'sgpr_spill_count')}+{figure(m, 'vgpr_spill_count')}")
+
         for s in sorted(set(sa) | set(sb)):
-            if s not in sa or s not in sb:
-                print(f"  {s}\n      only in {'A' if s in sa else 'B'}")
+            if s not in sa or s not in sb:       # (a renamed instantiation: its own figures, to lay beside those of the symbol it replaces)
+                print(f"  {s}\n      only in {'A' if s in sa else 'B'}   {figures(sa[s] if s in sa else sb[s])}")
                 continue
             a, b = sa[s], sb[s]
             cmp = {part: ("-" if part not in a and part not in b else "same" if a.get(part) == b.get(part) else "DIFFERS") for part in ("instr", "desc", "meta")}
             n_same += "DIFFERS" not in cmp.values()
             if not args.quiet or "DIFFERS" in cmp.values():
-                m = a.get("meta")
-                print(f"  {s}\n      instr={cmp['instr']} descriptor={cmp['desc']} metadata={cmp['meta']}   {len(a.get('instr', []))} lines, "
-                      f"vgpr {figure(m, 'vgpr_count')} sgpr {figure(m, 'sgpr_count')} agpr {figure(m, 'agpr_count')} lds(static) {figure(m, 'group_segment_fixed_size')} "
-                      f"scratch {figure(m, 'private_segment_fixed_size')} spills {figure(m, 'sgpr_spill_count')}+{figure(m, 'vgpr_spill_count')}")
+                print(f"  {s}\n      instr={cmp['instr']} descriptor={cmp['desc']} metadata={cmp['meta']}   {figures(a)}")
         good = same_set and n_same == len(sa) and ra == rb
         ok &= good
         print(f"  => {'identical' if good else 'NOT identical'}: {len(sa)} symbols in A, {len(sb)} in B, {n_same} identical in all three; "
