@@ -53,7 +53,7 @@
  * a launch that is not fully resident next to a static schedule) gives up, writes 1 + phase
  * to the error word (jen1_deep_run_err) and releases every other waiter; the results of
  * that launch are garbage, the host raises Jen1HipError and clears the word, and the next
- * launch is clean (tests/test_gpu_deep.py::test_nan_activations_flow_through_the_launch,
+ * launch is clean (tests/test_gpu_zz_fault_injection.py::test_nan_activations_flow_through_the_launch,
  * ::test_time_out_is_reported_and_cleared).
  *
  * Plain pointers and sizes only; all pointers are device pointers unless noted.
