@@ -64,12 +64,185 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
 }
 
-__device__ __forceinline__ void store_out(bf16_t* p, const float (&v)[4]) { store4(p, v); }
-__device__ __forceinline__ void store_out(float* p, const float (&v)[4]) { store4(p, v); }
+// Tile order inside an XCD's run of ids (the 256-row forms).  The 32 CUs of an XCD work on ~32 consecutive ids at a time and share one
+// 4 MiB L2: as a column of 32 M tiles under one weight tile they pull 32 + 1 operand slices per K step through it, as a bm x bn block
+// (bm * bn = 32) bm + bn.  Measured without the MFMAs (-DJEN1_BG256_NOMMA) the 256 x 256 kernel moved its operands at 7.7 TB/s whatever
+// the tile -- the traffic behind the L2s is the bound of big products, not the matrix cores.
+__device__ __forceinline__ void tile_of(int tile, int tiles_m, int tiles_n, int* tm, int* tn) {
+  const int bm = (tiles_m & 7) == 0 ? 8 : ((tiles_m & 3) == 0 ? 4 : ((tiles_m & 1) == 0 ? 2 : 1));
+  const int bn = 32 / bm;
+  if (tiles_n % bn == 0 && bm > 1) {
+    const int grp = tile >> 5, r = tile & 31;
+    const int gpm = tiles_m / bm;                       // blocks along m
+    const int gn_ = grp / gpm, gm_ = grp - gn_ * gpm;
+    *tm = gm_ * bm + (r % bm);
+    *tn = gn_ * bn + (r / bm);
+  } else {
+    *tn = tile / tiles_m;
+    *tm = tile - *tn * tiles_m;                         // consecutive ids: same weight tile, next M tile
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Tile operands.  Both operands go global -> LDS by LDS-DMA through a buffer descriptor that starts at the tile's first row and ends
+// behind its last one inside the matrix: the rows of a ragged last tile read as zeros.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) unsigned char lds_u8;
+
+// rows [r0, r0 + rows) of a [total][ld] operand of ES-byte elements
+template <int ES>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const void* p, int r0, int total, int rows, int ld) {
+  return __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(p) + (size_t)r0 * (size_t)ld * ES), 0,
+      (int)((size_t)((total - r0) < rows ? (total - r0) : rows) * (size_t)ld * ES), RSRC_FLAGS);
+}
+
+// source offsets of a wave's P LDS-DMA pieces of a tile of 128-byte rows: piece i of wave w (of NWV) fills rows (i * NWV + w) * 8 .. + 8
+// of the tile; lane l lands at row + (l >> 3), physical chunk l & 7, and fetches the global chunk (l & 7) ^ ((row >> 1) & 7) of that row
+template <int NWV, int P>
+__device__ __forceinline__ void dma_offsets(unsigned (&vo)[4], int w, int lane, int pitch_b) {
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int row = (i * NWV + w) * 8 + (lane >> 3);
+    vo[i] = (unsigned)row * (unsigned)pitch_b + (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
+  }
+}
+
+// K step kt into a stage: this wave's PA pieces of the activation tile at sb (the stage's base + w * 1024) and its PB pieces of the weight
+// tile A_B bytes behind them.  (Offset arrays of fixed bound 4, PA and PB of them used: with `const unsigned (&)[PA]` the builtin's operand
+// is type-dependent, and the host pass then rejects the specialization's second use; so is a lambda that captures the descriptors.)
+template <int NWV, int A_B, int PA, int PB>
+__device__ __forceinline__ void dma_issue(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, const unsigned (&voa)[4], const unsigned (&vob)[4],
+                                          lds_u8* sb, int kt) {
+  const unsigned so = (unsigned)kt * (unsigned)ROWB;   // the K step's byte offset inside the operand rows
+#pragma unroll
+  for (int i = 0; i < PA; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(sb + i * NWV * 1024), 16, voa[i], so, 0, 0);
+#pragma unroll
+  for (int i = 0; i < PB; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(sb + A_B + i * NWV * 1024), 16, vob[i], so, 0, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Output geometry and the direct epilogue, shared by the three NT kernels.
+// ---------------------------------------------------------------------------------------------------------------------
+// output row of GEMM row m
+__device__ __forceinline__ int out_row(const BArgs& g, int m) {
+  if (g.rows_in <= 0) return m;
+  const int q = (int)(((float)m + 0.5f) * g.inv_rows_in);
+  return q * g.rows_out + (m - q * g.rows_in);
+}
+
+// the group that holds stacked column n (groups never straddle a 128-column tile, nor a 16-column block of the 272 form, unless there is only one)
+__device__ __forceinline__ BGroup group_at(const BArgs& g, int n) {
+  int gi = 0;
+  if (g.groups)
+    for (int k = 1; k < g.n_groups; ++k) gi += (n >= g.groups[k].n0) ? 1 : 0;
+  return g.groups ? g.groups[gi] : g.inl;
+}
+
+__device__ __forceinline__ void add4(float (&v)[4], const float* p) {
+  const float4 bb = *reinterpret_cast<const float4*>(p);
+  v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
+}
+
+// a lane's 4 consecutive columns n .. n + 3 (inside group grp) of output row orow, as they leave the accumulator: alpha, bias, the row's
+// scale rs, optional accumulation, store as float32 or T
+template <typename T>
+__device__ __forceinline__ void store_direct(const BArgs& g, const BGroup& grp, int orow, int n, float rs, float (&v)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] *= g.alpha;
+  if (grp.bias) add4(v, grp.bias + n);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] *= rs;
+  const size_t off = (size_t)orow * (size_t)grp.ldc + (size_t)n;
+  float o[4];
+  if (g.c_f32) {
+    float* c = reinterpret_cast<float*>(grp.c) + off;
+    if (g.accumulate) {
+      load4(c, o);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] += o[r];
+    }
+    store4(c, v);
+  } else {
+    T* c = reinterpret_cast<T*>(grp.c) + off;
+    if (g.accumulate) {
+      load4(c, o);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] += o[r];
+    }
+    store4(c, v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The 64 x 64 block of one wave over a stage of 128-byte tile rows (big_gemm_nt_kernel, big_gemm_conv_kernel): 2 x 2 MFMA tiles of
+// 32 x 32 x 16 bf16, or 4 x 4 of 16 x 16 x 4 float32 (exact fp32).  The weight tile is the MFMA's A operand (rows n), the activation
+// tile its B operand (rows m): a lane then holds 4 consecutive n of one output row m -- 8-byte (bf16) stores.
+// C/D layout: 32x32: column (operand B index, here m) = lane & 31, rows (here n) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5);
+//             16x16: column m = lane & 15, rows n = 4 (lane >> 4) + r
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+struct Wave64 {
+  static constexpr bool F32 = is_f32<T>::value;
+  static constexpr int SUB = F32 ? 16 : 32;             // rows of one MFMA tile
+  static constexpr int NSUB = 64 / SUB;                 // tiles per wave and operand
+  static constexpr int KG = F32 ? 4 : 2;                // k groups (16-byte chunks) one MFMA k block spans
+  static constexpr int KB = 8 / KG;                     // k blocks per tile row
+  static constexpr int NQ = F32 ? 1 : 4;                // runs of 4 consecutive n a lane holds per MFMA tile
+  typedef typename std::conditional<F32, f32x4, f32x16>::type Acc;
+  Acc acc[NSUB][NSUB];                                  // [weight tile i][activation tile j]
+  int m_lane, n_lane;                                   // first tile row (m) / first column (n) of this lane inside the workgroup's tile
+  unsigned fa, fb, xo[KB];                              // this lane's weight / activation rows in a stage; its chunk per k block
+
+  // wave (wm, wn) of the workgroup; a_bytes: the activation tile's size (the weight tile lies behind it)
+  __device__ __forceinline__ Wave64(int lane, int wm, int wn, int a_bytes) {
+    const int fi = lane & (SUB - 1), fg = lane / SUB;
+    const int swz = (fi >> 1) & 7;                      // (row >> 1) & 7: the wave's row bases are multiples of 16
+    m_lane = wm * 64 + fi;
+    n_lane = wn * 64 + fg * 4;
+    fa = (unsigned)(wn * 64 + fi) * ROWB + a_bytes;
+    fb = (unsigned)(wm * 64 + fi) * ROWB;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) xo[kb] = (unsigned)((kb * KG + fg) ^ swz) * 16u;
+#pragma unroll
+    for (int i = 0; i < NSUB; ++i)
+#pragma unroll
+      for (int j = 0; j < NSUB; ++j)
+#pragma unroll
+        for (int r = 0; r < (F32 ? 4 : 16); ++r) acc[i][j][r] = 0.f;
+  }
+
+  // k block kb of the stage at base
+  __device__ __forceinline__ void step(const unsigned char* base, int kb) {
+    u32x4 wa[NSUB], xb[NSUB];
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s) {
+      wa[s] = *reinterpret_cast<const u32x4*>(base + fa + s * SUB * ROWB + xo[kb]);
+      xb[s] = *reinterpret_cast<const u32x4*>(base + fb + s * SUB * ROWB + xo[kb]);
+    }
+#pragma unroll
+    for (int i = 0; i < NSUB; ++i)
+#pragma unroll
+      for (int j = 0; j < NSUB; ++j) {
+        if constexpr (F32) {
+          // lane group fg holds k = 4 fg .. 4 fg + 3 of the 16-float block in BOTH operands: step s multiplies element s
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa[i][s]), __uint_as_float(xb[j][s]), acc[i][j], 0, 0, 0);
+        } else {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[i]), __builtin_bit_cast(bf16x8, xb[j]), acc[i][j], 0, 0, 0);
+        }
+      }
+  }
+
+  // the C/D walk: activation tile j -> tile row; (weight tile i, run q4 < NQ) -> first of 4 tile columns, held in acc[i][j][4 q4 .. + 4]
+  __device__ __forceinline__ int row(int j) const { return m_lane + j * SUB; }
+  __device__ __forceinline__ int col(int i, int q4) const { return n_lane + i * SUB + q4 * 8; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // NT form: C[m][n] = alpha * sum_k A[m][k] B[n][k]  (+ bias[n]) (* row_scale[m])
-// WM waves along M (2: 128 x 128 tile, 256 threads; 4: 256 x 128 tile, 512 threads), 2 along N, 64 x 64 per wave.
+// WM waves along M (2: 128 x 128 tile, 256 threads; 4: 256 x 128 tile, 512 threads), 2 along N, 64 x 64 per wave (Wave64).
 // NSTAGE = 3: ONE barrier per K step -- behind the barrier of step t every wave has finished step t - 1, so the stage it read is
 // refilled with tile t + 2 right there; two tiles in flight while one is multiplied.  NSTAGE = 2: the classic double buffer, two
 // barriers per step, half the LDS.
@@ -77,7 +250,6 @@ __device__ __forceinline__ void store_out(float* p, const float (&v)[4]) { store
 template <typename T, int WM, int NSTAGE>
 __global__ __launch_bounds__(512) void big_gemm_nt_kernel(const BArgs g) {
   constexpr int ES = Elem<T>::ES, BK = Elem<T>::BK;
-  constexpr bool F32 = is_f32<T>::value;
   constexpr int NWV = WM * 2;                          // waves
   constexpr int TM = WM * 64;                          // tile rows of the activation operand
   constexpr int A_B = TM * ROWB, B_B = BN * ROWB;      // bytes of the two operand tiles of a stage
@@ -91,71 +263,24 @@ __global__ __launch_bounds__(512) void big_gemm_nt_kernel(const BArgs g) {
   const int tn = tile / g.tiles_m, tm = tile - tn * g.tiles_m;         // consecutive ids: same weight tile, next M tile
   const int m0 = tm * TM, n0 = g.n_begin + tn * BN;
 
-  // ---- LDS-DMA addressing: instruction i of wave w fills rows (i * NWV + w) * 8 .. + 8 of a tile; lane l lands at row + (l >> 3),
-  // physical chunk l & 7, and fetches the global chunk (l & 7) ^ ((row >> 1) & 7) of that row --------------------------------
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.a) + (size_t)m0 * (size_t)g.lda * ES), 0,
-      (int)((size_t)((g.M - m0) < TM ? (g.M - m0) : TM) * (size_t)g.lda * ES), RSRC_FLAGS);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.b) + (size_t)n0 * (size_t)g.ldb * ES), 0,
-      (int)((size_t)((g.Ntot - n0) < BN ? (g.Ntot - n0) : BN) * (size_t)g.ldb * ES), RSRC_FLAGS);
-  unsigned voa[4], vob[4];          // (fixed bounds: a call of the LDS-DMA builtin with type-dependent operands does not instantiate in the host pass)
-  static_assert(PA <= 4 && PB <= 4, "DMA pieces per wave");
-#pragma unroll
-  for (int i = 0; i < PA; ++i) {
-    const int row = (i * NWV + w) * 8 + (lane >> 3);
-    voa[i] = (unsigned)row * (unsigned)(g.lda * ES) + (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
-  }
-#pragma unroll
-  for (int i = 0; i < PB; ++i) {
-    const int row = (i * NWV + w) * 8 + (lane >> 3);
-    vob[i] = (unsigned)row * (unsigned)(g.ldb * ES) + (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
-  }
-  typedef __attribute__((address_space(3))) unsigned char lds_u8;
-  lds_u8* const lds0 = (lds_u8*)smem;
-#define BG_ISSUE(stage_, kt_)                                                                                                        \
-  do {                                                                                                                               \
-    const unsigned so_ = (unsigned)(kt_) * (unsigned)ROWB;                                                                           \
-    lds_u8* const sb_ = lds0 + (stage_) * STAGE + w * 1024;                                                                          \
-    _Pragma("unroll") for (int i_ = 0; i_ < PA; ++i_)                                                                                \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(sb_ + i_ * NWV * 1024), 16, voa[i_], so_, 0, 0);                    \
-    _Pragma("unroll") for (int i_ = 0; i_ < PB; ++i_)                                                                                \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(sb_ + A_B + i_ * NWV * 1024), 16, vob[i_], so_, 0, 0);              \
-  } while (0)
+  const __amdgpu_buffer_rsrc_t ra = tile_rsrc<ES>(g.a, m0, g.M, TM, g.lda), rb = tile_rsrc<ES>(g.b, n0, g.Ntot, BN, g.ldb);
+  unsigned voa[4], vob[4];
+  dma_offsets<NWV, PA>(voa, w, lane, g.lda * ES);
+  dma_offsets<NWV, PB>(vob, w, lane, g.ldb * ES);
+  lds_u8* const sb = (lds_u8*)smem + w * 1024;         // this wave's first piece of stage 0
 
-  // ---- fragment addressing.  The weight tile is the MFMA's A operand (rows n), the activation tile its B operand (rows m): a
-  // lane then holds 4 consecutive n of one output row m -- 8-byte (bf16) stores -----------------------------------------------
-  const int wm = w % WM, wn = w / WM;
-  constexpr int SUB = F32 ? 16 : 32;                   // rows of one MFMA tile
-  constexpr int NSUB = 64 / SUB;                       // tiles per wave and operand
-  constexpr int KG = F32 ? 4 : 2;                      // k groups (16-byte chunks) one MFMA k block spans
-  constexpr int KB = 8 / KG;                           // k blocks per tile row
-  const int fi = lane & (SUB - 1), fg = lane / SUB;
-  const int swz = (fi >> 1) & 7;                       // (row >> 1) & 7: the wave's row bases are multiples of 16
-  const unsigned fa = (unsigned)(wn * 64 + fi) * ROWB + A_B;         // weight tile rows of this lane
-  const unsigned fb = (unsigned)(wm * 64 + fi) * ROWB;               // activation tile rows
-  unsigned xo[KB];
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) xo[kb] = (unsigned)((kb * KG + fg) ^ swz) * 16u;
-
-  typedef typename std::conditional<F32, f32x4, f32x16>::type Acc;
-  Acc acc[NSUB][NSUB];
-#pragma unroll
-  for (int i = 0; i < NSUB; ++i)
-#pragma unroll
-    for (int j = 0; j < NSUB; ++j)
-#pragma unroll
-      for (int r = 0; r < (F32 ? 4 : 16); ++r) acc[i][j][r] = 0.f;
+  Wave64<T> wv(lane, w % WM, w / WM, A_B);
+  constexpr int NSUB = Wave64<T>::NSUB;
 
   const int KT = g.K / BK;
-  BG_ISSUE(0, 0);
-  if (NSTAGE == 3 && KT > 1) BG_ISSUE(1, 1);
+  dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb, 0);
+  if (NSTAGE == 3 && KT > 1) dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb + STAGE, 1);
   int stage = 0;
   for (int kt = 0; kt < KT; ++kt) {
     if constexpr (NSTAGE == 2) {
       // two stages (64 KiB at WM = 2: two workgroups per CU cover each other's waits): tile kt + 1 is requested into the other
       // stage, which every wave left behind the closing barrier of step kt - 1
-      if (kt + 1 < KT) BG_ISSUE(stage ^ 1, kt + 1);
+      if (kt + 1 < KT) dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb + (stage ^ 1) * STAGE, kt + 1);
     }
     // this wave's pieces of tile kt have landed (tile kt + 1 may still be in flight) ...
     if (kt + 1 < KT) {
@@ -166,100 +291,38 @@ __global__ __launch_bounds__(512) void big_gemm_nt_kernel(const BArgs g) {
     }
     __builtin_amdgcn_s_barrier();                                // ... and everybody else's; every wave is done with step kt - 1
     if constexpr (NSTAGE == 3) {
-      if (kt + 2 < KT) BG_ISSUE(stage == 0 ? 2 : stage - 1, kt + 2);  // refill the stage step kt - 1 read
+      if (kt + 2 < KT) dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb + (stage == 0 ? 2 : stage - 1) * STAGE, kt + 2);     // refill the stage step kt - 1 read
     }
     const unsigned char* base = smem + stage * STAGE;
 #pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-      u32x4 wa[NSUB], xb[NSUB];
-#pragma unroll
-      for (int s = 0; s < NSUB; ++s) {
-        wa[s] = *reinterpret_cast<const u32x4*>(base + fa + s * SUB * ROWB + xo[kb]);
-        xb[s] = *reinterpret_cast<const u32x4*>(base + fb + s * SUB * ROWB + xo[kb]);
-      }
-#ifdef JEN1_BGEMM_SETPRIO
-      __builtin_amdgcn_s_setprio(1);
-#endif
-#pragma unroll
-      for (int i = 0; i < NSUB; ++i)
-#pragma unroll
-        for (int j = 0; j < NSUB; ++j) {
-          if constexpr (F32) {
-            // lane group fg holds k = 4 fg .. 4 fg + 3 of the 16-float block in BOTH operands: step s multiplies element s
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wa[i][s]), __uint_as_float(xb[j][s]), acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[i]), __builtin_bit_cast(bf16x8, xb[j]), acc[i][j], 0, 0, 0);
-          }
-        }
-#ifdef JEN1_BGEMM_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
-    }
+    for (int kb = 0; kb < Wave64<T>::KB; ++kb) wv.step(base, kb);
     if constexpr (NSTAGE == 2) __builtin_amdgcn_s_barrier();     // the stage is free for the loads of tile kt + 2
     stage = stage == NSTAGE - 1 ? 0 : stage + 1;
   }
 
-#undef BG_ISSUE
   // ---- epilogue ---------------------------------------------------------------------------------------------------------
-  // group of this column tile (groups never straddle a tile unless there is only one)
-  int gi = 0;
-  if (g.groups)
-    for (int k = 1; k < g.n_groups; ++k) gi += (n0 >= g.groups[k].n0) ? 1 : 0;
-  const BGroup grp = g.groups ? g.groups[gi] : g.inl;
-  T* cT = reinterpret_cast<T*>(grp.c);
-  float* cF = reinterpret_cast<float*>(grp.c);
+  const BGroup grp = group_at(g, n0);                  // the group of this column tile
 #pragma unroll
   for (int j = 0; j < NSUB; ++j) {
-    // C/D layout: 32x32: column (operand B index, here m) = lane & 31, rows (here n) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5);
-    //             16x16: column m = lane & 15, rows n = 4 (lane >> 4) + r
-    const int m = m0 + wm * 64 + j * SUB + fi;
+    const int m = m0 + wv.row(j);
     if (m >= g.M) continue;
-    int orow = m;
-    if (g.rows_in > 0) {
-      const int q = (int)(((float)m + 0.5f) * g.inv_rows_in);
-      orow = q * g.rows_out + (m - q * g.rows_in);
-    }
+    const int orow = out_row(g, m);
     const float rs = g.row_scale ? g.row_scale[orow] : 1.0f;
 #pragma unroll
     for (int i = 0; i < NSUB; ++i) {
 #pragma unroll
-      for (int q4 = 0; q4 < (F32 ? 1 : 4); ++q4) {
-        const int nl = F32 ? (wn * 64 + i * 16 + fg * 4) : (wn * 64 + i * 32 + q4 * 8 + fg * 4);
-        const int n = n0 + nl - grp.n0;                              // column inside the group
+      for (int q4 = 0; q4 < Wave64<T>::NQ; ++q4) {
+        const int n = n0 + wv.col(i, q4) - grp.n0;                   // column inside the group
         if (n >= grp.N) continue;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][q4 * 4 + r] * g.alpha;
-        if (grp.bias) {
-          const float4 bb = *reinterpret_cast<const float4*>(grp.bias + n);
-          v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= rs;
-        const size_t off = (size_t)orow * (size_t)grp.ldc + (size_t)n;
-        if (g.c_f32) {
-          if (g.accumulate) {
-            float o[4];
-            load4(cF + off, o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += o[r];
-          }
-          store_out(cF + off, v);
-        } else {
-          if (g.accumulate) {
-            float o[4];
-            load4(cT + off, o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += o[r];
-          }
-          store_out(cT + off, v);
-        }
+        for (int r = 0; r < 4; ++r) v[r] = wv.acc[i][j][q4 * 4 + r];
+        store_direct<T>(g, grp, orow, n, rs, v);
       }
     }
   }
 }
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Row-wise epilogue of the large tile forms (bf16 output, no accumulation): the finished tile goes through LDS -- the stages are free
@@ -269,6 +332,7 @@ __global__ __launch_bounds__(512) void big_gemm_nt_kernel(const BArgs g) {
 //   rowwise_tables  per 16-column block of the tile: output pointer, bias, pitch, first column inside its group, the group's width; per
 //                   tile row: the mapped output row (-1 past M) and the row scale
 //   rowwise_store   LDS tile [TM][CP bytes] -> global rows
+//   rowwise_epilogue  the whole of it for one kernel: tables, scale / bias, accumulators -> LDS tile, rowwise_store
 // ---------------------------------------------------------------------------------------------------------------------
 struct RowTab {
   bf16_t* c;
@@ -283,10 +347,7 @@ __device__ __forceinline__ void rowwise_tables(const BArgs& g, int m0, int n0, i
     RowTab e;
     e.c = nullptr; e.bias = nullptr; e.ldc = 0; e.n_first = 0; e.n_lim = 0; e.pad = 0;
     if (nb16 < g.Ntot) {
-      int gi = 0;
-      if (g.groups)
-        for (int k = 1; k < g.n_groups; ++k) gi += (nb16 >= g.groups[k].n0) ? 1 : 0;
-      const BGroup grp = g.groups ? g.groups[gi] : g.inl;
+      const BGroup grp = group_at(g, nb16);
       e.c = reinterpret_cast<bf16_t*>(grp.c); e.bias = grp.bias; e.ldc = grp.ldc; e.n_first = nb16 - grp.n0; e.n_lim = grp.N;
     }
     gt[tid] = e;
@@ -296,11 +357,7 @@ __device__ __forceinline__ void rowwise_tables(const BArgs& g, int m0, int n0, i
     int orow = -1;
     float rs = 1.0f;
     if (m < g.M) {
-      orow = m;
-      if (g.rows_in > 0) {
-        const int q = (int)(((float)m + 0.5f) * g.inv_rows_in);
-        orow = q * g.rows_out + (m - q * g.rows_in);
-      }
+      orow = out_row(g, m);
       if (g.row_scale) rs = g.row_scale[orow];
     }
     orl[tid] = orow;
@@ -329,6 +386,50 @@ __device__ __forceinline__ void rowwise_store(const unsigned char* ct, int CP, c
   }
 }
 
+// Which launches leave row-wise (group widths are multiples of 128; one group: of 4).  A macro, so that the kernel's `if` holds the
+// expression itself: asked through a bool-returning function (inlined, hinted with __builtin_expect or not) the compiler lays the direct
+// stores between the K loop and the row-wise code, which cost the stacked projection 0.5 of 47 us.
+#define BG_ROWWISE_OK(g) (!(g).c_f32 && !(g).accumulate && ((g).groups != nullptr || ((g).inl.N & 3) == 0))
+
+// The whole row-wise epilogue of a TM x TN tile held by NTHR threads in LDS_B bytes at smem.  The accumulator layout comes as three index
+// functions over NJ activation tiles x NI weight tiles x NQ runs of 4 columns: row(j) and col(i, q) inside the tile, val(i, j, q, r)
+template <int TM, int TN, int NTHR, int LDS_B, int NJ, int NI, int NQ, typename Row, typename Col, typename Val>
+__device__ __forceinline__ void rowwise_epilogue(const BArgs& g, unsigned char* smem, int m0, int n0, int tid, Row row, Col col, Val val) {
+  constexpr int CP = TN * 2 + 16;                     // bytes of a tile row in LDS (+16: the 16 rows of a store instruction hit 16 bank groups)
+  constexpr int NB16 = TN / 16;
+  static_assert(TM * CP + NB16 * (int)sizeof(RowTab) + TM * 8 <= LDS_B, "epilogue tile must fit the LDS allocation");
+  __syncthreads();                                    // every wave has left the K loop: the stages are free
+  unsigned char* ct = smem;
+  RowTab* gt = reinterpret_cast<RowTab*>(smem + TM * CP);
+  int* orl = reinterpret_cast<int*>(smem + TM * CP + NB16 * (int)sizeof(RowTab));
+  float* rsl = reinterpret_cast<float*>(orl + TM);
+  rowwise_tables<TM, NB16>(g, m0, n0, tid, gt, orl, rsl);
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int ml = row(j);
+    const float rs = rsl[ml];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const int nl = col(i, q);
+        const RowTab e = gt[nl >> 4];
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = val(i, j, q, r) * g.alpha;
+        const int nn = e.n_first + (nl & 15);
+        if (e.bias && nn < e.n_lim) add4(v, e.bias + nn);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] *= rs;
+        store4(reinterpret_cast<bf16_t*>(ct + ml * CP) + nl, v);
+      }
+    }
+  }
+  __syncthreads();
+  rowwise_store<TM, TN, NTHR>(ct, CP, gt, orl, tid);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // NT form, 256 x 256 output tile (bf16): 8 waves = 2 along m (128 activation rows each) x 4 along n (64 weight rows each), so a wave
 // owns 2 x 4 MFMA tiles of 32 x 32 (128 accumulator registers) and feeds 8 MFMAs from 6 fragment reads per k block -- the 64 x 64 waves
@@ -344,60 +445,20 @@ __global__ __launch_bounds__(512) void big_gemm_nt256_kernel(const BArgs g) {
   constexpr int A_B = TM * ROWB, B_B = TN * ROWB, STAGE = A_B + B_B;      // 32 KiB + 32 KiB
   constexpr int PA = TM / 8 / NWV, PB = TN / 8 / NWV;                     // 4 + 4 LDS-DMA pieces per wave and K step
   constexpr int NSA = 2, NSB = 4;                                         // MFMA tiles of a wave: weight rows (n) x activation rows (m)
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE + 12288];      // (+12 KiB: the row-wise epilogue's output tile)
+  constexpr int LDS_B = 2 * STAGE + 12288;                                // (+12 KiB: the row-wise epilogue's output tile)
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[LDS_B];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
-  // Tile order inside an XCD's run of ids.  The 32 CUs of an XCD work on ~32 consecutive ids at a time and share one 4 MiB L2: as a
-  // column of 32 M tiles under one weight tile they pull 32 + 1 operand slices per K step through it, as a bm x bn block (bm * bn = 32)
-  // bm + bn.  Measured without the MFMAs (-DJEN1_BG256_NOMMA) the kernel moved its operands at 7.7 TB/s whatever the tile -- the
-  // traffic behind the L2s is the bound of big products, not the matrix cores.
   int tn, tm;
-  {
-    const int bm = (g.tiles_m & 7) == 0 ? 8 : ((g.tiles_m & 3) == 0 ? 4 : ((g.tiles_m & 1) == 0 ? 2 : 1));
-    const int bn = 32 / bm;
-    if (g.tiles_n % bn == 0 && bm > 1) {
-      const int grp = tile >> 5, r = tile & 31;
-      const int gpm = g.tiles_m / bm;                   // blocks along m
-      const int gn_ = grp / gpm, gm_ = grp - gn_ * gpm;
-      tm = gm_ * bm + (r % bm);
-      tn = gn_ * bn + (r / bm);
-    } else {
-      tn = tile / g.tiles_m;
-      tm = tile - tn * g.tiles_m;                       // consecutive ids: same weight tile, next M tile
-    }
-  }
+  tile_of(xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, &tm, &tn);
   const int m0 = tm * TM, n0 = g.n_begin + tn * TN;
 
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.a) + (size_t)m0 * (size_t)g.lda * ES), 0,
-      (int)((size_t)((g.M - m0) < TM ? (g.M - m0) : TM) * (size_t)g.lda * ES), RSRC_FLAGS);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.b) + (size_t)n0 * (size_t)g.ldb * ES), 0,
-      (int)((size_t)((g.Ntot - n0) < TN ? (g.Ntot - n0) : TN) * (size_t)g.ldb * ES), RSRC_FLAGS);
-  unsigned voa[PA], vob[PB];
-#pragma unroll
-  for (int i = 0; i < PA; ++i) {
-    const int row = (i * NWV + w) * 8 + (lane >> 3);
-    voa[i] = (unsigned)row * (unsigned)(g.lda * ES) + (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
-  }
-#pragma unroll
-  for (int i = 0; i < PB; ++i) {
-    const int row = (i * NWV + w) * 8 + (lane >> 3);
-    vob[i] = (unsigned)row * (unsigned)(g.ldb * ES) + (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
-  }
-  typedef __attribute__((address_space(3))) unsigned char lds_u8;
-  lds_u8* const lds0 = (lds_u8*)smem;
-#define BG_ISSUE(stage_, kt_)                                                                                                        \
-  do {                                                                                                                               \
-    const unsigned so_ = (unsigned)(kt_) * (unsigned)ROWB;                                                                           \
-    lds_u8* const sb_ = lds0 + (stage_) * STAGE + w * 1024;                                                                          \
-    _Pragma("unroll") for (int i_ = 0; i_ < PA; ++i_)                                                                                \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(sb_ + i_ * NWV * 1024), 16, voa[i_], so_, 0, 0);                    \
-    _Pragma("unroll") for (int i_ = 0; i_ < PB; ++i_)                                                                                \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(sb_ + A_B + i_ * NWV * 1024), 16, vob[i_], so_, 0, 0);              \
-  } while (0)
+  const __amdgpu_buffer_rsrc_t ra = tile_rsrc<ES>(g.a, m0, g.M, TM, g.lda), rb = tile_rsrc<ES>(g.b, n0, g.Ntot, TN, g.ldb);
+  unsigned voa[4], vob[4];
+  dma_offsets<NWV, PA>(voa, w, lane, g.lda * ES);
+  dma_offsets<NWV, PB>(vob, w, lane, g.ldb * ES);
+  lds_u8* const sb = (lds_u8*)smem + w * 1024;         // this wave's first piece of stage 0
 
   const int wm = w & 1, wn = w >> 1;
   const int fi = lane & 31, fg = lane >> 5;
@@ -417,16 +478,12 @@ __global__ __launch_bounds__(512) void big_gemm_nt256_kernel(const BArgs g) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int KT = g.K / BK;
-  BG_ISSUE(0, 0);
+  dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb, 0);
   int stage = 0;
   for (int kt = 0; kt < KT; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's pieces of tile kt have landed ...
-#ifndef JEN1_BG256_NOBAR
     __builtin_amdgcn_s_barrier();                                // ... and everybody else's; every wave has left step kt - 1
-#endif
-#ifndef JEN1_BG256_NODMA
-    if (kt + 1 < KT) BG_ISSUE(stage ^ 1, kt + 1);                // refill the stage step kt - 1 read; a whole step to land
-#endif
+    if (kt + 1 < KT) dma_issue<NWV, A_B, PA, PB>(ra, rb, voa, vob, sb + (stage ^ 1) * STAGE, kt + 1);                   // refill the stage step kt - 1 read; a whole step to land
     const unsigned char* base = smem + stage * STAGE;
 #ifdef JEN1_BG256_NOMMA
     if (g.alpha == 1234.5f)
@@ -459,99 +516,31 @@ __global__ __launch_bounds__(512) void big_gemm_nt256_kernel(const BArgs g) {
     }
     stage ^= 1;
   }
-#undef BG_ISSUE
 
-  // ---- epilogue (as above; C/D layout 32x32: column (here m) = lane & 31, rows (here n) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)) ----
-  if (!g.c_f32 && !g.accumulate && (g.groups != nullptr || (g.inl.N & 3) == 0)) {      // (group widths are multiples of 128)
-    // bf16 output without accumulation: row-wise through LDS (rowwise_tables / rowwise_store above)
-    constexpr int CP = TN * 2 + 16;
-    constexpr int NB16 = TN / 16;
-    __syncthreads();
-    unsigned char* ct = smem;
-    RowTab* gt = reinterpret_cast<RowTab*>(smem + TM * CP);
-    int* orl = reinterpret_cast<int*>(smem + TM * CP + NB16 * (int)sizeof(RowTab));
-    float* rsl = reinterpret_cast<float*>(orl + TM);
-    static_assert(TM * CP + NB16 * (int)sizeof(RowTab) + TM * 8 <= 2 * STAGE + 12288, "epilogue tile must fit the LDS allocation");
-    rowwise_tables<TM, NB16>(g, m0, n0, tid, gt, orl, rsl);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NSB; ++j) {
-      const int ml = wm * (NSB * 32) + j * 32 + fi;
-      const float rs = rsl[ml];
-#pragma unroll
-      for (int i = 0; i < NSA; ++i) {
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const int nl = wn * (NSA * 32) + i * 32 + q4 * 8 + fg * 4;
-          const RowTab e = gt[nl >> 4];
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = acc[i][j][q4 * 4 + r] * g.alpha;
-          const int nn = e.n_first + (nl & 15);
-          if (e.bias && nn < e.n_lim) {
-            const float4 bb = *reinterpret_cast<const float4*>(e.bias + nn);
-            v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] *= rs;
-          store4(reinterpret_cast<T*>(ct + ml * CP) + nl, v);
-        }
-      }
-    }
-    __syncthreads();
-    rowwise_store<TM, TN, NWV * 64>(ct, CP, gt, orl, tid);
+  // ---- epilogue; C/D layout 32x32: column (here m) = lane & 31, rows (here n) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
+  auto row = [&](int j) { return wm * (NSB * 32) + j * 32 + fi; };
+  auto col = [&](int i, int q4) { return wn * (NSA * 32) + i * 32 + q4 * 8 + fg * 4; };
+  if (BG_ROWWISE_OK(g)) {
+    rowwise_epilogue<TM, TN, NWV * 64, LDS_B, NSB, NSA, 4>(g, smem, m0, n0, tid, row, col, [&](int i, int j, int q4, int r) { return acc[i][j][q4 * 4 + r]; });
     return;
   }
-  int gi = 0;
-  if (g.groups)
-    for (int k = 1; k < g.n_groups; ++k) gi += (n0 >= g.groups[k].n0) ? 1 : 0;
-  const BGroup grp = g.groups ? g.groups[gi] : g.inl;
-  T* cT = reinterpret_cast<T*>(grp.c);
-  float* cF = reinterpret_cast<float*>(grp.c);
+  const BGroup grp = group_at(g, n0);
 #pragma unroll
   for (int j = 0; j < NSB; ++j) {
-    const int m = m0 + wm * (NSB * 32) + j * 32 + fi;
+    const int m = m0 + row(j);
     if (m >= g.M) continue;
-    int orow = m;
-    if (g.rows_in > 0) {
-      const int q = (int)(((float)m + 0.5f) * g.inv_rows_in);
-      orow = q * g.rows_out + (m - q * g.rows_in);
-    }
+    const int orow = out_row(g, m);
     const float rs = g.row_scale ? g.row_scale[orow] : 1.0f;
 #pragma unroll
     for (int i = 0; i < NSA; ++i) {
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
-        const int nl = wn * (NSA * 32) + i * 32 + q4 * 8 + fg * 4;
-        const int n = n0 + nl - grp.n0;
+        const int n = n0 + col(i, q4) - grp.n0;
         if (n >= grp.N) continue;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][q4 * 4 + r] * g.alpha;
-        if (grp.bias) {
-          const float4 bb = *reinterpret_cast<const float4*>(grp.bias + n);
-          v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= rs;
-        const size_t off = (size_t)orow * (size_t)grp.ldc + (size_t)n;
-        if (g.c_f32) {
-          if (g.accumulate) {
-            float o[4];
-            load4(cF + off, o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += o[r];
-          }
-          store_out(cF + off, v);
-        } else {
-          if (g.accumulate) {
-            float o[4];
-            load4(cT + off, o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += o[r];
-          }
-          store_out(cT + off, v);
-        }
+        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][q4 * 4 + r];
+        store_direct<T>(g, grp, orow, n, rs, v);
       }
     }
   }
@@ -576,33 +565,15 @@ __global__ __launch_bounds__(512) void big_gemm_nt_s4_kernel(const BArgs g) {
   constexpr int NPA = TM / 16, NPB = TN / 16, NP = NPA + NPB;             // LDS-DMA pieces of 16 rows per K step: 16 + 16 / 17
   constexpr int NI = TN / 16, NJ = 2;
   static_assert(NPA == 2 * NWV && NPB >= 2 * NWV && NPB <= 2 * NWV + 1, "piece distribution");
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * STAGE + 16384];      // (+16 KiB: the epilogue's output tile is a little larger)
+  constexpr int LDS_B = NST * STAGE + 16384;                              // (+16 KiB: the epilogue's output tile is a little larger)
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[LDS_B];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
   int tn, tm;
-  {
-    const int bm = (g.tiles_m & 7) == 0 ? 8 : ((g.tiles_m & 3) == 0 ? 4 : ((g.tiles_m & 1) == 0 ? 2 : 1));
-    const int bn = 32 / bm;
-    if (g.tiles_n % bn == 0 && bm > 1) {
-      const int grp = tile >> 5, r = tile & 31;
-      const int gpm = g.tiles_m / bm;
-      const int gn_ = grp / gpm, gm_ = grp - gn_ * gpm;
-      tm = gm_ * bm + (r % bm);
-      tn = gn_ * bn + (r / bm);
-    } else {
-      tn = tile / g.tiles_m;
-      tm = tile - tn * g.tiles_m;
-    }
-  }
+  tile_of(xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, &tm, &tn);
   const int m0 = tm * TM, n0 = g.n_begin + tn * TN;
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.a) + (size_t)m0 * (size_t)g.lda * ES), 0,
-      (int)((size_t)((g.M - m0) < TM ? (g.M - m0) : TM) * (size_t)g.lda * ES), RSRC_FLAGS);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(g.b) + (size_t)n0 * (size_t)g.ldb * ES), 0,
-      (int)((size_t)((g.Ntot - n0) < TN ? (g.Ntot - n0) : TN) * (size_t)g.ldb * ES), RSRC_FLAGS);
+  const __amdgpu_buffer_rsrc_t ra = tile_rsrc<ES>(g.a, m0, g.M, TM, g.lda), rb = tile_rsrc<ES>(g.b, n0, g.Ntot, TN, g.ldb);
   // wave w: activation pieces w and w + 8, weight pieces w and w + 8 (+ weight piece 16 for wave 0 when TN = 272); lane l of a piece lands at
   // row l >> 2, physical chunk l & 3 and fetches the global chunk (l & 3) ^ S[(row >> 2) & 3]
   const unsigned sw4 = 0x1320u;                                            // S[k] = (sw4 >> (4 k)) & 3  ->  {0, 2, 3, 1}
@@ -615,7 +586,6 @@ __global__ __launch_bounds__(512) void big_gemm_nt_s4_kernel(const BArgs g) {
     const unsigned sx = (sw4 >> (4 * ((row >> 2) & 3))) & 3u;
     vo[j] = (unsigned)row * (unsigned)((isb ? g.ldb : g.lda) * ES) + (((unsigned)(lane & 3)) ^ sx) * 16u;
   }
-  typedef __attribute__((address_space(3))) unsigned char lds_u8;
   lds_u8* const lds0 = (lds_u8*)smem;
   const bool extra = (NPB > 2 * NWV) && w == 0;
 #define S4_ISSUE(stage_, kt_)                                                                                                        \
@@ -666,91 +636,30 @@ __global__ __launch_bounds__(512) void big_gemm_nt_s4_kernel(const BArgs g) {
   }
 #undef S4_ISSUE
 
-  // ---- epilogue, bf16 output without accumulation: row-wise through LDS (rowwise_tables / rowwise_store above) ------------------------
-  constexpr int CP = TN * 2 + 16;                     // bytes of a tile row in LDS (+16: the 16 rows of a store instruction hit 16 bank groups)
-  if (!g.c_f32 && !g.accumulate && (g.groups != nullptr || (g.inl.N & 3) == 0)) {      // (group widths are multiples of 128)
-    __syncthreads();                                  // every wave has left the K loop: the stages are free
-    unsigned char* ct = smem;
-    RowTab* gt = reinterpret_cast<RowTab*>(smem + TM * CP);
-    int* orl = reinterpret_cast<int*>(smem + TM * CP + NI * (int)sizeof(RowTab));
-    float* rsl = reinterpret_cast<float*>(orl + TM);
-    static_assert(TM * CP + NI * (int)sizeof(RowTab) + TM * 8 <= NST * STAGE + 16384, "epilogue tile must fit the LDS allocation");
-    rowwise_tables<TM, NI>(g, m0, n0, tid, gt, orl, rsl);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int ml = w * 32 + j * 16 + fi;
-      const float rs = rsl[ml];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const RowTab e = gt[i];
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] * g.alpha;
-        const int nn = e.n_first + fg * 4;
-        if (e.bias && nn < e.n_lim) {
-          const float4 bb = *reinterpret_cast<const float4*>(e.bias + nn);
-          v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= rs;
-        store4(reinterpret_cast<T*>(ct + ml * CP) + i * 16 + fg * 4, v);
-      }
-    }
-    __syncthreads();
-    rowwise_store<TM, TN, NWV * 64>(ct, CP, gt, orl, tid);
+  // ---- epilogue; C/D layout 16x16: column (here m) = lane & 15, rows (here n) = 4 (lane >> 4) + r --------------------------------------
+  auto row = [&](int j) { return w * 32 + j * 16 + fi; };
+  if (BG_ROWWISE_OK(g)) {
+    rowwise_epilogue<TM, TN, NWV * 64, LDS_B, NJ, NI, 1>(g, smem, m0, n0, tid, row, [&](int i, int) { return i * 16 + fg * 4; },
+                                                          [&](int i, int j, int, int r) { return acc[i][j][r]; });
     return;
   }
-  // ---- epilogue: C/D layout 16x16: column (here m) = lane & 15, rows (here n) = 4 (lane >> 4) + r ---------------------------------
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
-    const int m = m0 + w * 32 + j * 16 + fi;
+    const int m = m0 + row(j);
     if (m >= g.M) continue;
-    int orow = m;
-    if (g.rows_in > 0) {
-      const int q = (int)(((float)m + 0.5f) * g.inv_rows_in);
-      orow = q * g.rows_out + (m - q * g.rows_in);
-    }
+    const int orow = out_row(g, m);
     const float rs = g.row_scale ? g.row_scale[orow] : 1.0f;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int nb16 = n0 + i * 16;                                        // first column of this 16-column block (inside ONE group)
       if (nb16 >= g.Ntot) continue;
-      int gi = 0;
-      if (g.groups)
-        for (int k = 1; k < g.n_groups; ++k) gi += (nb16 >= g.groups[k].n0) ? 1 : 0;
-      const BGroup grp = g.groups ? g.groups[gi] : g.inl;
+      const BGroup grp = group_at(g, nb16);
       const int n = nb16 + fg * 4 - grp.n0;
       if (n >= grp.N) continue;
       float v[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] * g.alpha;
-      if (grp.bias) {
-        const float4 bb = *reinterpret_cast<const float4*>(grp.bias + n);
-        v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] *= rs;
-      const size_t off = (size_t)orow * (size_t)grp.ldc + (size_t)n;
-      if (g.c_f32) {
-        float* cF = reinterpret_cast<float*>(grp.c);
-        if (g.accumulate) {
-          float o[4];
-          load4(cF + off, o);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += o[r];
-        }
-        store_out(cF + off, v);
-      } else {
-        T* cT = reinterpret_cast<T*>(grp.c);
-        if (g.accumulate) {
-          float o[4];
-          load4(cT + off, o);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += o[r];
-        }
-        store_out(cT + off, v);
-      }
+      for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r];
+      store_direct<T>(g, grp, orow, n, rs, v);
     }
   }
 }
@@ -786,6 +695,7 @@ __global__ __launch_bounds__(256, 2) void big_gemm_conv_kernel(const CArgs g) {
   const int tile = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
   const int tn = tile / g.tiles_m, tm = tile - tn * g.tiles_m;
   const int m0 = tm * TM, n0 = tn * BN;
+  // (whole-operand descriptors: the activation rows of a tile are not consecutive, and the weight offset carries the tap)
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.x), 0, (int)((size_t)g.rows_x * (size_t)g.ldx * ES), RSRC_FLAGS);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.w), 0, (int)((size_t)g.taps * (size_t)g.w_tap_stride * ES), RSRC_FLAGS);
   // instruction i of wave w fills rows (i * 4 + w) * 8 .. + 8 of a tile; lane l lands at row + (l >> 3), physical chunk l & 7, and
@@ -804,7 +714,6 @@ __global__ __launch_bounds__(256, 2) void big_gemm_conv_kernel(const CArgs g) {
     xc[i] = chunk;
     vob[i] = (unsigned)(n0 + row) * (unsigned)(g.ldw * ES) + chunk;
   }
-  typedef __attribute__((address_space(3))) unsigned char lds_u8;
   lds_u8* const lds0 = (lds_u8*)smem;
   const int spt = (g.ci + BK - 1) / BK;                                   // K steps per tap (the last one may be ragged: ci % 8 == 0)
   const unsigned ci_b = (unsigned)(g.ci * ES);
@@ -832,22 +741,7 @@ __global__ __launch_bounds__(256, 2) void big_gemm_conv_kernel(const CArgs g) {
                                                  cin_b_ + xc[i_] < ci_b ? vob[i_] : 0x7ffffff0u, sob_, 0, 0);                        \
   } while (0)
 
-  // fragments: the weight tile is the MFMA's A operand (rows n), the activation tile its B operand (rows m)
-  const int wm = w & 1, wn = w >> 1;
-  const int fi = lane & 31, fg = lane >> 5;
-  const int swz = (fi >> 1) & 7;
-  const unsigned fa = (unsigned)(wn * 64 + fi) * ROWB + A_B;
-  const unsigned fb = (unsigned)(wm * 64 + fi) * ROWB;
-  unsigned xo[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) xo[kb] = (unsigned)((kb * 2 + fg) ^ swz) * 16u;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  Wave64<bf16_t> wv(lane, w & 1, w >> 1, A_B);
 
   const int KT = g.taps * spt;
   CG_ISSUE(0, 0);
@@ -862,43 +756,27 @@ __global__ __launch_bounds__(256, 2) void big_gemm_conv_kernel(const CArgs g) {
     __builtin_amdgcn_s_barrier();
     const unsigned char* base = smem + stage * STAGE;
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      u32x4 wa[2], xv[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        wa[q] = *reinterpret_cast<const u32x4*>(base + fa + q * 32 * ROWB + xo[kb]);
-        xv[q] = *reinterpret_cast<const u32x4*>(base + fb + q * 32 * ROWB + xo[kb]);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[i]), __builtin_bit_cast(bf16x8, xv[j]), acc[i][j], 0, 0, 0);
-    }
+    for (int kb = 0; kb < 4; ++kb) wv.step(base, kb);
     __builtin_amdgcn_s_barrier();
     stage ^= 1;
   }
 #undef CG_ISSUE
-  // C / D layout of the 32 x 32 MFMA: column (here m) = lane & 31, rows (here n) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   bf16_t* y = reinterpret_cast<bf16_t*>(g.y);
   const bf16_t* res = reinterpret_cast<const bf16_t*>(g.residual);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int m = m0 + wm * 64 + j * 32 + fi;
+    const int m = m0 + wv.row(j);
     if (m >= g.M) continue;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
-        const int n = n0 + wn * 64 + i * 32 + q4 * 8 + fg * 4;
+        const int n = n0 + wv.col(i, q4);
         if (n >= g.N) continue;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][q4 * 4 + r];
-        if (g.bias) {
-          const float4 bb = *reinterpret_cast<const float4*>(g.bias + n);
-          v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-        }
+        for (int r = 0; r < 4; ++r) v[r] = wv.acc[i][j][q4 * 4 + r];
+        if (g.bias) add4(v, g.bias + n);
         const size_t off = (size_t)m * (size_t)g.ldy + (size_t)n;
         if (res) {
           float o[4];
@@ -906,7 +784,7 @@ __global__ __launch_bounds__(256, 2) void big_gemm_conv_kernel(const CArgs g) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += o[r];
         }
-        store_out(y + off, v);
+        store4(y + off, v);
       }
     }
   }
@@ -1226,6 +1104,89 @@ __global__ __launch_bounds__(256) void kv_fixed_fill_kernel(const FixedEntry* __
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------
+// jen1_big_gemm: three forms.  (1) 128 x 128 tiles, two LDS stages (64 KiB: two workgroups per CU cover each other's barriers and waits):
+// products of a few hundred tiles (the training shapes, 1024 .. 2064 rows against 512 .. 2048 columns).  (2) 256 x 128 tiles, 8 waves,
+// three stages: float32, and bf16 products whose groups are not 256-column multiples.  (3) 256 x 256 tiles (big_gemm_nt256_kernel), bf16:
+// products of >= ~200 such tiles.  A launch runs in rounds of one tile per CU, so the columns are cut where the big tiles fill whole
+// rounds and the rest goes to form (1) in a second launch: the stacked projection of a sampling plan (1024 x 17408: 4 x 68 tiles)
+// is one full round of 256 big tiles + 64 small ones instead of a second round that 16 of the 256 CUs work on.
+// The four-stage form (big_gemm_nt_s4_kernel<272>) takes column counts that are multiples of 272 when that tiling fills its rounds of one
+// tile per CU better than 256-wide tiles (the stacked projection, M = 1024: 256 tiles = exactly one round against 272 = 1.06: 54 -> 47 us;
+// the 256-wide instance of the same kernel measured slower than the two-stage 32 x 32 form everywhere and is not built).
+// ---------------------------------------------------------------------------------------------------------------------
+// The tuning switches (unset: the route below decides).  JEN1_BGEMM_WM = 2 / 4 forces form (1) / (2) for every call of the process (read
+// once; any other value is ignored).  JEN1_BGEMM_T256 = 0 / 1 forbids / forces form (3); JEN1_BGEMM_S4 = 0: never the 272 form, 272:
+// whenever the shape allows.  These two are read per call: the parity tests switch them.
+struct BForce { int wm, t256, s4; };
+static BForce big_gemm_forces() {
+  static const int wm = [] { const char* e = getenv("JEN1_BGEMM_WM"); const int v = e ? atoi(e) : 0; return v == 2 || v == 4 ? v : 0; }();
+  const char* e256 = getenv("JEN1_BGEMM_T256");
+  const char* es4 = getenv("JEN1_BGEMM_S4");
+  return {wm, e256 ? atoi(e256) : -1, es4 ? atoi(es4) : -1};
+}
+
+struct BRoute {
+  bool s272;                    // the whole product on the 256 x 272 form; else
+  int n_big;                    // columns [0, n_big) on the 256 x 256 form, and the rest on
+  int wm;                       // 2: 128 x 128 tiles, two stages; 4: 256 x 128 tiles, three stages
+};
+static BRoute big_gemm_route(const jen1_bgemm_args& a, int n_cu, const BForce& f) {
+  BRoute r = {false, 0, 2};
+  const bool bf16 = a.dtype == JEN1_BF16 && !f.wm;
+  const int n_groups = a.groups ? a.n_groups : 1;
+  const int tm = (a.M + 255) / 256, tn_all = (a.Ntot + 255) / 256;
+  if (bf16 && f.s4 != 0 && f.t256 != 1 && a.K >= 32 && a.K % 32 == 0 && a.Ntot % 272 == 0 &&
+      (n_groups == 1 || (a.group_align >= 16 && a.group_align % 16 == 0))) {
+    const long long t272 = (long long)tm * (a.Ntot / 272), t256 = (long long)tm * tn_all;
+    // rounds of one tile per CU x tile width: which tiling fills the chip better
+    const double c272 = (double)((t272 + n_cu - 1) / n_cu) * 272.0, c256 = (double)((t256 + n_cu - 1) / n_cu) * 256.0;
+    r.s272 = f.s4 == 272 || (t272 >= (n_cu * 3) / 4 && c272 < c256 && a.K >= 512);
+    if (r.s272) return r;
+  }
+  if (bf16 && f.t256 != 0 && (n_groups == 1 || (a.group_align >= 256 && a.group_align % 256 == 0))) {
+    if (f.t256 == 1) {
+      r.n_big = a.Ntot;
+    } else if (tm * tn_all >= (n_cu * 3) / 4 && a.K >= 512) {
+      // whole rounds of big tiles; the last round may stay if it is at least 3/4 full, and a remainder narrower than 256 columns rides along
+      const int rounds = (tm * tn_all) / n_cu, tail = tm * tn_all - rounds * n_cu;
+      int tn_big = tn_all;
+      if (tail > 0 && tail * 4 < n_cu * 3 && rounds >= 1) tn_big = (rounds * n_cu) / tm;
+      r.n_big = tn_big >= tn_all ? a.Ntot : tn_big * 256;
+      if (n_groups > 1 && r.n_big < a.Ntot && r.n_big % a.group_align != 0) r.n_big -= r.n_big % a.group_align;      // (cut on a group boundary multiple)
+    }
+  }
+  const int t256 = tm * ((a.Ntot - r.n_big + BN - 1) / BN);
+  r.wm = f.wm ? f.wm : ((t256 >= 512 && a.K >= 2048) ? 4 : 2);
+  return r;
+}
+
+// one launch helper per kernel; each sets the tile counts of its tiling
+static void launch_s4_272(BArgs g, hipStream_t s) {
+  g.tiles_m = (g.M + 255) / 256;
+  g.tiles_n = g.Ntot / 272;
+  hipLaunchKernelGGL(big_gemm_nt_s4_kernel<272>, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+}
+static void launch_nt256(BArgs g, int n_big, hipStream_t s) {         // columns [0, n_big)
+  g.Ntot = n_big;
+  g.tiles_m = (g.M + 255) / 256;
+  g.tiles_n = (n_big + 255) / 256;
+  hipLaunchKernelGGL(big_gemm_nt256_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+}
+static void launch_nt(BArgs g, int n_begin, int dtype, int wm, hipStream_t s) {      // columns [n_begin, Ntot)
+  g.n_begin = n_begin;
+  g.tiles_m = (g.M + wm * 64 - 1) / (wm * 64);
+  g.tiles_n = (g.Ntot - n_begin + BN - 1) / BN;
+  const dim3 grid(g.tiles_m * g.tiles_n), block(wm * 128);
+  if (wm == 4) {
+    if (dtype == JEN1_F32) hipLaunchKernelGGL((big_gemm_nt_kernel<float, 4, 3>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((big_gemm_nt_kernel<bf16_t, 4, 3>), grid, block, 0, s, g);
+  } else {
+    if (dtype == JEN1_F32) hipLaunchKernelGGL((big_gemm_nt_kernel<float, 2, 2>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((big_gemm_nt_kernel<bf16_t, 2, 2>), grid, block, 0, s, g);
+  }
+}
+
 extern "C" int jen1_big_gemm(const jen1_bgemm_args* a, void* stream) {
   JEN1_CHECK(a && a->a && a->b && ((a->groups && a->n_groups >= 1) || (a->c && a->n_groups <= 1)), "big_gemm: null argument");
   const int es = a->dtype == JEN1_F32 ? 4 : 2;
@@ -1244,79 +1205,16 @@ extern "C" int jen1_big_gemm(const jen1_bgemm_args* a, void* stream) {
   g.inv_rows_in = a->rows_in > 0 ? 1.0f / (float)a->rows_in : 0.f;
   g.alpha = a->alpha;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // Three forms.  (1) 128 x 128 tiles, two LDS stages (64 KiB: two workgroups per CU cover each other's barriers and waits): products
-  // of a few hundred tiles (the training shapes, 1024 .. 2064 rows against 512 .. 2048 columns).  (2) 256 x 128 tiles, 8 waves, three
-  // stages: float32, and bf16 products whose groups are not 256-column multiples.  (3) 256 x 256 tiles (big_gemm_nt256_kernel), bf16:
-  // products of >= ~200 such tiles.  A launch runs in rounds of one tile per CU, so the columns are cut where the big tiles fill whole
-  // rounds and the rest goes to form (1) in a second launch: the stacked projection of a sampling plan (1024 x 17408: 4 x 68 tiles)
-  // is one full round of 256 big tiles + 64 small ones instead of a second round that 16 of the 256 CUs work on.
-  // JEN1_BGEMM_WM = 2 / 4 forces form (1) / (2), JEN1_BGEMM_T256 = 0 / 1 forbids / forces form (3) (tuning runs).
-  static const int force_wm = getenv("JEN1_BGEMM_WM") ? atoi(getenv("JEN1_BGEMM_WM")) : 0;
-  const char* e256 = getenv("JEN1_BGEMM_T256");      // (read per call: the parity tests switch it)
-  const int force_t256 = e256 ? atoi(e256) : -1;
   static const int n_cu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess) n = 0; return n > 0 ? n : 256; }();
-  const bool ok256 = a->dtype == JEN1_BF16 && !force_wm && force_t256 != 0 && (g.n_groups == 1 || (a->group_align >= 256 && a->group_align % 256 == 0));
-  int n_big = 0;                                        // columns [0, n_big) on the 256 x 256 form
-  if (ok256) {
-    const int tm = (a->M + 255) / 256, tn_all = (a->Ntot + 255) / 256;
-    if (force_t256 == 1) {
-      n_big = a->Ntot;
-    } else if (tm * tn_all >= (n_cu * 3) / 4 && a->K >= 512) {
-      // whole rounds of big tiles; the last round may stay if it is at least 3/4 full, and a remainder narrower than 256 columns rides along
-      const int rounds = (tm * tn_all) / n_cu, tail = tm * tn_all - rounds * n_cu;
-      int tn_big = tn_all;
-      if (tail > 0 && tail * 4 < n_cu * 3 && rounds >= 1) tn_big = (rounds * n_cu) / tm;
-      n_big = tn_big >= tn_all ? a->Ntot : tn_big * 256;
-      if (g.n_groups > 1 && n_big < a->Ntot && n_big % a->group_align != 0) n_big -= n_big % a->group_align;      // (cut on a group boundary multiple)
-    }
-  }
-  {
-    // the four-stage form (big_gemm_nt_s4_kernel<272>): column counts that are multiples of 272 when that tiling fills its rounds of one
-    // tile per CU better than 256-wide tiles (the stacked projection, M = 1024: 256 tiles = exactly one round against 272 = 1.06: 54 -> 47 us;
-    // the 256-wide instance of the same kernel measured slower than the two-stage 32 x 32 form everywhere and is not built).
-    // JEN1_BGEMM_S4 = 0: never; 272: whenever the shape allows (tuning / parity tests)
-    const char* es4 = getenv("JEN1_BGEMM_S4");
-    const int force_s4 = es4 ? atoi(es4) : -1;
-    if (a->dtype == JEN1_BF16 && !force_wm && force_s4 != 0 && force_t256 != 1 && a->K >= 32 && a->K % 32 == 0 && a->Ntot % 272 == 0 &&
-        (g.n_groups == 1 || (a->group_align >= 16 && a->group_align % 16 == 0))) {
-      const int tm = (a->M + 255) / 256;
-      const long long t272 = (long long)tm * (a->Ntot / 272), t256 = (long long)tm * ((a->Ntot + 255) / 256);
-      // rounds of one tile per CU x tile width: which tiling fills the chip better
-      const double c272 = (double)((t272 + n_cu - 1) / n_cu) * 272.0, c256 = (double)((t256 + n_cu - 1) / n_cu) * 256.0;
-      if (force_s4 == 272 || (t272 >= (n_cu * 3) / 4 && c272 < c256 && a->K >= 512)) {
-        BArgs gc = g;
-        gc.tiles_m = tm;
-        gc.tiles_n = a->Ntot / 272;
-        hipLaunchKernelGGL(big_gemm_nt_s4_kernel<272>, dim3(gc.tiles_m * gc.tiles_n), dim3(512), 0, s, gc);
-        JEN1_HIP(hipGetLastError());
-        return 0;
-      }
-    }
-  }
-  if (n_big > 0) {
-    BArgs gb = g;
-    gb.Ntot = n_big;
-    gb.tiles_m = (a->M + 255) / 256;
-    gb.tiles_n = (n_big + 255) / 256;
-    hipLaunchKernelGGL(big_gemm_nt256_kernel, dim3(gb.tiles_m * gb.tiles_n), dim3(512), 0, s, gb);
-    JEN1_HIP(hipGetLastError());
-    if (n_big >= a->Ntot) return 0;
-    g.n_begin = n_big;
-  }
-  const int n_rest = a->Ntot - g.n_begin;
-  const int t256 = ((a->M + 255) / 256) * ((n_rest + BN - 1) / BN);
-  const int wm = force_wm ? (force_wm == 5 ? 4 : force_wm) : ((t256 >= 512 && a->K >= 2048) ? 4 : 2);
-  g.tiles_m = (a->M + wm * 64 - 1) / (wm * 64);
-  g.tiles_n = (n_rest + BN - 1) / BN;
-  const dim3 grid(g.tiles_m * g.tiles_n);
-  if (wm == 4 && force_wm == 5) {                       // (tuning: 256 x 128 tiles on two stages)
-    hipLaunchKernelGGL((big_gemm_nt_kernel<bf16_t, 4, 2>), grid, dim3(512), 0, s, g);
-  } else if (wm == 4) {
-    if (a->dtype == JEN1_F32) hipLaunchKernelGGL((big_gemm_nt_kernel<float, 4, 3>), grid, dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((big_gemm_nt_kernel<bf16_t, 4, 3>), grid, dim3(512), 0, s, g);
+  const BRoute r = big_gemm_route(*a, n_cu, big_gemm_forces());
+  if (r.s272) {
+    launch_s4_272(g, s);
   } else {
-    if (a->dtype == JEN1_F32) hipLaunchKernelGGL((big_gemm_nt_kernel<float, 2, 2>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((big_gemm_nt_kernel<bf16_t, 2, 2>), grid, dim3(256), 0, s, g);
+    if (r.n_big > 0) {
+      launch_nt256(g, r.n_big, s);
+      JEN1_HIP(hipGetLastError());
+    }
+    if (r.n_big < a->Ntot) launch_nt(g, r.n_big, a->dtype, r.wm, s);
   }
   JEN1_HIP(hipGetLastError());
   return 0;
@@ -1367,6 +1265,17 @@ static int tn_splits(int tiles, int MT) {
   return splits;
 }
 
+// cut the reduction of a TN product (g.M rows, g.tiles_n x g.tiles_k output tiles) into slices and launch it; whole: one slice, as the
+// store form needs (every workgroup owns its output tile; no atomics, no zero-fill before)
+static void tn_launch(TArgs& g, bool whole, void* stream) {
+  const int tiles = g.tiles_n * g.tiles_k, MT = (g.M + 63) / 64;
+  const int splits = whole ? 1 : tn_splits(tiles, MT);
+  g.mt_per_split = (MT + splits - 1) / splits;
+  g.splits = (MT + g.mt_per_split - 1) / g.mt_per_split;
+  g.main_blocks = tiles * g.splits;
+  hipLaunchKernelGGL(big_gemm_tn_kernel, dim3(g.main_blocks + g.bias_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
+}
+
 static int big_gemm_tn_launch(const void* a, const void* b, float* c, int M, int N, int K, int lda, int ldb, int ldc, float alpha, int store, void* stream);
 extern "C" int jen1_big_gemm_tn(const void* a, const void* b, float* c, int M, int N, int K, int lda, int ldb, int ldc, float alpha, void* stream) {
   return big_gemm_tn_launch(a, b, c, M, N, K, lda, ldb, ldc, alpha, 0, stream);
@@ -1385,13 +1294,8 @@ static int big_gemm_tn_launch(const void* a, const void* b, float* c, int M, int
   g.a = a; g.b = b; g.c = c; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha;
   g.tiles_n = (N + 127) / 128;
   g.tiles_k = (K + 127) / 128;
-  const int tiles = g.tiles_n * g.tiles_k, MT = (M + 63) / 64;
-  const int splits = store ? 1 : tn_splits(tiles, MT);      // (store: every workgroup owns its output tile; no atomics, no zero-fill before)
   g.store = store;
-  g.mt_per_split = (MT + splits - 1) / splits;
-  g.splits = (MT + g.mt_per_split - 1) / g.mt_per_split;
-  g.main_blocks = tiles * g.splits;
-  hipLaunchKernelGGL(big_gemm_tn_kernel, dim3(g.main_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
+  tn_launch(g, store != 0, stream);
   JEN1_HIP(hipGetLastError());
   return 0;
 }
@@ -1417,18 +1321,13 @@ extern "C" int jen1_big_gemm_tn_conv(const void* dy, const void* x, float* gw, f
   g.tiles_n = (co + 127) / 128;
   g.cpt = taps > 1 ? 16 / taps : 16;
   g.tiles_k = taps > 1 ? ((ci + 7) / 8 + g.cpt - 1) / g.cpt : (ci + 127) / 128;
-  const int tiles = g.tiles_n * g.tiles_k, MT = (int)((M + 63) / 64);
-  int splits = tn_splits(tiles, MT);
-  g.mt_per_split = (MT + splits - 1) / splits;
-  g.splits = (MT + g.mt_per_split - 1) / g.mt_per_split;
-  g.main_blocks = tiles * g.splits;
   if (gb) {
     int nbk = (int)(M / 1536);
     nbk = nbk < 1 ? 1 : (nbk > 32 ? 32 : nbk);
     g.bias_rows = (int)((M + nbk - 1) / nbk);
     g.bias_blocks = (int)((M + g.bias_rows - 1) / g.bias_rows);
   }
-  hipLaunchKernelGGL(big_gemm_tn_kernel, dim3(g.main_blocks + g.bias_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
+  tn_launch(g, false, stream);
   JEN1_HIP(hipGetLastError());
   return 0;
 }

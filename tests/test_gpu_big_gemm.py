@@ -474,3 +474,94 @@ def test_stacked_projection_on_the_272_column_tiles(monkeypatch, force):
         got = cache[:, :NL].reshape(B * NL, wd).float()
         assert float((got - ref).abs().max() / ref.abs().max()) < 1e-2, (n0, wd)
         assert bool((cache[:, NL] == -3.0).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the 256 x 128 tile / three-stage forms (big_gemm_nt_kernel<float | bf16, 4, 3>): chosen only for >= 512 such tiles at K >= 2048, or by
+# JEN1_BGEMM_WM=4, which the library reads once per process -- so the cases run in a child process that has it set from the start
+# ---------------------------------------------------------------------------------------------------------------------
+WM4_LIMIT_S = 120
+
+
+def _wm4_cases():
+    """every case against a float64 product of the same (rounded) operands, the metric and the tolerances of the tests above; prints each
+    figure, returns the failures"""
+    bad = []
+
+    def judge(name, got, ref, tol):
+        err = float((got.double() - ref).abs().max() / ref.abs().max())
+        print(f"{name}: {err:.3e} (tol {tol:g})", flush=True)
+        if not err < tol:
+            bad.append(f"{name}: {err:.3e} >= {tol:g}")
+
+    # 1, 2, 3 and 5 K steps (prologue, first refill, wrap of the three stages); ragged M below and above one 256-row tile
+    for dtype, Ks in (("bf16", (64, 128, 192, 320)), ("f32", (32, 64, 96, 160))):
+        td = torch.float32 if dtype == "f32" else torch.bfloat16
+        tol = 1e-5 if dtype == "f32" else 1e-2
+        for K in Ks:
+            for M, N in ((1, 128), (257, 384), (300, 256)):
+                gen = torch.Generator(device="cuda").manual_seed(M * 7 + N + K)
+                a = (torch.randn((M, K), device="cuda", generator=gen) * 0.5).to(td)
+                b = (torch.randn((N, K), device="cuda", generator=gen) * 0.5).to(td)
+                guard = torch.full((M + 3, N), 7.0, device="cuda", dtype=td)          # rows past M must stay untouched
+                c = guard[:M]
+                _run(a, b, [(c, None, 0, N)], dtype=dtype)
+                judge(f"plain/{dtype}/M{M}/N{N}/K{K}", c, a.double() @ b.double().t(), tol)
+                if not bool((guard[M:] == 7.0).all()):
+                    bad.append(f"plain/{dtype}/M{M}/N{N}/K{K}: rows past M were written")
+        # 3 groups of 128 columns, row map into [B][129] caches, row scale, bias
+        B, NL, K, widths = 3, 128, 192, [128, 128, 128]
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        xs = torch.randn((B * NL, K), device="cuda", generator=gen).to(td)
+        w = (torch.randn((sum(widths), K), device="cuda", generator=gen) * 0.05).to(td)
+        mask_b = (torch.rand((B, NL + 1), device="cuda", generator=gen) > 0.3).float()       # indexed by the OUTPUT row: [B][129]
+        mask = mask_b[:, :NL].reshape(-1)
+        outs, groups, n0 = [], [], 0
+        for wd in widths:
+            cache = torch.full((B, NL + 1, wd), -3.0, device="cuda", dtype=td)
+            bias = torch.randn((wd,), device="cuda", generator=gen)
+            outs.append((cache, bias, n0, wd))
+            groups.append((cache.view(B * (NL + 1), wd), bias, n0, wd))
+            n0 += wd
+        _run(xs, w, groups, row_scale=mask_b, rows_in=NL, rows_out=NL + 1, dtype=dtype)
+        for cache, bias, n0, wd in outs:
+            ref = (xs.double() @ w[n0:n0 + wd].double().t() + bias.double()[None]) * mask.double()[:, None]
+            judge(f"grouped/{dtype}/n0={n0}", cache[:, :NL].reshape(B * NL, wd), ref, tol)
+            if not bool((cache[:, NL] == -3.0).all()):
+                bad.append(f"grouped/{dtype}/n0={n0}: the 129th row was written")
+    # accumulate, alpha, float32 output
+    M, N, K = 300, 256, 128
+    gen = torch.Generator(device="cuda").manual_seed(9)
+    a = torch.randn((M, K), device="cuda", generator=gen).to(torch.bfloat16)
+    b = torch.randn((N, K), device="cuda", generator=gen).to(torch.bfloat16)
+    c = torch.randn((M, N), device="cuda", generator=gen)
+    c0 = c.clone()
+    _run(a, b, [(c, None, 0, N)], c_f32=True, accumulate=True, alpha=0.25)
+    judge("accumulate/alpha/f32-out", c, c0.double() + 0.25 * (a.double() @ b.double().t()), 1e-5)
+    return bad
+
+
+def test_three_stage_256x128_forms_forced_match_float64():
+    """JEN1_BGEMM_WM=4 from the start of a child process: big_gemm_nt_kernel<T, 4, 3> in both dtypes on 1, 2, 3 and 5 K steps, ragged M,
+    column groups with row map, row scale and bias, and the accumulating float32-output epilogue (_wm4_cases)"""
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env["JEN1_BGEMM_WM"] = "4"
+    env["PYTHONPATH"] = os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(L.__file__))), os.path.dirname(os.path.abspath(__file__))]
+                                        + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=WM4_LIMIT_S, env=env)
+    except subprocess.TimeoutExpired as e:
+        pytest.fail(f"the JEN1_BGEMM_WM=4 child did not finish within {WM4_LIMIT_S} s (killed):\n{(e.stdout or b'')[-2000:]}\n{(e.stderr or b'')[-4000:]}")
+    assert r.returncode == 0 and "WM4 OK" in r.stdout, f"exit code {r.returncode}\n--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-4000:]}"
+
+
+if __name__ == "__main__":          # the child of the test above
+    import os
+    import sys
+    assert os.environ.get("JEN1_BGEMM_WM") == "4"
+    failures = _wm4_cases()
+    print("WM4 OK" if not failures else "WM4 FAILED\n" + "\n".join(failures), flush=True)
+    sys.exit(1 if failures else 0)
