@@ -1177,6 +1177,11 @@ class OpBuilder:
             if cfg is None:
                 cfg = self.pick_cfg(a.B, a.L_out, M)
         BM, BN, tb, nb, wgs = tiles(cfg)
+        if force is not None and ("tb" in force or "nb" in force):
+            # the tests' knob: a tile geometry the heuristics would not pick (jen1_conv_gemm's own validation decides whether it is legal)
+            tb = force.get("tb", tb)
+            nb = force.get("nb", max(1, min(a.B, BN // tb)))
+            wgs = -(-a.L_out // tb) * -(-a.B // nb) * -(-M // BM)
         if cfg in self.TILE_CFGS:
             a.cfg, a.tb, a.nb, a.splitk, a.kc_stage = cfg, tb, 1, 1, 1
             return
@@ -1201,12 +1206,13 @@ class OpBuilder:
         # LDS stage: the whole K range of the workgroup in one stage whenever it fits (a second stage
         # costs a barrier and a global round trip); wide tiles stay <= 64 KiB to keep 2 WGs per CU
         limit = 64 * 1024 if cfg in (L.CFG_W64x64, L.CFG_W128x64) else 150 * 1024
-        stage = cps
+        forced_stage = force.get("kc_stage") if force is not None else None      # (the tests' knob, like tb / nb above)
+        stage = forced_stage or cps
         while True:
             a.kc_stage = stage
             ok_boundary = (not a.c1) or ((a.c0 // 32) % min(stage, cps) == 0)
             nbytes = lib.jen1_conv_gemm_lds_bytes(C.byref(a))
-            if ok_boundary and (nbytes <= limit or stage == 1):
+            if forced_stage or (ok_boundary and (nbytes <= limit or stage == 1)):
                 break
             stage -= 1
         assert nbytes <= 160 * 1024, f"LDS {nbytes} B too large (tb={tb}, nb={nb}, taps={a.taps}, stride={a.stride})"

@@ -5,7 +5,9 @@ Python; importable without a GPU (tests/test_persistent_phases_host.py pins all 
 A case is a program of ONE phase on operands that exist before the launch; an operand listed in the case's ``live`` is produced by a
 plain 1x1 conv phase in front instead (from a 32-channel tensor ``z.<operand>``), so the phase under test polls it.  Every reference is
 written the way the model writes the operation (reference blocks.py:34-53, :69-95, :137-145, :219-231, :355-380), on channel-last tensors,
-in float64, on operands rounded to the launch dtype.
+in float64, on operands rounded to the launch dtype.  ``prologue_ref`` / ``conv_phase_ref`` are also the references of the one-launch
+conv GEMM's suite (tests/conv_gemm_common.py): what that contract has more -- a LayerNorm or SiLU-only prologue, a padded last GroupNorm
+group, ``row_scale`` -- are keywords whose defaults leave the phases' results as they were, bit for bit.
 
 The ``wrong`` keyword of a reference selects one mistake these kernels can plausibly make; the host tests require that on the committed
 inputs every applicable one is at least ``POWER`` times the GPU tolerance away from the right answer in the GPU test's own metric.
@@ -34,19 +36,40 @@ def ceil_to(a, b):
 
 
 # ====================================================================================================== conv / linear phase
-def prologue_ref(x0, x1, *, src1_scale=1.0, groups=0, eps=1e-5, p1=None, p2=None, rows=None, silu=False, wrong=None):
+def prologue_ref(x0, x1, *, src1_scale=1.0, groups=0, eps=1e-5, p1=None, p2=None, rows=None, silu=False, wrong=None, creal=None, ln=None,
+                 pad_row=False):
     """[x0, x1 * src1_scale] -> GroupNorm over the concat (``groups`` > 0) with the affine  xhat * p1 + p2  -> SiLU.  p1 / p2: [C]
     (gamma / beta) or the fused GroupNorm-FiLM table's halves [rows][C] with ``rows`` [B] the table row of every batch element.
+    creal: the real channels of a tensor padded to C columns (zeros) -- a group is creal / groups channels, the last one also takes the
+    padding columns, every group counts creal / groups channels.  ln = (ln_C, gamma or None, beta or None, eps): LayerNorm of every row
+    over its first ln_C columns instead (groups = 0; gamma = None: standardise only).  groups = 0 without ln: SiLU only, or nothing.
+    pad_row: the image of an all-zero row under the same prologue is appended as row L (conv_phase_ref's ``pad_row``).
     wrong: "stats_next_element" (the statistics of element b also cover element b + 1), "scale_after_norm" (src1_scale applied to the
-    normalised values instead of the raw ones), "film_row0" (everybody takes element 0's table row)."""
+    normalised values instead of the raw ones), "film_row0" (everybody takes element 0's table row), "pad_group_count" (the last group
+    of a padded tensor divides by the channels it covers, padding included)."""
     scale_first = wrong != "scale_after_norm"
     x = x0.double() if x1 is None else torch.cat([x0.double(), x1.double() * (src1_scale if scale_first else 1.0)], -1)
+    xin = torch.cat([x, torch.zeros_like(x[:, :1])], 1) if pad_row else x           # the rows to transform (statistics: the real ones)
     if groups:
         B, Ln, C = x.shape
-        xg = x.reshape(B, Ln, groups, C // groups)
-        sg = torch.cat([xg, xg.roll(-1, 0)], 1) if wrong == "stats_next_element" else xg
-        mean, var = sg.mean(dim=(1, 3), keepdim=True), sg.var(dim=(1, 3), unbiased=False, keepdim=True)
-        x = ((xg - mean) / torch.sqrt(var + eps)).reshape(B, Ln, C)
+        if creal is not None and creal != C:
+            cpg = creal // groups
+            gi = (torch.arange(C) // cpg).clamp(max=groups - 1)
+            oh = F.one_hot(gi, groups).double()
+            n = torch.full((groups,), float(cpg * Ln), dtype=torch.float64)
+            if wrong == "pad_group_count":
+                n[-1] = float((C - (groups - 1) * cpg) * Ln)
+            s1, s2 = x.sum(1) @ oh, (x * x).sum(1) @ oh
+            if wrong == "stats_next_element":
+                s1, s2, n = s1 + s1.roll(-1, 0), s2 + s2.roll(-1, 0), 2 * n
+            mean = s1 / n
+            var = s2 / n - mean * mean
+            x = (xin - mean[:, None, gi]) / torch.sqrt(var[:, None, gi] + eps)
+        else:
+            xg = x.reshape(B, Ln, groups, C // groups)
+            sg = torch.cat([xg, xg.roll(-1, 0)], 1) if wrong == "stats_next_element" else xg
+            mean, var = sg.mean(dim=(1, 3), keepdim=True), sg.var(dim=(1, 3), unbiased=False, keepdim=True)
+            x = ((xin.reshape(B, -1, groups, C // groups) - mean) / torch.sqrt(var + eps)).reshape(B, -1, C)
         if not scale_first and x1 is not None:
             x = torch.cat([x[..., : x0.shape[-1]], x[..., x0.shape[-1]:] * src1_scale], -1)
         if p1.dim() == 1:
@@ -54,37 +77,59 @@ def prologue_ref(x0, x1, *, src1_scale=1.0, groups=0, eps=1e-5, p1=None, p2=None
         else:
             r = rows.long() if wrong != "film_row0" else rows.long()[:1].expand(B)
             x = x * p1.double()[r][:, None, :] + p2.double()[r][:, None, :]
+    elif ln is not None:
+        ln_C, g_, b_, leps = ln
+        xs = xin[..., :ln_C]
+        x = (xin - xs.mean(-1, keepdim=True)) / torch.sqrt(xs.var(-1, unbiased=False, keepdim=True) + leps)
+        if g_ is not None:
+            x = x * g_.double() + b_.double()
+    else:
+        x = xin
     return F.silu(x) if silu else x
 
 
-def _rows_at(x, idx, wrong):
-    """rows ``idx`` [L_out] of every batch element of x [B][L][C], zero outside [0, L).  wrong "halo_read": a row outside the batch
-    element is whatever lies there in the flat [B L][C] tensor -- the neighbouring batch element's row"""
+def _rows_at(x, idx, wrong, pad=None):
+    """rows ``idx`` [L_out] of every batch element of x [B][L][C], zero outside [0, L) -- ``pad`` [B][1][C] there when given.
+    wrong "halo_read": a row outside the batch element is whatever lies there in the flat [B L][C] tensor -- the neighbouring batch
+    element's row"""
     B, Ln, C = x.shape
     if wrong == "halo_read":
         flat = (torch.arange(B)[:, None] * Ln + idx[None, :]) % (B * Ln)
         return x.reshape(B * Ln, C)[flat]
     ok = (idx >= 0) & (idx < Ln)
-    return x[:, idx.clamp(0, Ln - 1)] * ok[None, :, None]
+    v = x[:, idx.clamp(0, Ln - 1)] * ok[None, :, None]
+    return v if pad is None else v + pad * (~ok)[None, :, None]
 
 
 def conv_phase_ref(x, extras, W, bias, *, taps=1, stride=1, pad_left=0, L_out, edge_bias=None, m_split=0, k_split=0, act=L.ACT_NONE,
-                   residual=None, out_C=None, ps_f=1, ps_off=0, L_y=None, y_row0=0, out_L=None, wrong=None):
+                   residual=None, out_C=None, ps_f=1, ps_off=0, L_y=None, y_row0=0, out_L=None, wrong=None, pad_row=None, row_scale=None,
+                   tb=None, k_tail=None):
     """One GEMM phase behind its prologue.  x: [B][L_in][cmain] float64 (``prologue_ref``); extras: [(tensor [B][L_in][ce], row shift)] raw
     K segments behind the taps; W: [M][taps cmain + sum ce] in K order (tap, channel), then the extras; GEMM column t reads input row
     t stride + tap - pad_left (extras: t stride + shift), zeros outside [0, L_in).  GEMM row m = ph out_C + co lands on output row
     y_row0 + t ps_f + ph - ps_off (when that is in [0, L_y)), column co: the sub-pixel form of ConvTranspose1d.  bias: [out_C], or [M]
     beside edge_bias [2][M] that replaces it in column 0 / L_out - 1.  Rows < m_split sum only the first k_split 32-channel chunks and
-    take the residual, rows >= m_split take ``act`` (m_split = 0: all rows take both).
-    Returns [B][out_L][out_C] float64, NaN where the phase writes nothing.
-    wrong: "halo_read", "edge_swapped", "k_split_ignored", "ps_off_ignored"."""
+    take the residual, rows >= m_split take ``act`` (m_split = 0: all rows take both).  row_scale [B][out_L] multiplies the finished
+    row, after the residual.  Returns [B][out_L][out_C] float64, NaN where the phase writes nothing.
+    wrong: "halo_read", "edge_swapped", "k_split_ignored", "ps_off_ignored"; "pad_before_prologue" (the rows outside [0, L_in) of the
+    taps are ``pad_row`` [B][1][cmain], the prologue's image of a zero row, instead of zeros); "edge_tap_dropped" (a tap or extra segment
+    is left out of a whole position tile of ``tb`` GEMM columns when it is dead for the tile's FIRST column); "k_tail_dropped" (the K
+    columns ``k_tail`` are left out); "residual_after_mask" (row_scale * act(...) + residual); "gelu_tanh" (tanh GELU); "stats_with_cropped"
+    (no crop: every GEMM column is kept, as [B][L_out ps_f][out_C] -- what statistics that ignore the crop would sum)."""
     B = x.shape[0]
     M = W.shape[0]
     out_C = out_C or M
     t = torch.arange(L_out)
-    cols = [_rows_at(x, t * stride + k - pad_left, wrong) for k in range(taps)]
+    pad = pad_row if wrong == "pad_before_prologue" else None
+    cols = [_rows_at(x, t * stride + k - pad_left, wrong, pad) for k in range(taps)]
     cols += [_rows_at(e.double(), t * stride + sh, wrong) for e, sh in extras]
+    if wrong == "edge_tap_dropped":
+        t0 = t // tb * tb
+        shifts = [k - pad_left for k in range(taps)] + [sh for _, sh in extras]
+        cols = [c_ * (t0 * stride + sh >= 0)[None, :, None] for c_, sh in zip(cols, shifts)]
     X = torch.cat(cols, -1)                                                    # [B][L_out][K]
+    if wrong == "k_tail_dropped":
+        X[..., k_tail] = 0.0
     W = W.double()
     y = X @ W.T
     if m_split and wrong != "k_split_ignored":
@@ -99,7 +144,12 @@ def conv_phase_ref(x, extras, W, bias, *, taps=1, stride=1, pad_left=0, L_out, e
     elif bias is not None:
         y = y + bias.double()[co]
     if act == L.ACT_GELU:
-        y = torch.cat([y[..., :m_split], gelu(y[..., m_split:])], -1)
+        hi = y[..., m_split:]
+        hi = 0.5 * hi * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (hi + 0.044715 * hi ** 3))) if wrong == "gelu_tanh" else gelu(hi)
+        y = torch.cat([y[..., :m_split], hi], -1)
+    if wrong == "stats_with_cropped":
+        assert residual is None and row_scale is None
+        return y.reshape(B, L_out * ps_f, out_C)
     L_y = L_y if L_y is not None else L_out * ps_f
     out_L = out_L if out_L is not None else y_row0 + L_y
     out = torch.full((B, out_L, out_C), float("nan"), dtype=torch.float64)
@@ -108,12 +158,16 @@ def conv_phase_ref(x, extras, W, bias, *, taps=1, stride=1, pad_left=0, L_out, e
         ty = t * ps_f + ph - off
         ok = (ty >= 0) & (ty < L_y)
         out[:, y_row0 + ty[ok]] = y[:, ok, ph * out_C: (ph + 1) * out_C]
+    if row_scale is not None and wrong == "residual_after_mask":
+        out = out * row_scale.double()[..., None]
     if residual is not None:
         r = residual.double()
         if m_split:
             out[..., :m_split] += r[..., :m_split]
         else:
             out = out + r
+    if row_scale is not None and wrong != "residual_after_mask":
+        out = out * row_scale.double()[..., None]
     return out
 
 
