@@ -573,6 +573,32 @@ int jen1_gain_apply(const float* x, float* y, float* gain, const double* lufs, c
                     int C, int64_t L, int strategy, int limit, double headroom_db, double energy_floor, void* stream);
 
 /*
+ * Whitening of the codec latents (csrc/latent_norm.hip, jen1_amd/normalizer.py; the reference has only an empty stub): the moments a
+ * whitening transform is fitted from, and the affine map that applies it or its inverse.  C: a multiple of 16 in 16..128; B, T >= 1.
+ * Both calls check their arguments before anything is launched, run on ``stream`` and allocate nothing: capturable.
+ *
+ * jen1_latent_moments: z [B][C][T] float32 contiguous.  ADDS to state [1 + C + C C] float64 on the device:
+ *     state[0] += n, the frames counted;   state[1 + c] += sum z[b][c][t];   state[1 + C + c C + d] += sum z[b][c][t] z[b][d][t]
+ *   over the frames t < lengths[b] of every row (all T frames when lengths is NULL).  lengths: HOST pointer to B int32, each in 0..T,
+ *   read during the call (they ride to the device in launch arguments: no copy, no synchronisation).
+ *   Float64 from the first product on (a product of two float32 values is exact in float64; the only rounding is in the sums).  A
+ *   workgroup forms the products of a run of 128 frames of one row on v_mfma_f64_16x16x4_f64 and writes one float64 partial; a second
+ *   launch adds the partials to the state in ascending order.  No atomics, every sum in one fixed order: bit-reproducible.  Only the
+ *   16 x 16 tiles on or above the diagonal are formed and element (c, d), c > d, is the sum of (d, c): the matrix is symmetric bit
+ *   for bit.  workspace: DEVICE scratch, 8-byte aligned, of at least jen1_latent_moments_workspace(B, C, T) bytes (0 for arguments
+ *   the call would refuse); its contents before and after the call mean nothing.
+ *
+ * jen1_latent_affine: y[b][:][t] = A (z[b][:][t] - pre) + post.  z, y [B][C][T] float32; A [C][C] float32 row-major; pre, post [C]
+ *   float32 or NULL (zero).  Forward: A = W, pre = mean.  Inverse: A = W^-1, post = mean.  v_mfma_f32_16x16x4_f32: every output is
+ *   the float32 fmaf chain over k = 0 .. C - 1 from 0, on (z - pre) rounded once, plus post.  y == z is allowed: a workgroup reads
+ *   all C channels of its 64 frames before it writes any, and no other workgroup touches them.  A = I without pre / post returns z.
+ */
+int64_t jen1_latent_moments_workspace(int B, int C, int T);
+int jen1_latent_moments(const float* z, const int32_t* lengths /* HOST */, double* state, void* workspace, int64_t workspace_bytes,
+                        int B, int C, int T, void* stream);
+int jen1_latent_affine(const float* z, float* y, const float* A, const float* pre, const float* post, int B, int C, int T, void* stream);
+
+/*
  * Long-form sampling on overlapping windows (csrc/windows.hip, jen1_amd/windows.py; not in the reference).  The latents of a piece
  * live on a canvas [n][C][L] (float32); the sampler's batch rows [n W][C][T] are W windows of T frames per piece, row s W + j = window
  * j of piece s, which starts at canvas frame offsets[j].  offsets: DEVICE int32 [W], ascending, 0 <= offsets[j] <= L - T; that every

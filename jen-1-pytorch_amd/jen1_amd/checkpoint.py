@@ -8,6 +8,7 @@ after loading, the HIP engine repacks its weights on next use.
 
 With an EMA of the weights (jen1_amd/ema.py) the file carries one more key, ``'ema'``: the EMA weights under the same key schema.
 The reference's loader reads only ``model`` / ``optimizer`` / ``epoch`` / ``learning_rate``, so such files still load there.
+A latent ``Normalizer`` (jen1_amd/normalizer.py) is one more key of the same kind, ``'normalizer'``: its ``state_dict()``.
 """
 from __future__ import annotations
 
@@ -22,24 +23,28 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") else model
 
 
-def save_checkpoint(model, optimizer, lr, iteration, checkpoint_path, logger=None, ema=None) -> None:
+def save_checkpoint(model, optimizer, lr, iteration, checkpoint_path, logger=None, ema=None, normalizer=None) -> None:
     """script_util.py:79-90 (without the old-checkpoint cleanup, which is run management, not format).  ``ema``: a ``ParamEMA`` over the
-    model's parameters, saved under ``'ema'`` (its ``state_dict()``); the other keys are unchanged."""
+    model's parameters, saved under ``'ema'`` (its ``state_dict()``); ``normalizer``: the latent ``Normalizer`` the model was trained behind,
+    saved under ``'normalizer'``; the other keys are unchanged."""
     if logger is not None:
         logger.info(f"Saving model and optimizer state at iteration {iteration} to {checkpoint_path}")
     ck = {"model": _unwrap(model).state_dict(), "epoch": iteration,
           "optimizer": optimizer.state_dict() if optimizer is not None else None, "learning_rate": lr}
     if ema is not None:
         ck["ema"] = ema.state_dict(_unwrap(model))
+    if normalizer is not None:
+        ck["normalizer"] = normalizer.state_dict()
     torch.save(ck, checkpoint_path)
 
 
-def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None, ema=None, weights: str = "model"):
+def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None, ema=None, weights: str = "model", normalizer=None):
     """script_util.py:93-124: returns (model, optimizer, learning_rate, epoch).
 
     ``ema``: a ``ParamEMA`` over the model's parameters, restored from the file's ``'ema'`` entry; a file without one (a checkpoint of the
     reference, or of a run without EMA) seeds it from the weights loaded into the model.  ``weights="ema"`` loads the file's EMA weights into
-    the model instead of ``'model'`` (sampling from the EMA); the file must have them."""
+    the model instead of ``'model'`` (sampling from the EMA); the file must have them.  ``normalizer``: a ``Normalizer``, restored from the
+    file's ``'normalizer'`` entry; a file without one leaves it untouched, which is logged."""
     if weights not in ("model", "ema"):
         raise ValueError(f"weights must be 'model' or 'ema', not {weights!r}")
     assert os.path.isfile(checkpoint_path)
@@ -69,9 +74,28 @@ def load_checkpoint(checkpoint_path, model, logger=None, optimizer=None, ema=Non
         else:
             ema.load_state_dict(m.state_dict(), model=m)
             (logger or logging.getLogger(__name__)).info(f"{checkpoint_path} has no EMA weights: the EMA starts from the loaded '{weights}' weights")
+    if normalizer is not None:
+        if ck.get("normalizer") is not None:
+            normalizer.load_state_dict(ck["normalizer"])
+        else:
+            (logger or logging.getLogger(__name__)).info(f"{checkpoint_path} has no latent normalizer: the one passed in is left as it is")
     if logger is not None:
         logger.info(f"Loaded checkpoint '{checkpoint_path}' (epoch {epoch})")
     return model, optimizer, learning_rate, epoch
+
+
+def load_normalizer(checkpoint_path):
+    """the ``Normalizer`` saved in the file's ``'normalizer'`` entry, or None for a file without one (``Jen1`` builds its normalizer from
+    this when none is passed in).  The file is mapped, not read: only the entry's own tensors are touched."""
+    assert os.path.isfile(checkpoint_path)
+    try:
+        ck = torch.load(checkpoint_path, map_location="cpu", weights_only=False, mmap=True)
+    except (RuntimeError, ValueError):             # (a file in the legacy, non-zip format cannot be mapped)
+        ck = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    if ck.get("normalizer") is None:
+        return None
+    from .normalizer import Normalizer
+    return Normalizer.from_state_dict(ck["normalizer"])
 
 
 def load_model_diffsize(checkpoint_path, model):

@@ -115,10 +115,14 @@ class LatentCollate:
     one rate stack), every clip is trimmed or zero-padded to exactly ``sample_duration * sample_rate`` samples, and the batch is encoded by
     one ``audio_encoder.encode_latents`` call.  ``normalize`` / ``target_lufs`` (not in the reference): a strategy of
     ``jen1_amd.audio.normalize_audio`` applied with ``limit="clip"`` to the padded, converted batch in front of the encoder, so that clips
-    reach it at one level and not at whatever level their files have; None feeds them as they are."""
+    reach it at one level and not at whatever level their files have; None feeds them as they are.  ``normalizer`` (not in the reference
+    beyond its empty stub): a fitted ``jen1_amd.normalizer.Normalizer``; the batch's latents go through its ``normalize`` behind
+    ``encode_latents``, so the trainer sees whitened latents.  ``with_lengths`` (for FITTING one, ``Normalizer.fit``): the batch carries a
+    third entry, the valid latent frames of every clip -- its own sample count behind the conversion, mapped to frames -- so that the
+    zero padding of short clips stays out of the statistics."""
 
     def __init__(self, audio_encoder, device="cuda", sample_duration=10, convert_audio: Optional[Callable] = None,
-                 normalize: Optional[str] = None, target_lufs=-14.0):
+                 normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None, with_lengths: bool = False):
         self.audio_encoder, self.device, self.sample_duration = audio_encoder, device, sample_duration
         self._convert = convert_audio
         if normalize is not None:
@@ -126,6 +130,15 @@ class LatentCollate:
             if normalize not in audio.STRATEGIES:
                 raise ValueError(f"unknown normalize {normalize!r}: None or one of {audio.STRATEGIES}")
         self.normalize, self.target_lufs = normalize, target_lufs
+        self.normalizer, self.with_lengths = normalizer, bool(with_lengths)
+
+    def valid_frames(self, n_valid: int, n_out: int, frames: int) -> int:
+        """the latent frames that hold audio of a clip of ``n_valid`` samples padded to ``n_out``: the frames the encoder gives the clip
+        alone (its segments start where the padded clip's do), or the clip's share of ``frames``, rounded up, without that query"""
+        n_valid = max(0, min(int(n_valid), n_out))
+        count = getattr(self.audio_encoder, "segment_frames", None)
+        t = sum(count(n_valid)) if count is not None and n_valid > 0 else -(-n_valid * frames // n_out)
+        return max(0, min(int(t), frames))
 
     def convert_audio(self, wav, sr, target_sr, target_channels):
         if self._convert is not None:
@@ -151,6 +164,7 @@ class LatentCollate:
         n_out = int(self.sample_duration * rate)
         out = torch.zeros((len(batch), channels, n_out), dtype=torch.float32, device=self.device)
         by_rate = {}
+        valid = [0] * len(batch)
         for i, (_chunk, sr, _meta) in enumerate(batch):
             by_rate.setdefault(int(sr), []).append(i)
         for sr, idx in by_rate.items():
@@ -162,11 +176,17 @@ class LatentCollate:
             conv = self.convert_audio(group.to(self.device), sr, rate, channels)
             n = min(n_out, conv.shape[-1])
             out[idx, :, :n] = conv[:, :, :n].to(self.device, torch.float32)
+            for i, c in zip(idx, clips):
+                valid[i] = min(n, -(-c.shape[-1] * rate // sr))
         if self.normalize is not None:             # the level of every clip, set in one call on the padded batch (not in the reference)
             from . import audio
             out = audio.normalize_audio(out, rate, strategy=self.normalize, target_lufs=self.target_lufs, limit="clip", device=self.device)
         emb = ae.encode_latents(out)[0]
-        return emb, [meta for _chunk, _sr, meta in batch]
+        meta = [meta for _chunk, _sr, meta in batch]
+        lengths = [self.valid_frames(v, n_out, emb.shape[-1]) for v in valid] if self.with_lengths else None
+        if self.normalizer is not None:
+            emb = self.normalizer.normalize(emb)
+        return (emb, meta) if lengths is None else (emb, meta, lengths)
 
 
 class LatentLoader:
@@ -186,12 +206,13 @@ class LatentLoader:
 
 def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sample_duration, aug_shift, batch_size: int = 50, shuffle: bool = True,
                     split_ratio=0.8, device="cpu", durations_path=None, cumsum_path=None, audio_file_txt_path=None, *, audio_encoder=None,
-                    num_workers: int = 0, dataset_cls=None, normalize: Optional[str] = None, target_lufs=-14.0):
+                    num_workers: int = 0, dataset_cls=None, normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None,
+                    with_lengths: bool = False):
     """(train loader, validation loader) of ``(emb, metadata)`` batches.  ``dataset_dir``: one folder (split by ``split_ratio``) or a
     (train, validation) pair.  ``audio_encoder`` (an ``EncodecHIP``) installs ``LatentCollate`` on ``device``; without it the loaders yield
     the raw item lists.  ``num_workers`` > 0 reads the files in spawned worker processes, which never touch the GPU.  ``dataset_cls``: a
     ``MusicDataset`` subclass to build instead (one that selects or tags items; importable by name when workers are used).  ``normalize`` /
-    ``target_lufs`` are handed to ``LatentCollate``."""
+    ``target_lufs``, ``normalizer`` and ``with_lengths`` are handed to ``LatentCollate``."""
     cls = MusicDataset if dataset_cls is None else dataset_cls
 
     def make(folder):
@@ -204,7 +225,8 @@ def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sampl
         train_dataset, val_dataset = random_split(dataset, [train_size, len(dataset) - train_size])
     else:
         train_dataset, val_dataset = make(dataset_dir[0]), make(dataset_dir[1])
-    fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs)
+    fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs,
+                                                             normalizer=normalizer, with_lengths=with_lengths)
     kw = dict(batch_size=batch_size, collate_fn=collate, drop_last=True, num_workers=num_workers)
     if num_workers > 0:
         kw["multiprocessing_context"] = "spawn"        # never fork a process that has initialised the GPU

@@ -45,7 +45,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .checkpoint import load_checkpoint
+from .checkpoint import load_checkpoint, load_normalizer
 from .config import GDMConfig, VDMConfig, full_model_config
 from .diffusion import GaussianDiffusion, get_beta_schedule
 from .model import UNetCFG1d
@@ -74,18 +74,22 @@ class Jen1:
                  input_concat_ids: Sequence[str] = ("masked_input", "mask"), *, audio_encoder, conditioner: Callable,
                  convert_audio: Optional[Callable] = None, model_config: Optional[dict] = None,
                  diffusion_config: Optional[GDMConfig] = None, compute_dtype: str = "bf16", vdm_config: Optional[VDMConfig] = None,
-                 weights: str = "model", latents: str = "codes"):
+                 weights: str = "model", latents: str = "codes", normalizer=None):
         """``weights="ema"`` (keyword-only, not in the reference): sample from the checkpoint's EMA weights (``checkpoint.load_checkpoint``).
         ``latents`` (keyword-only, not in the reference): ``"codes"`` builds the known latents as generation.py:145-150 does, ``encode`` then
         ``quantizer.decode`` of the concatenated codes; ``"fused"`` asks ``audio_encoder.encode_latents`` for them (jen1_amd.encodec.EncodecHIP:
-        the residual search writes the latents itself)."""
+        the residual search writes the latents itself).
+        ``normalizer`` (keyword-only; the reference has only an empty stub): the ``jen1_amd.normalizer.Normalizer`` the model was trained
+        behind.  None: the one saved in the checkpoint's ``'normalizer'`` entry when the file has one, else no normalisation.  With one,
+        the known latents are normalised right behind ``get_emb`` and the sampler's result is denormalised right in front of the decoder:
+        masks, ``preserve_known``, windows and the samplers work in the normalised space, as training does."""
         if weights not in ("model", "ema"):
             raise ValueError(f"weights must be 'model' or 'ema', not {weights!r}")
         if latents not in ("codes", "fused"):
             raise ValueError(f"latents must be 'codes' or 'fused', not {latents!r}")
         if latents == "fused" and not hasattr(audio_encoder, "encode_latents"):
             raise ValueError("latents='fused' needs an audio_encoder with encode_latents (jen1_amd.encodec.EncodecHIP)")
-        self.latents = latents
+        self.latents, self.normalizer = latents, normalizer
         self.ckpt_path, self.device, self.sample_rate, self.weights = ckpt_path, device, sample_rate, weights
         self.conditioner, self.audio_encoder = conditioner, audio_encoder
         self.cross_attn_cond_ids, self.global_cond_ids, self.input_concat_ids = cross_attn_cond_ids, global_cond_ids, input_concat_ids
@@ -127,6 +131,8 @@ class Jen1:
                               compute_dtype=self.compute_dtype, device=self.device, **cfg)
             if self.ckpt_path is not None:
                 model, _, _, _ = load_checkpoint(self.ckpt_path, model, weights=self.weights)
+                if self.normalizer is None:
+                    self.normalizer = load_normalizer(self.ckpt_path)
             self._model = model.eval()
         return diffusion, self._model
 
@@ -370,12 +376,16 @@ class Jen1:
             known = known.to(self.device)
         else:
             known = self.get_emb(wav.to(self.device)).to(self.device)           # [B, 128, T']
+        if self.normalizer is not None:    # from here to the decoder everything lives in the normalised space, as in training
+            known = self.normalizer.normalize(known.to(torch.float32))
         keep = torch.nn.functional.interpolate(keep.to(self.device), size=known.shape[2])
         if windows is not None:
             z = self._sample_windows(diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler,
                                      wav.shape[-1], *windows)
         else:
             z = self._sample_plain(diffusion, model, prompt, known, keep, causal, seed_with_audio, steps, preserve_known, sampler, metadata)
+        if self.normalizer is not None:
+            z = self.normalizer.denormalize(z.to(torch.float32))
         # the reference hands the latents to its CPU decoder (generation.py:129-130); a decoder that lives on a device says so
         # (EncodecHIP.decoder_device) and gets them where they are
         if decode == "segments":

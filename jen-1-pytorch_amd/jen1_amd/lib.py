@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip", "latent_norm.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -281,6 +281,10 @@ SYMBOLS = {
     "jen1_kweight_tile_chunks": (c_int, [c_int]),
     "jen1_loudness_gate": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, _P]),
     "jen1_gain_apply": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, C.c_double, C.c_double, _P]),
+    # csrc/latent_norm.hip: moments of the codec latents (lengths: a HOST pointer) and the whitening map
+    "jen1_latent_moments_workspace": (c_int64, [c_int, c_int, c_int]),
+    "jen1_latent_moments": (c_int, [_P, C.POINTER(c_int), _P, _P, c_int64, c_int, c_int, c_int, _P]),
+    "jen1_latent_affine": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     # csrc/windows.hip: overlapping sampler windows on one canvas
     "jen1_window_merge": (c_int, [_P, _P] + [c_int] * 6 + [_P, _P]),
     "jen1_window_gather": (c_int, [_P, _P, _P] + [c_int] * 6 + [_P]),
