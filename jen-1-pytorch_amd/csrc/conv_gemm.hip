@@ -32,6 +32,7 @@
 //   * optional inter-workgroup split-K: partial slabs + agent-scope release / ticket /
 //     acquire, last arriver reduces (cdna_hip_programming.md section 5).
 #include "mfma_frag.h"
+#include "tile_conv.h"       // norm_rstd, silu8
 
 // Tuning builds only (-DJEN1_PROFILE): workgroup (0,0,0), thread 0 records the constant-rate 100 MHz
 // s_memrealtime counter at phase boundaries into args.slab (reused as a debug buffer).
@@ -316,10 +317,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
             }
           }
         }
-        if (do_silu) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] = PRECISE ? silu_precise(x[j]) : silu_f(x[j]);
-        }
+        if (do_silu) silu8<PRECISE>(x);
       }
       store8(tile + (size_t)row * ldsld + cl, x);
     }
@@ -385,11 +383,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
         }
         s *= sc;
         q *= sc * sc;
-        const float inv_n = 1.0f / (float)a.gn_count;
-        mean = s * inv_n;
-        float var = q * inv_n - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        rstd = PRECISE ? 1.0f / sqrtf(var + a.gn_eps) : rsqrtf(var + a.gn_eps);
+        rstd = norm_rstd<PRECISE>(s, q, 1.0f / (float)a.gn_count, a.gn_eps, mean);
       }
       grp[2 * i] = mean;
       grp[2 * i + 1] = rstd;
@@ -403,10 +397,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
       float mean = 0.f, rstd = 0.f;
       if (b < a.B && tin >= 0 && tin < a.L_in) {
         const float* rs = a.ln_rowstats + ((size_t)b * a.L_in + tin) * 2;
-        mean = rs[0] * inv_c;
-        float var = rs[1] * inv_c - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        rstd = PRECISE ? 1.0f / sqrtf(var + a.ln_eps) : rsqrtf(var + a.ln_eps);
+        rstd = norm_rstd<PRECISE>(rs[0], rs[1], inv_c, a.ln_eps, mean);
       }
       rowtab[2 * i] = mean;
       rowtab[2 * i + 1] = rstd;
@@ -601,6 +592,7 @@ __global__ __launch_bounds__(64 * WM * WK) void conv_gemm_kernel(const jen1_conv
         if (a.ln_fold) {
           // Linear(LayerNorm(x)) = rstd * (W'x - mean * rowsum(W')) + W beta   (blocks.py:427-429)
           const float inv_c = 1.0f / (float)a.ln_C;
+          // (norm_rstd written out: profiles/tile_conv_refactor.txt, section 3)
           const float mean = lnrs[nf].x * inv_c;
           float var = lnrs[nf].y * inv_c - mean * mean;
           var = var < 0.f ? 0.f : var;

@@ -26,6 +26,7 @@
 #endif
 #include "live_words.h"      // the reserved-word protocol: Raw8 / Raw4, ld_live, raw_bad, st_word, live_poll_again
 #include "mfma_frag.h"
+#include "tile_conv.h"       // the tile convolution's arithmetic: GroupNorm table, sub-pixel phase, epilogue sums; norm_rstd, silu8
 #include "jen1_deep.h"
 
 namespace {
@@ -829,12 +830,8 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
       s = e.x + o.x;
       q = e.y + o.y;
     }
-    const float inv_count = HF(inv_count);
-    const float gn_eps = HF(gn_eps);
-    const float mean = s * inv_count;
-    float var = q * inv_count - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    const float rstd = PRECISE ? 1.0f / sqrtf(var + gn_eps) : rsqrtf(var + gn_eps);
+    float mean;
+    const float rstd = norm_rstd<PRECISE>(s, q, HF(inv_count), HF(gn_eps), mean);
     const bool silu = HI(pro_mode) == JEN1_PRO_GN_SILU;
     DK_STAMPN(sy, 8);
     // bf16 / fp8 staging: the affine map as ONE fused multiply-add per element (a = rstd * gamma', b = beta' - mean * a)
@@ -849,10 +846,7 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
 #ifndef JEN1_DEEP_EXP_NONORM      // timing experiment only (results are garbage): what a consumer would save if producers stored the normalised activation
 #pragma unroll
       for (int j = 0; j < 8; ++j) xf[i][j] = PRECISE ? (xf[i][j] - mean) * rstd * p1[j] + p2[j] : xf[i][j] * pa[j] + pb[j];
-      if (silu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[i][j] = PRECISE ? silu_precise(xf[i][j]) : silu_f(xf[i][j]);
-      }
+      if (silu) silu8<PRECISE>(xf[i]);
 #else
       xf[i][0] += mean + rstd + pa[0] + pb[0];
 #endif
@@ -877,10 +871,7 @@ __device__ __forceinline__ void gemm_unit(const unsigned char* D, int u, Sync& s
         raw_to_float(xt[i], x);
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = PRECISE ? (x[j] * mt_[i] - mean) * rstd * p1[j] + p2[j] : (x[j] * mt_[i]) * pa[j] + pb[j];
-        if (silu) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] = PRECISE ? silu_precise(x[j]) : silu_f(x[j]);
-        }
+        if (silu) silu8<PRECISE>(x);
         store8(tile + tt[i], x);
       }
     }
@@ -1251,10 +1242,8 @@ __device__ __forceinline__ void attn_unit(const unsigned char* D, int u, Sync& s
       s = row16_sum(s);
       q2 = row16_sum(q2);
       if (li == 0) {
-        const float mean = s * inv_c;
-        float var = q2 * inv_c - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        const float rstd = PRECISE ? 1.0f / sqrtf(var + ln_eps) : rsqrtf(var + ln_eps);
+        float mean;
+        const float rstd = norm_rstd<PRECISE>(s, q2, inv_c, ln_eps, mean);
         st_s[r] = make_float2(mean, rstd);
       }
     }
@@ -1690,10 +1679,10 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf) {
         const int m = (mt0 + mf) * 16 + lg * 4;
-        int ph = 0;
-        for (int k = 1; k < ps_f0; ++k) ph += (m >= k * out_C0) ? 1 : 0;
+        int co;
+        subpixel_phase(m, out_C0, ps_f0, co);
         bias4[mf] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (biasp && nfw > 0 && mt0 + mf < MT) bias4[mf] = *reinterpret_cast<const f32x4*>(biasp + (m - ph * out_C0));
+        if (biasp && nfw > 0 && mt0 + mf < MT) bias4[mf] = *reinterpret_cast<const f32x4*>(biasp + co);
       }
     }
     DK_STAMP(sy, 7);
@@ -1764,17 +1753,10 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
         }
         s += fs; q += fq;
       }
-      const float sc = k1 ? sc1 : 1.0f;
-      s *= sc;
-      q *= sc * sc;
-      const float inv_count = TF(h.inv_count);
-      const float mean = s * inv_count;
-      float var = q * inv_count - mean * mean;
-      var = var < 0.f ? 0.f : var;
-      const float rstd = PRECISE ? 1.0f / sqrtf(var + TF(h.gn_eps)) : rsqrtf(var + TF(h.gn_eps));
-      const float A = rstd * g1;
-      tabA[c] = A * sc;
-      tabS[c] = g2 - mean * A;
+      float A, S;
+      gn_affine<PRECISE>(s, q, k1 ? sc1 : 1.0f, TF(h.inv_count), TF(h.gn_eps), g1, g2, A, S);
+      tabA[c] = A;
+      tabS[c] = S;
     }
     __syncthreads();
   }
@@ -1798,7 +1780,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
       const int c = cur.c[k];
       float x[8];
       raw_to_float(cur.x[k], x);
-      int to = cur.to[k];
+      int to = cur.to[k];                         // (the tree is written out in all three kernels: profiles/tile_conv_refactor.txt, section 3)
       if (to >= 0) {
         if (c < cmain) {
           if (gn) {
@@ -1893,9 +1875,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
       const int m = (mt0 + mf) * 16 + lg * 4;
-      int ph = 0;
-      for (int k = 1; k < ps_f; ++k) ph += (m >= k * out_C) ? 1 : 0;
-      co_[mf] = m - ph * out_C;
+      const int ph = subpixel_phase(m, out_C, ps_f, co_[mf]);
 #pragma unroll
       for (int nf = 0; nf < NFW; ++nf) {
         const int n = (nf0 + nf) * 16 + li;
@@ -1945,8 +1925,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
             const unsigned off = (unsigned)yrow_[mf][nf] * (unsigned)ld_y + (unsigned)co_[mf];
             if (y_f32) st_live4<false>(TP(h.y, float*) + off, v);
             else st_live4<false>(TP(h.y, GT*) + off, v);
-            gs += (v[0] + v[1]) + (v[2] + v[3]);
-            gq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+            sums4(v, gs, gq);
           }
         }
       }
@@ -1954,9 +1933,7 @@ __device__ __forceinline__ void tile_unit(const unsigned char* D, int u, Sync& s
       if (out_part) {
         // the 16 rows of an M tile lie in ONE statistics group (out_cps is a multiple of 16): all 64 lanes, fixed tree
         gs = row16_sum(gs); gq = row16_sum(gq);
-        auto rl = [](float v, int l) __attribute__((always_inline)) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); };
-        const float ts = (rl(gs, 0) + rl(gs, 16)) + (rl(gs, 32) + rl(gs, 48));       // the four rows of the wave, fixed order, no LDS round trips
-        const float tq = (rl(gq, 0) + rl(gq, 16)) + (rl(gq, 32) + rl(gq, 48));
+        const float ts = rows4_sum(gs), tq = rows4_sum(gq);       // the four rows of the wave, fixed order, no LDS round trips
         const float fgo = mt0 + mf < MT ? (float)(int)(((float)__builtin_amdgcn_readlane(co_[mf], 0) + 0.5f) * TF(tl.inv_out_cps)) : -1.0f;
         if (lane == 0) *reinterpret_cast<float4*>(red + (wv * MF + mf) * 4) = make_float4(ts, tq, fgo, 0.f);
       }

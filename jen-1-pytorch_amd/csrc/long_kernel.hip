@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "live_words.h"      // the reserved-word protocol: Raw8 / Raw4, ld_live, raw_bad, st_word<LOC>, live_poll_again
 #include "mfma_frag.h"
+#include "tile_conv.h"       // the tile convolution's arithmetic: GroupNorm table (fine_sum4, gn_affine), epilogue sums
 #include "jen1_long.h"
 
 namespace {
@@ -64,7 +65,6 @@ __device__ __forceinline__ void wload(F& f, __amdgpu_buffer_rsrc_t r, unsigned v
 #endif
   buf_frag<0>(f, r, voff, soff);
 }
-__device__ __forceinline__ float rlane(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
 template <typename T> struct LongCfg;
 #ifndef JEN1_LONG_RING_B
@@ -374,28 +374,11 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
     }
     const float2* rk = stl + (k1 ? 32 : 0);
     float s = 0.f, q = 0.f;
-    // (entries in fixed order; four independent reads in flight)
-    for (int i = 0; i < cnt; i += 4) {
-      float2 e4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) e4[j] = rk[(i + j < cnt) ? i0 + i + j : i0];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s += (i + j < cnt) ? e4[j].x : 0.f;
-        q += (i + j < cnt) ? e4[j].y : 0.f;
-      }
-    }
-    const float sc = k1 ? LF(src1_scale) : 1.0f;
-    s *= sc;
-    q *= sc * sc;
-    const float inv_count = LF(inv_count);
-    const float mean = s * inv_count;
-    float var = q * inv_count - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    const float rstd = PRECISE ? 1.0f / sqrtf(var + LF(gn_eps)) : rsqrtf(var + LF(gn_eps));
-    const float A = rstd * g1;
-    tabA[c] = A * sc;
-    tabS[c] = g2 - mean * A;
+    fine_sum4(rk, i0, cnt, s, q);
+    float A, S;
+    gn_affine<PRECISE>(s, q, k1 ? LF(src1_scale) : 1.0f, LF(inv_count), LF(gn_eps), g1, g2, A, S);
+    tabA[c] = A;
+    tabS[c] = S;
   }
   if (gn) __syncthreads();
   LK_STAMP(sy, 4);
@@ -560,15 +543,13 @@ __device__ __forceinline__ void long_unit(const DescRegs& dr, int b, int slot, L
           for (int r = 0; r < 4; ++r) v[r] += r4[r];
         }
         st_live4<LOC>(LP(y, T*) + ((unsigned)yrow[nf] * (unsigned)ld_y + (unsigned)co), v);
-        gs += (v[0] + v[1]) + (v[2] + v[3]);
-        gq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+        sums4(v, gs, gq);
       }
     }
     if (out_part) {
       // the wave's 16 channels x its valid positions: all 64 lanes, fixed tree, one word
       gs = row16_sum(gs); gq = row16_sum(gq);
-      const float ts = (rlane(gs, 0) + rlane(gs, 16)) + (rlane(gs, 32) + rlane(gs, 48));
-      const float tq = (rlane(gq, 0) + rlane(gq, 16)) + (rlane(gq, 32) + rlane(gq, 48));
+      const float ts = rows4_sum(gs), tq = rows4_sum(gq);
       if (lane == 0) {
         const int ne = LI(out_entries);
         st_word<LOC>(out_part + 2 * ((size_t)(b * 8 + wv) * ne + slot), 0, __float_as_uint(ts), __float_as_uint(tq));

@@ -7,7 +7,7 @@
 // merges the fine-group sums of ITS group straight from the producers' statistics (a few broadcast
 // loads that are in flight together with the activation vector, gamma / beta and the FiLM rows), and
 // the kernel arguments arrive as one explicit batch of scalar loads.
-#include "common.h"
+#include "tile_conv.h"       // norm_rstd, gn_affine, film_affine
 
 namespace {
 
@@ -100,10 +100,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormDev a_unused)
     const float sc = s1 ? a.src1_scale : 1.0f;
     s *= sc;
     q *= sc * sc;
-    mean = s * a.inv_count;
-    float var = q * a.inv_count - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    rstd = PRECISE ? 1.0f / sqrtf(var + a.eps) : rsqrtf(var + a.eps);
+    rstd = norm_rstd<PRECISE>(s, q, a.inv_count, a.eps, mean);
     // y = (x*sc - mean) * rstd * gamma + beta, then FiLM, then SiLU
     float A[8], Bc[8];
 #pragma unroll
@@ -111,11 +108,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormDev a_unused)
       A[j] = rstd * (affine ? gam[j] : 1.0f);
       Bc[j] = (affine ? bet[j] : 0.0f) - mean * A[j];
       A[j] *= sc;
-      if (film) {
-        const float f1 = fs[j] + 1.0f;
-        A[j] *= f1;
-        Bc[j] = Bc[j] * f1 + fh[j];
-      }
+      if (film) film_affine(A[j], Bc[j], fs[j], fh[j]);
     }
     if ((a.cpg & 7) != 0) {
       // groups narrower than a vector (tiny configurations): per-channel statistics, same formula
@@ -132,16 +125,9 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormDev a_unused)
           sj += st[b * 64 + 2 * f];
           qj += st[b * 64 + 2 * f + 1];
         }
-        sj *= sc;
-        qj *= sc * sc;
-        const float mj = sj * a.inv_count;
-        float vj = qj * a.inv_count - mj * mj;
-        vj = vj < 0.f ? 0.f : vj;
-        const float rj = PRECISE ? 1.0f / sqrtf(vj + a.eps) : rsqrtf(vj + a.eps);
-        float Aj = rj * (affine ? gam[j] : 1.0f);
-        float Bj = (affine ? bet[j] : 0.0f) - mj * Aj;
-        Aj *= sc;
-        if (film) {
+        float Aj, Bj;
+        gn_affine<PRECISE>(sj, qj, sc, a.inv_count, a.eps, affine ? gam[j] : 1.0f, affine ? bet[j] : 0.0f, Aj, Bj);
+        if (film) {      // (film_affine written out: profiles/tile_conv_refactor.txt, section 3)
           const float f1 = fs[j] + 1.0f;
           Aj *= f1;
           Bj = Bj * f1 + fh[j];
@@ -157,10 +143,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormDev a_unused)
     }
   } else {
     const float2 rs = *reinterpret_cast<const float2*>(a.ln_rowstats + 2 * grow);
-    mean = rs.x * a.inv_count;
-    float var = rs.y * a.inv_count - mean * mean;
-    var = var < 0.f ? 0.f : var;
-    rstd = PRECISE ? 1.0f / sqrtf(var + a.eps) : rsqrtf(var + a.eps);
+    rstd = norm_rstd<PRECISE>(rs.x, rs.y, a.inv_count, a.eps, mean);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       x[j] = (x[j] - mean) * rstd;

@@ -20,6 +20,7 @@
 //   * 16-row M tile per workgroup, the 4 waves split K and reduce through LDS; optional
 //     inter-workgroup split-K with write-through slabs + ticket (cdna_hip_programming.md G16 R1).
 #include "mfma_frag.h"
+#include "tile_conv.h"       // norm_rstd
 
 #ifdef JEN1_PROFILE
 #define SG_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0 && a.dbg) \
@@ -422,10 +423,8 @@ __global__ __launch_bounds__(64 * SG_NW) void stream_gemm_kernel(const StreamArg
       float v[4];
       if (e.ln_fold) {
         // Linear(LayerNorm(x)) = rstd * (W'x - mean * rowsum(W')) + W beta   (blocks.py:427-429)
-        const float mean = lnrs[nf].x * e.inv_lnC;
-        float var = lnrs[nf].y * e.inv_lnC - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        const float rstd = PRECISE ? 1.0f / sqrtf(var + e.ln_eps) : rsqrtf(var + e.ln_eps);
+        float mean;
+        const float rstd = norm_rstd<PRECISE>(lnrs[nf].x, lnrs[nf].y, e.inv_lnC, e.ln_eps, mean);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = (acc[nf][r] - mean * lnu[r]) * rstd + bias4[r];
       } else {

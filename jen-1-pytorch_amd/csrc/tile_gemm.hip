@@ -18,6 +18,7 @@
 //     stream from L2 through a register ring with scalar offsets;
 //   * 4 waves x (16 MF) output rows x (16 NF) positions, v_mfma_f32_16x16x32_bf16 / 16x16x4_f32.
 #include "mfma_frag.h"
+#include "tile_conv.h"       // gn_affine, film_affine; affine8, scale8, zero8; subpixel_phase
 
 namespace {
 
@@ -252,20 +253,9 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
           q += in ? t4[j].y : 0.f;
         }
       }
-      const float sc = s1 ? h.src1_scale : 1.0f;
-      s *= sc;
-      q *= sc * sc;
-      const float mean = s * h.inv_count;
-      float var = q * h.inv_count - mean * mean;
-      var = var < 0.f ? 0.f : var;
-      const float rstd = PRECISE ? 1.0f / sqrtf(var + h.eps) : rsqrtf(var + h.eps);
-      float A = rstd * gam;
-      float S = bet - mean * A;
-      A *= sc;
-      if (h.film) {
-        A *= fs + 1.0f;
-        S = S * (fs + 1.0f) + fh;
-      }
+      float A, S;
+      gn_affine<PRECISE>(s, q, s1 ? h.src1_scale : 1.0f, h.inv_count, h.eps, gam, bet, A, S);
+      if (h.film) film_affine(A, S, fs, fh);      // (FiLM at table time: this kernel only)
       tabA[c] = A;
       tabS[c] = S;
     }
@@ -290,25 +280,21 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
       const int tin = tin0 + row;
       float x[8];
       vec_to_float(cur.x[u], x);
+      // (SiLU also without GroupNorm, JEN1_PRO_SILU: this kernel only; its loop is written out: profiles/tile_conv_refactor.txt, section 3)
       if (tin >= 0 && tin < h.L_in) {
         if (XS && c >= ctot) {
           // raw extra segment: staged as it is
         } else if (gn) {
-          const float4 a0 = *reinterpret_cast<const float4*>(tabA + c), a1 = *reinterpret_cast<const float4*>(tabA + c + 4);
-          const float4 s0 = *reinterpret_cast<const float4*>(tabS + c), s1 = *reinterpret_cast<const float4*>(tabS + c + 4);
-          x[0] = x[0] * a0.x + s0.x; x[1] = x[1] * a0.y + s0.y; x[2] = x[2] * a0.z + s0.z; x[3] = x[3] * a0.w + s0.w;
-          x[4] = x[4] * a1.x + s1.x; x[5] = x[5] * a1.y + s1.y; x[6] = x[6] * a1.z + s1.z; x[7] = x[7] * a1.w + s1.w;
+          affine8(x, tabA + c, tabS + c);
         } else if (c >= h.c0 && h.src1_scale != 1.0f) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] *= h.src1_scale;
+          scale8(x, h.src1_scale);
         }
         if (do_silu && (!XS || c < ctot)) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) x[j] = PRECISE ? silu_precise(x[j]) : silu_f(x[j]);
         }
       } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = 0.f;
+        zero8(x);
       }
       store8(tile + (size_t)row * ldsld + c, x);
     }
@@ -332,9 +318,8 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
     for (int mf = 0; mf < MF; ++mf) {
       const int m = (mt0 + mf) * 16 + lg * 4;
       if (mt0 + mf >= h.MT) continue;
-      int ph = 0;
-      for (int k = 1; k < e.ps_f; ++k) ph += (m >= k * e.out_C) ? 1 : 0;
-      const int co = m - ph * e.out_C;
+      int co;
+      const int ph = subpixel_phase(m, e.out_C, e.ps_f, co);
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
         const int n = nf * 16 + li;
@@ -385,16 +370,15 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(const TileArgs a_unused)
   T* yT = reinterpret_cast<T*>(e.y);
   float* yF = reinterpret_cast<float*>(e.y);
   const int m_wg0 = blockIdx.x * 64 * MF;                       // first GEMM row of the workgroup
-  int phw = 0;
-  for (int k = 1; k < e.ps_f; ++k) phw += (m_wg0 >= k * e.out_C) ? 1 : 0;
-  const int fgw0 = (int)(((float)(m_wg0 - phw * e.out_C) + 0.5f) * e.inv_out_cpf);      // first fine group the workgroup can touch
+  int co_wg0;
+  subpixel_phase(m_wg0, e.out_C, e.ps_f, co_wg0);
+  const int fgw0 = (int)(((float)co_wg0 + 0.5f) * e.inv_out_cpf);      // first fine group the workgroup can touch
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) {
     const int m = (mt0 + mf) * 16 + lg * 4;
     if (mt0 + mf >= h.MT) continue;
-    int ph = 0;
-    for (int k = 1; k < e.ps_f; ++k) ph += (m >= k * e.out_C) ? 1 : 0;
-    const int co = m - ph * e.out_C;
+    int co;
+    const int ph = subpixel_phase(m, e.out_C, e.ps_f, co);
     float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
     if (e.bias) bb = *reinterpret_cast<const float4*>(e.bias + co);
     float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};

@@ -670,6 +670,8 @@ LONG_CASES = {
                              live=("x0",), **LGN, reach=dict(mblocks=1, tb=2), wrong=(HALO, NEXT, ROW0)),
     "film_step":       _case("FiLM table by step, statistics from totals", B=8, L_in=64, c0=128, M=128, taps=3, pad_left=1, film="step",
                              st="totals", **LGN, reach=dict(mblocks=1, tb=2), wrong=(HALO, NEXT, "step_ignored")),
+    "raw_two_src":     _case("no GroupNorm, scaled second source", B=8, L_in=32, c0=64, c1=64, src1_scale=0.25, M=128, taps=3, pad_left=1,
+                             wrong=(HALO,)),
 }
 
 
@@ -707,6 +709,10 @@ TILE_CASES = {
                           reach=dict(tb=16, bm=256, tail=True), wrong=(HALO,)),
     "bm256_up2":    _case("bm 256, sub-pixel", B=2, c0=64, M=256, **_up(2, 1, 30), reach=dict(bm=256, tail=True),
                           wrong=(HALO, "ps_off_ignored")),
+    "gn_two_src":   _case("GroupNorm + SiLU over two sources, groups inside the scaled second source", B=2, L_in=16, c0=64, c1=64,
+                          src1_scale=0.25, M=128, taps=3, pad_left=1, st="totals", **LGN, wrong=(HALO, NEXT), wrong_f32=(SCALE,)),
+    "raw_two_src":  _case("no GroupNorm, scaled second source", B=2, L_in=16, c0=64, c1=64, src1_scale=0.25, M=128, taps=3, pad_left=1,
+                          wrong=(HALO,)),
 }
 
 
