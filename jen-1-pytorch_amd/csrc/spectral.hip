@@ -28,6 +28,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "jen1_analysis.h"
 #include "jen1_spectral.h"
 
 namespace {
@@ -83,8 +84,8 @@ __device__ __forceinline__ float spec_sample(const float* __restrict__ row, cons
 __device__ __forceinline__ float2 spec_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
 
 // P transforms of N points, in place, buffer p at buf + p * pitch.  The caller has synchronised behind its stores; every stage ends
-// with a barrier.
-__device__ __forceinline__ void spec_fft(float2* buf, const float2* __restrict__ tw, int N, int logN, int P, int pitch) {
+// with a barrier.  `tws`: the stride of the twiddle table (2: the table of 2 N points serves a transform of N).
+__device__ __forceinline__ void spec_fft(float2* buf, const float2* __restrict__ tw, int N, int logN, int P, int pitch, int tws = 1) {
   const int quarter = N >> 2, logQ4 = logN - 2;
   int L = N;
   for (; L >= 4; L >>= 2) {
@@ -97,7 +98,7 @@ __device__ __forceinline__ void spec_fft(float2* buf, const float2* __restrict__
       const float2 t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
       const float2 t2 = make_float2(a1.x + a3.x, a1.y + a3.y);
       const float2 t3 = make_float2(a1.y - a3.y, a3.x - a1.x);                       // -i (a1 - a3)
-      const int m = j * tstep;
+      const int m = j * tstep * tws;
       z[0] = make_float2(t0.x + t2.x, t0.y + t2.y);
       z[q] = spec_cmul(make_float2(t1.x + t3.x, t1.y + t3.y), tw[m]);
       z[2 * q] = spec_cmul(make_float2(t0.x - t2.x, t0.y - t2.y), tw[2 * m]);
@@ -314,6 +315,124 @@ __global__ __launch_bounds__(SPEC_THREADS) void spec_distance_sum_kernel(const d
   }
 }
 
+// ---- jen1_music_features (include/jen1_analysis.h).  A frame's values must not depend on its neighbours (the same bits whichever tile it
+// falls in), so frames are not packed in pairs here: a real frame of N samples is N / 2 complex points z[m] = x[2m] + i x[2m+1] -- the
+// frame as it lies in memory -- one transform of N / 2 points (the table of N at stride 2), and
+//   X[k] = E[k] + W_N^k O[k],  X[N/2 - k] = conj(E[k] - W_N^k O[k]),  E, O = what spec_untangle gives at k of the N / 2 points.
+// 2 P buffers of N / 2 + 1 float2 (the same bytes as the P buffers above, the same shift of one bank pair per buffer); a tile is 2 P
+// consecutive frames, the first of which is only there for the flux of the second: tiles overlap by one frame.
+constexpr int FEAT_LDS_MAX = 160 * 1024;
+inline int feat_tile(int N) { return 2 * spec_pairs(N); }
+inline size_t feat_buf_bytes(int N) { return (size_t)feat_tile(N) * (size_t)(N / 2 + 1) * sizeof(float2); }
+inline size_t feat_part_bytes(int N) { return (size_t)SPEC_WAVES * 12 * feat_tile(N) * sizeof(double); }        // per wave [12][tile] chroma sums
+inline size_t feat_lds_bytes(int N, int n_bands) { return feat_buf_bytes(N) + feat_part_bytes(N) + (size_t)feat_tile(N) * n_bands * sizeof(float); }
+inline int feat_max_bands(int N) {
+  const long long v = ((long long)FEAT_LDS_MAX - (long long)feat_buf_bytes(N) - (long long)feat_part_bytes(N)) / ((long long)feat_tile(N) * 4);
+  return (int)(v > SPEC_MAX_BANDS ? SPEC_MAX_BANDS : v);
+}
+
+// spec_rev(k, 1 << logN) without the loop: the base-4 digits of the low bits in reverse order (a bit reversal, then the two bits of
+// every digit swapped back), and with an odd logN the top bit of k last
+__device__ __forceinline__ int feat_rev(int k, int logN) {
+  const int m2 = logN & ~1;
+  unsigned r = __builtin_bitreverse32((unsigned)k & ((1u << m2) - 1u)) >> (32 - m2);
+  r = ((r & 0xAAAAAAAAu) >> 1) | ((r & 0x55555555u) << 1);
+  return (logN & 1) ? (int)((r << 1) | ((unsigned)k >> m2)) : (int)r;
+}
+
+// where (|X[k]|^2, |X[k]|) of bin k in [0, N2] lies in a buffer of N2 = N / 2 points: bin N2 in the padding slot behind them
+__device__ __forceinline__ int feat_pos(int k, int N2, int logN2) { return k == N2 ? N2 : feat_rev(k, logN2); }
+
+__global__ __launch_bounds__(SPEC_THREADS) void spec_features_kernel(const float* __restrict__ x, long long row_stride, float* __restrict__ onset,
+                                                                     float* __restrict__ chroma, const float* __restrict__ chroma_w, SpecFrame f,
+                                                                     SpecBands B, float gamma, int tiles) {
+  extern __shared__ __attribute__((aligned(16))) float2 buf[];
+  const int N2 = f.N >> 1, pitch = N2 + 1, TF = 2 * f.P, logTF = f.logP + 1, bins = N2 + 1;
+  const int logN2 = f.logN - 1;
+  double* part = reinterpret_cast<double*>(buf + (size_t)TF * pitch);                   // [waves][12][TF] partial chroma sums
+  float* mel = reinterpret_cast<float*>(part + SPEC_WAVES * 12 * TF);                    // [n_bands][TF]
+  const long long row = blockIdx.x / tiles, g0 = (long long)(blockIdx.x % tiles) * (TF - 1) - 1;      // frame of slot 0 (-1 in the first tile)
+  const float* xr = x + row * row_stride;
+  float* bf = reinterpret_cast<float*>(buf);
+  for (int e = threadIdx.x; e < TF * f.N; e += SPEC_THREADS) {
+    const int j = e >> f.logN, i = e & (f.N - 1);
+    const long long g = g0 + j;
+    bf[(size_t)j * pitch * 2 + i] = g < 0 ? 0.f : spec_sample(xr, f, g, i);
+  }
+  __syncthreads();
+  spec_fft(buf, f.tw, N2, f.logN - 1, TF, pitch, 2);
+  // bins k and N2 - k of slot j from the points k and N2 - k, written over them: a thread reads and writes only its own two slots
+  for (int e = threadIdx.x; e < (N2 / 2 + 1) * TF; e += SPEC_THREADS) {
+    const int j = e & (TF - 1), k = e >> logTF;
+    float2* z = buf + j * pitch;
+    float2 E, O;
+    spec_untangle(z, k, N2, E, O);
+    const float2 T = spec_cmul(O, f.tw[k]);
+    const float pa = (E.x + T.x) * (E.x + T.x) + (E.y + T.y) * (E.y + T.y);
+    const float pb = (E.x - T.x) * (E.x - T.x) + (E.y - T.y) * (E.y - T.y);
+    z[spec_rev(k, N2)] = make_float2(pa, sqrtf(pa));
+    if (k == 0)
+      z[N2] = make_float2(pb, sqrtf(pb));
+    else if (2 * k != N2)
+      z[spec_rev(N2 - k, N2)] = make_float2(pb, sqrtf(pb));
+  }
+  __syncthreads();
+  // Y[b][j] = log1p(gamma * sum_k w[b][k] |X[k]|): float64 sums, the logarithm in float64 rounded once
+  for (int e = threadIdx.x; e < B.n_bands * TF; e += SPEC_THREADS) {
+    const int j = e & (TF - 1), b = e >> logTF;
+    double acc = 0.0;
+    int lo, hi;
+    long long w0;
+    if (spec_band(B, b, bins, lo, hi, w0)) {
+      const float2* z = buf + j * pitch;
+      for (int k = lo; k < hi; ++k) acc = fma((double)B.w[w0 + k], (double)z[feat_pos(k, N2, logN2)].y, acc);
+    }
+    mel[e] = (float)log1p((double)gamma * acc);
+  }
+  // chroma: lane (frame j, group g) owns a run of consecutive bins and all twelve classes of it (runs, because neighbouring bins lie
+  // n_fft / 8 apart after the digit reversal -- one bank pair -- while the starts of runs do not); a wave adds its groups frame by
+  // frame in a halving tree, the waves follow in ascending order
+  {
+    const int j = threadIdx.x & (TF - 1), g = threadIdx.x >> logTF, G = SPEC_THREADS >> logTF, run = (bins + G - 1) / G;
+    const float2* z = buf + j * pitch;
+    const int k1 = min(bins, (g + 1) * run);
+    double acc[12];
+#pragma unroll
+    for (int p = 0; p < 12; ++p) acc[p] = 0.0;
+    for (int k = g * run; k < k1; ++k) {
+      const double v = (double)z[feat_pos(k, N2, logN2)].x;
+#pragma unroll
+      for (int p = 0; p < 12; ++p) acc[p] = fma((double)chroma_w[(size_t)p * bins + k], v, acc[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < 12; ++p) {
+      double v = acc[p];
+      for (int o = 32; o >= TF; o >>= 1) v += __shfl_down(v, o);
+      if ((threadIdx.x & 63) < TF) part[((threadIdx.x >> 6) * 12 + p) * TF + j] = v;
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 12 * TF; e += SPEC_THREADS) {
+    const int j = e & (TF - 1), p = e >> logTF;
+    const long long g = g0 + j;
+    if (j == 0 || g >= f.frames) continue;
+    double acc = 0.0;
+    for (int w = 0; w < SPEC_WAVES; ++w) acc += part[(w * 12 + p) * TF + j];
+    chroma[(row * 12 + p) * f.frames + g] = (float)acc;
+  }
+  // the flux of slot j >= 1 against slot j - 1, the bands in ascending order
+  if (threadIdx.x >= SPEC_THREADS - TF) {
+    const int j = threadIdx.x - (SPEC_THREADS - TF);
+    const long long g = g0 + j;
+    if (j >= 1 && g < f.frames) {
+      double acc = 0.0;
+      if (g >= 1)
+        for (int b = 0; b < B.n_bands; ++b) acc += (double)fmaxf(0.f, mel[b * TF + j] - mel[b * TF + j - 1]);
+      onset[row * f.frames + g] = (float)(acc / (double)B.n_bands);
+    }
+  }
+}
+
 inline long long spec_frames(long long n, int N, int hop, int center) {
   if (!spec_nfft_ok(N) || hop < 1 || hop > N || (center != 0 && center != 1) || n < 1 || n >= (1ll << 40)) return -1;
   if (center) return n > N / 2 ? 1 + n / hop : -1;
@@ -444,6 +563,34 @@ extern "C" int jen1_spectral_distance(const float* x, int64_t x_stride, const fl
   hipLaunchKernelGGL(spec_distance_kernel, dim3((unsigned)(tiles * rows)), dim3(SPEC_THREADS), spec_lds_bytes(n_fft), s, x, (long long)x_stride, y,
                      (long long)y_stride, static_cast<double*>(workspace), f, B, kind, floor, (int)tiles);
   hipLaunchKernelGGL(spec_distance_sum_kernel, dim3((unsigned)rows), dim3(SPEC_THREADS), 0, s, static_cast<const double*>(workspace), out, (int)tiles);
+  JEN1_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int jen1_music_features_tile_frames(int n_fft) { return spec_nfft_ok(n_fft) ? feat_tile(n_fft) - 1 : 0; }
+
+extern "C" int jen1_music_features_max_bands(int n_fft) { return spec_nfft_ok(n_fft) ? feat_max_bands(n_fft) : 0; }
+
+extern "C" int jen1_music_features(const float* x, int64_t row_stride, float* onset, float* chroma, const float* window, const float* twiddle,
+                                   const int32_t* band_lo, const int32_t* band_hi, const int32_t* band_off, const float* band_w, int n_bands,
+                                   int64_t n_weights, const float* chroma_w, float gamma, int rows, int64_t n, int n_fft, int hop, int win_length,
+                                   int center, void* stream) {
+  SpecFrame f;
+  SpecBands B;
+  long long tiles = 0;
+  if (int rc = spec_plan("jen1_music_features", x, window, twiddle, rows, n, row_stride, n_fft, hop, win_length, center, 2, &f, &tiles)) return rc;
+  if (int rc = spec_bands("jen1_music_features", band_lo, band_hi, band_off, band_w, n_bands, n_weights, &B)) return rc;
+  JEN1_CHECK(n_bands <= feat_max_bands(n_fft), "jen1_music_features: n_bands = %d, at most %d fit in LDS at n_fft = %d", n_bands, feat_max_bands(n_fft),
+             n_fft);
+  JEN1_CHECK(gamma > 0.f && isfinite(gamma), "jen1_music_features: gamma = %g, must be positive", (double)gamma);
+  JEN1_CHECK(onset != nullptr && chroma != nullptr && chroma_w != nullptr, "jen1_music_features: null pointer");
+  const long long per = feat_tile(n_fft) - 1;
+  tiles = (f.frames + per - 1) / per;
+  JEN1_CHECK(tiles * (rows > 0 ? rows : 1) < (1ll << 31), "jen1_music_features: %lld tiles x %d rows exceed the grid", tiles, rows);
+  if (rows == 0) return 0;
+  JEN1_MAX_LDS_ONCE(spec_features_kernel, FEAT_LDS_MAX);
+  hipLaunchKernelGGL(spec_features_kernel, dim3((unsigned)(tiles * rows)), dim3(SPEC_THREADS), feat_lds_bytes(n_fft, n_bands),
+                     reinterpret_cast<hipStream_t>(stream), x, (long long)row_stride, onset, chroma, chroma_w, f, B, gamma, (int)tiles);
   JEN1_HIP(hipGetLastError());
   return 0;
 }

@@ -119,10 +119,21 @@ class LatentCollate:
     beyond its empty stub): a fitted ``jen1_amd.normalizer.Normalizer``; the batch's latents go through its ``normalize`` behind
     ``encode_latents``, so the trainer sees whitened latents.  ``with_lengths`` (for FITTING one, ``Normalizer.fit``): the batch carries a
     third entry, the valid latent frames of every clip -- its own sample count behind the conversion, mapped to frames -- so that the
-    zero padding of short clips stays out of the statistics."""
+    zero padding of short clips stays out of the statistics.  ``analyze`` (not in the reference): a tuple from ("tempo", "key"); for every
+    item whose metadata lacks a named entry the value is measured from the clip itself (``jen1_amd.analysis.analyze`` on the converted
+    batch, in front of ``normalize`` and the encoder, with the clip's valid sample count) and put into a COPY of its metadata.  Values
+    the JSON has win; a clip the analyser cannot decide (tempo 0, key -1) gets no entry, so the conditioner's own rule for a missing key
+    applies.  The results come to the host in one copy per batch, behind the enqueued encode call.  ``analyzer``: a stand-in for
+    ``analysis.analyze`` with its signature."""
 
     def __init__(self, audio_encoder, device="cuda", sample_duration=10, convert_audio: Optional[Callable] = None,
-                 normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None, with_lengths: bool = False):
+                 normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None, with_lengths: bool = False, analyze=(),
+                 analyzer: Optional[Callable] = None):
+        self.analyze = tuple(analyze)
+        bad = [a for a in self.analyze if a not in ("tempo", "key")]
+        if bad:
+            raise ValueError(f"unknown analyze entries {bad}: a tuple from ('tempo', 'key')")
+        self._analyzer = analyzer
         self.audio_encoder, self.device, self.sample_duration = audio_encoder, device, sample_duration
         self._convert = convert_audio
         if normalize is not None:
@@ -145,6 +156,26 @@ class LatentCollate:
             return self._convert(wav, sr, target_sr, target_channels)
         from . import audio
         return audio.convert_audio(wav, sr, target_sr, target_channels, device=self.device)
+
+    def analyze_batch(self, wav, rate, valid):
+        if self._analyzer is not None:
+            return self._analyzer(wav, rate, lengths=valid)
+        from . import analysis
+        return analysis.analyze(wav, rate, lengths=valid, device=self.device)
+
+    def fill_metadata(self, meta, measured):
+        """copies of ``meta`` with the entries of ``self.analyze`` they lack, from one device-to-host copy of the measured [tempo; key]"""
+        host = torch.stack([torch.as_tensor(measured["tempo"]).to(torch.float64), torch.as_tensor(measured["key"]).to(torch.float64)]).cpu()
+        out = []
+        for i, md in enumerate(meta):
+            md = dict(md)
+            bpm, k = float(host[0, i]), int(host[1, i])
+            if "tempo" in self.analyze and "tempo" not in md and bpm > 0.0:
+                md["tempo"] = bpm
+            if "key" in self.analyze and "key" not in md and k >= 0:
+                md["key"] = k
+            out.append(md)
+        return out
 
     @staticmethod
     def _channels(chunk: torch.Tensor, target: int) -> torch.Tensor:
@@ -178,11 +209,16 @@ class LatentCollate:
             out[idx, :, :n] = conv[:, :, :n].to(self.device, torch.float32)
             for i, c in zip(idx, clips):
                 valid[i] = min(n, -(-c.shape[-1] * rate // sr))
+        measured = None
+        if self.analyze and any(name not in meta for _chunk, _sr, meta in batch for name in self.analyze):
+            measured = self.analyze_batch(out, rate, valid)                  # device tensors: nothing waits here
         if self.normalize is not None:             # the level of every clip, set in one call on the padded batch (not in the reference)
             from . import audio
             out = audio.normalize_audio(out, rate, strategy=self.normalize, target_lufs=self.target_lufs, limit="clip", device=self.device)
         emb = ae.encode_latents(out)[0]
         meta = [meta for _chunk, _sr, meta in batch]
+        if measured is not None:
+            meta = self.fill_metadata(meta, measured)
         lengths = [self.valid_frames(v, n_out, emb.shape[-1]) for v in valid] if self.with_lengths else None
         if self.normalizer is not None:
             emb = self.normalizer.normalize(emb)
@@ -207,12 +243,12 @@ class LatentLoader:
 def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sample_duration, aug_shift, batch_size: int = 50, shuffle: bool = True,
                     split_ratio=0.8, device="cpu", durations_path=None, cumsum_path=None, audio_file_txt_path=None, *, audio_encoder=None,
                     num_workers: int = 0, dataset_cls=None, normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None,
-                    with_lengths: bool = False):
+                    with_lengths: bool = False, analyze=()):
     """(train loader, validation loader) of ``(emb, metadata)`` batches.  ``dataset_dir``: one folder (split by ``split_ratio``) or a
     (train, validation) pair.  ``audio_encoder`` (an ``EncodecHIP``) installs ``LatentCollate`` on ``device``; without it the loaders yield
     the raw item lists.  ``num_workers`` > 0 reads the files in spawned worker processes, which never touch the GPU.  ``dataset_cls``: a
     ``MusicDataset`` subclass to build instead (one that selects or tags items; importable by name when workers are used).  ``normalize`` /
-    ``target_lufs``, ``normalizer`` and ``with_lengths`` are handed to ``LatentCollate``."""
+    ``target_lufs``, ``normalizer``, ``with_lengths`` and ``analyze`` are handed to ``LatentCollate``."""
     cls = MusicDataset if dataset_cls is None else dataset_cls
 
     def make(folder):
@@ -226,7 +262,7 @@ def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sampl
     else:
         train_dataset, val_dataset = make(dataset_dir[0]), make(dataset_dir[1])
     fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs,
-                                                             normalizer=normalizer, with_lengths=with_lengths)
+                                                             normalizer=normalizer, with_lengths=with_lengths, analyze=analyze)
     kw = dict(batch_size=batch_size, collate_fn=collate, drop_last=True, num_workers=num_workers)
     if num_workers > 0:
         kw["multiprocessing_context"] = "spawn"        # never fork a process that has initialised the GPU

@@ -443,6 +443,24 @@ class Jen1:
         y = ae.decode_latents(z.to(getattr(ae, "decoder_device", "cpu")), seg_frames, scales=scales, length=x.shape[-1])
         return spectral.audio_report(y.to(self.device), x, self.sample_rate, device=self.device)
 
+    def control_report(self, wav: torch.Tensor, sr: Optional[int] = None, conditions=None) -> dict:
+        """How ``wav`` (``[C, n]`` or ``[B, C, n]`` at rate ``sr``; None: the model's own) follows the global controls it was asked for: the
+        audio is converted as ``codec_report`` converts it and the result is ``jen1_amd.analysis.control_report`` -- the measured tempo and
+        key of every row, and against the ``"tempo"`` / ``"key"`` entries of ``conditions`` (the dict ``generate`` took, or one per row)
+        the verdicts ``tempo_match``, ``tempo_match_octave``, ``key_match`` and ``key_related``.  Not in the reference."""
+        from . import analysis
+        if wav.dim() == 2:
+            wav = wav.unsqueeze(0)
+        x = self.convert_audio(wav, sr, self.sample_rate, self.audio_encoder.channels).to(self.device)
+        rows = [conditions or {}] * int(x.shape[0]) if not isinstance(conditions, (list, tuple)) else list(conditions)
+        if len(rows) != int(x.shape[0]):
+            raise ValueError(f"control_report: {len(rows)} condition dicts for {int(x.shape[0])} rows")
+        target = lambda name: None if all(name not in c for c in rows) else [c.get(name) for c in rows]
+        tempo, key = target("tempo"), target("key")
+        if any(v is None for t in (tempo, key) if t is not None for v in t):
+            raise ValueError("control_report: a control is given for some rows only")
+        return analysis.control_report(x, self.sample_rate, tempo=tempo, key=key, device=self.device)
+
     # generation.py:152-192
     def get_conditioning(self, cond):
         """as written in the reference: input-concat entries are read as ``cond[key][0]`` -- the FIRST batch element --
