@@ -124,11 +124,17 @@ class LatentCollate:
     batch, in front of ``normalize`` and the encoder, with the clip's valid sample count) and put into a COPY of its metadata.  Values
     the JSON has win; a clip the analyser cannot decide (tempo 0, key -1) gets no entry, so the conditioner's own rule for a missing key
     applies.  The results come to the host in one copy per batch, behind the enqueued encode call.  ``analyzer``: a stand-in for
-    ``analysis.analyze`` with its signature."""
+    ``analysis.analyze`` with its signature.  ``augment`` (not in the reference): a ``jen1_amd.effects.Augment``; every item gets one
+    draw (rate, semitones), the items of one draw are stretched and shifted together on the converted batch (in front of the analyser,
+    ``normalize`` and the encoder) and cropped or zero-padded back to the batch's length, a clip's valid sample count becomes
+    ``min(n_out, round(valid / rate))``, and the ``tempo`` / ``key`` entries the JSON has are moved with the draw in a COPY of the
+    metadata -- measured entries are measured on the augmented audio and need no such step.  None (the default) changes nothing.
+    ``augmenter``: a stand-in for ``effects.stretch_and_shift`` called as ``augmenter(wav, sr, rate=, semitones=)``."""
 
     def __init__(self, audio_encoder, device="cuda", sample_duration=10, convert_audio: Optional[Callable] = None,
                  normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None, with_lengths: bool = False, analyze=(),
-                 analyzer: Optional[Callable] = None):
+                 analyzer: Optional[Callable] = None, augment=None, augmenter: Optional[Callable] = None):
+        self.augment, self._augmenter = augment, augmenter
         self.analyze = tuple(analyze)
         bad = [a for a in self.analyze if a not in ("tempo", "key")]
         if bad:
@@ -162,6 +168,32 @@ class LatentCollate:
             return self._analyzer(wav, rate, lengths=valid)
         from . import analysis
         return analysis.analyze(wav, rate, lengths=valid, device=self.device)
+
+    def augment_batch(self, wav, rate, speed, semitones):
+        if self._augmenter is not None:
+            return self._augmenter(wav, rate, rate=speed, semitones=semitones)
+        from . import effects
+        return effects.stretch_and_shift(wav, rate, rate=speed, semitones=semitones, device=self.device)
+
+    def apply_augment(self, out, rate, valid, meta):
+        """one draw per item, the items of one draw as one batch: ``out`` changed in place, (valid, meta) of the augmented clips"""
+        n_out = int(out.shape[-1])
+        draws = [self.augment.draw() for _ in meta]
+        groups = {}
+        for i, d in enumerate(draws):
+            groups.setdefault(d, []).append(i)
+        valid, meta = list(valid), list(meta)
+        for (speed, semis), idx in groups.items():
+            if float(speed) == 1.0 and int(semis) == 0:
+                continue
+            y = self.augment_batch(out[idx], rate, speed, semis).to(self.device, torch.float32)
+            n = min(n_out, int(y.shape[-1]))
+            out[idx] = 0.0
+            out[idx, :, :n] = y[:, :, :n]
+            for i in idx:
+                valid[i] = min(n_out, int(round(valid[i] / float(speed))))
+                meta[i] = self.augment.transform_metadata(meta[i], speed, semis)
+        return valid, meta
 
     def fill_metadata(self, meta, measured):
         """copies of ``meta`` with the entries of ``self.analyze`` they lack, from one device-to-host copy of the measured [tempo; key]"""
@@ -209,14 +241,16 @@ class LatentCollate:
             out[idx, :, :n] = conv[:, :, :n].to(self.device, torch.float32)
             for i, c in zip(idx, clips):
                 valid[i] = min(n, -(-c.shape[-1] * rate // sr))
+        meta = [meta for _chunk, _sr, meta in batch]
+        if self.augment is not None:
+            valid, meta = self.apply_augment(out, rate, valid, meta)
         measured = None
-        if self.analyze and any(name not in meta for _chunk, _sr, meta in batch for name in self.analyze):
+        if self.analyze and any(name not in md for md in meta for name in self.analyze):
             measured = self.analyze_batch(out, rate, valid)                  # device tensors: nothing waits here
         if self.normalize is not None:             # the level of every clip, set in one call on the padded batch (not in the reference)
             from . import audio
             out = audio.normalize_audio(out, rate, strategy=self.normalize, target_lufs=self.target_lufs, limit="clip", device=self.device)
         emb = ae.encode_latents(out)[0]
-        meta = [meta for _chunk, _sr, meta in batch]
         if measured is not None:
             meta = self.fill_metadata(meta, measured)
         lengths = [self.valid_frames(v, n_out, emb.shape[-1]) for v in valid] if self.with_lengths else None
@@ -243,12 +277,13 @@ class LatentLoader:
 def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sample_duration, aug_shift, batch_size: int = 50, shuffle: bool = True,
                     split_ratio=0.8, device="cpu", durations_path=None, cumsum_path=None, audio_file_txt_path=None, *, audio_encoder=None,
                     num_workers: int = 0, dataset_cls=None, normalize: Optional[str] = None, target_lufs=-14.0, normalizer=None,
-                    with_lengths: bool = False, analyze=()):
+                    with_lengths: bool = False, analyze=(), augment=None):
     """(train loader, validation loader) of ``(emb, metadata)`` batches.  ``dataset_dir``: one folder (split by ``split_ratio``) or a
     (train, validation) pair.  ``audio_encoder`` (an ``EncodecHIP``) installs ``LatentCollate`` on ``device``; without it the loaders yield
     the raw item lists.  ``num_workers`` > 0 reads the files in spawned worker processes, which never touch the GPU.  ``dataset_cls``: a
     ``MusicDataset`` subclass to build instead (one that selects or tags items; importable by name when workers are used).  ``normalize`` /
-    ``target_lufs``, ``normalizer``, ``with_lengths`` and ``analyze`` are handed to ``LatentCollate``."""
+    ``target_lufs``, ``normalizer``, ``with_lengths`` and ``analyze`` are handed to ``LatentCollate``; ``augment`` (a
+    ``jen1_amd.effects.Augment``) to the training loader's only."""
     cls = MusicDataset if dataset_cls is None else dataset_cls
 
     def make(folder):
@@ -261,10 +296,13 @@ def get_dataloaders(dataset_dir, sr, channels, min_duration, max_duration, sampl
         train_dataset, val_dataset = random_split(dataset, [train_size, len(dataset) - train_size])
     else:
         train_dataset, val_dataset = make(dataset_dir[0]), make(dataset_dir[1])
-    fn = None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs,
-                                                             normalizer=normalizer, with_lengths=with_lengths, analyze=analyze)
+    def collate_fn(aug):
+        return None if audio_encoder is None else LatentCollate(audio_encoder, device, sample_duration, normalize=normalize, target_lufs=target_lufs,
+                                                                   normalizer=normalizer, with_lengths=with_lengths, analyze=analyze, augment=aug)
+    fn = collate_fn(None)
+    train_fn = fn if augment is None else collate_fn(augment)
     kw = dict(batch_size=batch_size, collate_fn=collate, drop_last=True, num_workers=num_workers)
     if num_workers > 0:
         kw["multiprocessing_context"] = "spawn"        # never fork a process that has initialised the GPU
-    return (LatentLoader(DataLoader(train_dataset, shuffle=shuffle, **kw), fn),
+    return (LatentLoader(DataLoader(train_dataset, shuffle=shuffle, **kw), train_fn),
             LatentLoader(DataLoader(val_dataset, shuffle=False, **kw), fn))

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip", "latent_norm.hip", "vggish.hip", "analysis.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip", "latent_norm.hip", "vggish.hip", "analysis.hip", "vocoder.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -335,6 +335,17 @@ ANALYSIS_SYMBOLS = {
     "jen1_key": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, c_int, _P]),
 }
 
+# every symbol include/jen1_vocoder.h declares (inverse STFT with a gathered overlap-add, phase vocoder: csrc/vocoder.hip; window_host of
+# jen1_istft: a HOST pointer)
+VOCODER_SYMBOLS = {
+    "jen1_istft_tile_samples": (c_int, [c_int]),
+    "jen1_istft_tile_frames": (c_int, [c_int]),
+    "jen1_istft": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int, _P]),
+    "jen1_vocoder_frames": (c_int64, [c_int64, C.c_double]),
+    "jen1_phase_vocoder_tile_frames": (c_int, []),
+    "jen1_phase_vocoder": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, C.c_double, _P]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -349,7 +360,7 @@ def build(verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "jen1_hip.h"), os.path.join(INCLUDE, "jen1_train.h"),
             os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h"), os.path.join(INCLUDE, "jen1_t5.h"), os.path.join(INCLUDE, "jen1_spectral.h"),
-            os.path.join(INCLUDE, "jen1_fad.h"), os.path.join(INCLUDE, "jen1_analysis.h")]
+            os.path.join(INCLUDE, "jen1_fad.h"), os.path.join(INCLUDE, "jen1_analysis.h"), os.path.join(INCLUDE, "jen1_vocoder.h")]
     hdrs += [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h") and h != "common.h"]
     deps = srcs + hdrs
     if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -398,7 +409,7 @@ def load() -> C.CDLL:
     # pulls in the system runtime instead, and two runtimes in one process fail with "no ROCm-capable device".
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS, **SPECTRAL_SYMBOLS, **FAD_SYMBOLS, **ANALYSIS_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS, **SPECTRAL_SYMBOLS, **FAD_SYMBOLS, **ANALYSIS_SYMBOLS, **VOCODER_SYMBOLS}.items():
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,10 @@ evaluation of its output at all.
     window      "hann" (periodic, ``torch.hann_window(win_length)``) or a 1-D tensor of win_length values; shorter than n_fft it is centred
                 in the frame with (n_fft - win_length) // 2 zeros on its left
     stft        complex64 [..., n_fft / 2 + 1, frames], not normalised, one-sided
+    istft       ``torch.istft`` of that layout: the windowed inverse frames overlap-added in a fixed order and divided by the summed
+                squared window (refused where that sum vanishes: NOLA); float32 [..., length]
+    vocoder     ``phase_vocoder`` resamples the frame axis by ``rate`` (the textbook phase vocoder, as ``torchaudio.functional.phase_vocoder``):
+                magnitudes interpolated, phase advances accumulated exactly; complex64 [..., n_fft / 2 + 1, len(arange(0, frames, rate))]
     mel         ``mel_filterbank`` restates ``torchaudio.functional.melscale_fbanks`` (htk / slaney scale, optional slaney norm) in float64;
                 the kernel gets it as a banded matrix (per band a bin range and its weights) and knows nothing of mel
     distances   sc = sqrt(sum (|X| - |Y|)^2 / sum |Y|^2),  log_mag = mean |log max(|X|, floor) - log max(|Y|, floor)|  over bins and frames,
@@ -287,6 +291,99 @@ def mel_spectrogram(wav: torch.Tensor, sr: int, n_fft: int = 2048, hop: int = 51
                              lo.data_ptr(), hi.data_ptr(), off.data_ptr(), w.data_ptr(), int(n_mels), nw, rows, n, n_fft, hop, win_length,
                              int(bool(center)), kind, LOGS.index(log), float(floor), torch.cuda.current_stream(dev).cuda_stream), "jen1_mel")
     return out
+
+
+def _check_spec(spec: torch.Tensor, what: str) -> int:
+    """n_fft of a complex64 spectrogram [..., n_fft / 2 + 1, frames]"""
+    if not torch.is_tensor(spec) or spec.dtype != torch.complex64:
+        raise TypeError(f"{what}: spectrograms are complex64 tensors, not {getattr(spec, 'dtype', type(spec))}")
+    if spec.requires_grad:
+        raise ValueError(f"{what}: there is no autograd; detach the input")
+    if spec.dim() < 2 or int(spec.shape[-1]) < 1:
+        raise ValueError(f"{what}: a spectrogram needs a bin axis and a frame axis that is not empty, not shape {tuple(spec.shape)}")
+    n_fft = 2 * (int(spec.shape[-2]) - 1)
+    if n_fft not in N_FFTS:
+        raise ValueError(f"{what}: {int(spec.shape[-2])} bins are not n_fft / 2 + 1 of an n_fft in {N_FFTS}")
+    return n_fft
+
+
+def vocoder_frame_count(frames: int, rate: float) -> int:
+    """frames of ``phase_vocoder`` for ``frames`` input frames: ``len(numpy.arange(0, frames, rate))``, by the library's own rule"""
+    from . import lib as L
+    if not (float(rate) > 0.0 and math.isfinite(float(rate))):
+        raise ValueError(f"rate = {rate} must be positive and finite")
+    count = int(L.load().jen1_vocoder_frames(int(frames), float(rate)))
+    if count < 1:
+        raise ValueError(f"rate = {rate} gives no usable frame count from {frames} frames")
+    return count
+
+
+def istft(spec: torch.Tensor, n_fft: int, hop: Optional[int] = None, win_length: Optional[int] = None, window="hann", center: bool = True,
+          length: Optional[int] = None, device="cuda") -> torch.Tensor:
+    """``torch.istft(spec, n_fft, hop, win_length, window, center=center, length=length)`` of a one-sided complex64 ``[..., n_fft / 2 + 1,
+    frames]``: float32 ``[..., length]`` on ``device``.  ``length`` defaults to ``hop * (frames - 1)`` (plus n_fft with center=False);
+    a longer one is filled with zeros past the last frame.  A window whose squared overlap-add vanishes somewhere (NOLA) is refused."""
+    from . import lib as L
+    got = _check_spec(spec, "istft")
+    _check_n_fft(n_fft)
+    n_fft = int(n_fft)
+    if got != n_fft:
+        raise ValueError(f"istft: the input has {int(spec.shape[-2])} bins, n_fft = {n_fft} needs {n_fft // 2 + 1}")
+    if win_length is None:
+        win_length = int(window.numel()) if torch.is_tensor(window) else n_fft
+    win_length = int(win_length)
+    if win_length > n_fft or win_length < 1:
+        raise ValueError(f"win_length = {win_length} must be in [1, n_fft = {n_fft}]")
+    hop = n_fft // 4 if hop is None else int(hop)
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"hop = {hop} must be in [1, n_fft = {n_fft}]")
+    if torch.is_tensor(window):
+        if window.dim() != 1 or int(window.numel()) != win_length:
+            raise ValueError(f"window of shape {tuple(window.shape)} must be 1-D with win_length = {win_length} values")
+        host = window.detach().to("cpu", torch.float32).contiguous().numpy()
+    elif window == "hann":
+        host = hann_window(win_length)
+    else:
+        raise ValueError(f"unknown window {window!r}: 'hann' or a 1-D tensor")
+    frames = int(spec.shape[-1])
+    length = hop * (frames - 1) + (0 if center else n_fft) if length is None else int(length)
+    if length < 1:
+        raise ValueError(f"istft: length = {length} must be positive ({frames} frames at hop {hop})")
+    dev = _device(device, "istft")
+    lib = L.load()
+    lead = tuple(spec.shape[:-2])
+    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    x = torch.view_as_real(spec.to(dev).contiguous())
+    out = torch.empty(lead + (length,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.jen1_istft(x.data_ptr(), out.data_ptr(), length, _window(window, win_length, dev).data_ptr(), host.ctypes.data,
+                               _twiddle(n_fft, dev).data_ptr(), rows, frames, length, n_fft, hop, win_length, int(bool(center)),
+                               torch.cuda.current_stream(dev).cuda_stream), "jen1_istft")
+    return out
+
+
+def phase_vocoder(spec: torch.Tensor, rate: float, hop: int, device="cuda") -> torch.Tensor:
+    """``torchaudio.functional.phase_vocoder(spec, rate, 2 pi hop k / n_fft)``: the frame axis of a complex64 ``[..., n_fft / 2 + 1,
+    frames]`` resampled at steps of ``rate`` frames (rate > 1: fewer frames, faster), complex64 ``[..., n_fft / 2 + 1, J]`` on ``device``.
+    ``hop`` is the hop the spectrogram was taken with."""
+    from . import lib as L
+    n_fft = _check_spec(spec, "phase_vocoder")
+    if not 1 <= int(hop) <= n_fft:
+        raise ValueError(f"hop = {hop} must be in [1, n_fft = {n_fft}]")
+    frames = int(spec.shape[-1])
+    if not (float(rate) > 0.0 and math.isfinite(float(rate))):
+        raise ValueError(f"rate = {rate} must be positive and finite")
+    dev = _device(device, "phase_vocoder")
+    lib = L.load()
+    count = vocoder_frame_count(frames, rate)
+    lead = tuple(spec.shape[:-2])
+    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    x = torch.view_as_real(spec.to(dev).contiguous())
+    out = torch.empty(tuple(spec.shape[:-1]) + (count, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.jen1_phase_vocoder(x.data_ptr(), out.data_ptr(), rows, frames, n_fft, int(hop), float(rate),
+                                       torch.cuda.current_stream(dev).cuda_stream), "jen1_phase_vocoder")
+    return torch.view_as_complex(out)
 
 
 # ------------------------------------------------------------------------------------------------------------- distances
