@@ -446,6 +446,15 @@ int jen1_adamw_ema_step_counted(float* p, const float* g, float* m, float* v, in
  * [B * 128] text rows into the [B][129] rows of a K/V cache (rows_in = 0: orow = m).  K must be a multiple of 64 (bf16) / 32
  * (f32), every n0_g and N_g a multiple of 128 when there is more than one group.  ``groups`` is a DEVICE table; NULL = one
  * group described by the inline fields c / bias / ldc (nothing to copy to the device: usable while a graph is being recorded).
+ * The epilogue is applied in the order written: alpha scales the sum only, the bias is added before row_scale, so a row whose
+ * row_scale is 0 comes out as zeros, bias included (accumulate then adds those zeros to what C held).
+ * Widths and alignment: results leave 4 columns at a time, so the width of a single group (Ntot) and every ldc are multiples of 4
+ * with ldc >= N_g, every c is 8-byte aligned (16-byte when the output is float32) and every bias 16-byte aligned.  The call checks
+ * this for one group (Ntot) and for the inline fields; a device table is the caller's promise (jen1_amd.lib.bgemm_group_table checks it
+ * when it builds one).
+ * Row map: rows_in > 0 needs rows_out >= rows_in (a smaller rows_out would map two GEMM rows onto one output row) and M < 2^22 (the
+ * kernels divide by rows_in in float32, which is exact below that); output rows orow with orow % rows_out >= rows_in are not written.
+ * group_align is 0 or a multiple of 128, on every tile form: a table whose boundaries are finer is refused.
  */
 typedef struct jen1_bgemm_group {
   void* c;                 /* output of the group: compute dtype, or float32 when c_f32 */
@@ -479,7 +488,8 @@ int jen1_big_gemm_tn_store(const void* a, const void* b, float* c, int M, int N,
  * (+ residual[row][n]); rows outside [0, T_in) count as zeros.  W_tap = w + tap * w_tap_stride (tap_rev: taps - 1 - tap), [co][ld_w] with the
  * ci input channels contiguous.  The forward and (stride 1, pad' = taps - 1 - pad, tap_rev) data-gradient passes of `_Conv1d`
  * (blocks.py:34-53) over many rows: the long levels of the training pass.  ci must be a multiple of 8 (the last 64-channel K step of a tap
- * may be ragged: its missing chunks are not read). */
+ * may be ragged: its missing chunks are not read).  Results leave 4 columns at a time: co and ld_y are multiples of 4, y and residual
+ * (which shares y's pitch) 8-byte aligned, bias 16-byte aligned; B * T_out < 2^22. */
 int jen1_big_gemm_conv(const void* x, const void* w, const float* bias, const void* residual, void* y, int B, int T_in, int T_out, int ci, int co,
                        int taps, int stride, int pad, int tap_rev, int ld_x, int ld_w, int w_tap_stride, int ld_y, const int32_t* shift_b /* [B] added to
                        the row shift tap - pad per batch element (causal and centred clips in one pass, blocks.py:45-50), or NULL */,

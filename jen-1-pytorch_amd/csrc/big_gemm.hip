@@ -1195,7 +1195,20 @@ extern "C" int jen1_big_gemm(const jen1_bgemm_args* a, void* stream) {
   JEN1_CHECK(a->M >= 1 && a->Ntot >= 1 && a->K >= bk && a->K % bk == 0, "big_gemm: K=%d must be a positive multiple of %d", a->K, bk);
   JEN1_CHECK(a->lda >= a->K && a->ldb >= a->K && (a->lda * es) % 16 == 0 && (a->ldb * es) % 16 == 0, "big_gemm: row pitches must be 16-byte multiples >= K");
   JEN1_CHECK((int64_t)a->M * a->lda * es < ((int64_t)1 << 31) && (int64_t)a->Ntot * a->ldb * es < ((int64_t)1 << 31), "big_gemm: operand too large for 31-bit offsets");
-  JEN1_CHECK(a->n_groups == 1 || a->Ntot % BN == 0, "big_gemm: stacked groups need 128-column multiples");
+  const int ng = a->groups ? a->n_groups : 1;
+  JEN1_CHECK(ng == 1 || a->Ntot % BN == 0, "big_gemm: stacked groups need 128-column multiples");
+  JEN1_CHECK(ng == 1 || (a->group_align >= 0 && a->group_align % BN == 0), "big_gemm: group_align=%d must be a multiple of 128 (0 = 128)", a->group_align);
+  // the epilogues store 4 columns at once (8 bytes of bf16, 16 of float32): widths, pitches and bases must keep such a store inside the row
+  JEN1_CHECK(ng > 1 || a->Ntot % 4 == 0, "big_gemm: the width of a single group (%d) must be a multiple of 4", a->Ntot);
+  if (!a->groups) {
+    const uintptr_t sb = (a->c_f32 || a->dtype == JEN1_F32) ? 16 : 8;
+    JEN1_CHECK(a->ldc >= a->Ntot && a->ldc % 4 == 0, "big_gemm: ldc=%d must be a multiple of 4 and >= %d", a->ldc, a->Ntot);
+    JEN1_CHECK(reinterpret_cast<uintptr_t>(a->c) % sb == 0 && reinterpret_cast<uintptr_t>(a->bias) % 16 == 0,
+               "big_gemm: c must be %d-byte aligned and bias 16-byte aligned", (int)sb);
+  }
+  // the row map divides in float32: exact below 2^22 rows (as in the convolution forms); rows_out < rows_in would map two rows onto one
+  JEN1_CHECK(a->rows_in == 0 || (a->rows_in > 0 && a->rows_out >= a->rows_in && a->M < (1 << 22)),
+             "big_gemm: a row map needs rows_out >= rows_in > 0 and M < 2^22 (rows_in=%d rows_out=%d M=%d)", a->rows_in, a->rows_out, a->M);
   BArgs g;
   memset(&g, 0, sizeof(g));
   g.a = a->a; g.b = a->b; g.groups = reinterpret_cast<const BGroup*>(a->groups); g.row_scale = a->row_scale;
@@ -1227,6 +1240,8 @@ extern "C" int jen1_big_gemm_conv(const void* x, const void* w, const float* bia
   JEN1_CHECK(ci >= 8 && ci % 8 == 0, "big_gemm_conv: the input channels (%d) must be a multiple of 8 (the columns [ci, pitch) are not read)", ci);
   JEN1_CHECK(co >= 4 && co % 4 == 0 && ld_x >= ci && ld_w >= ci && ld_y >= co && ld_x % 8 == 0 && ld_w % 8 == 0 && ld_y % 4 == 0,
              "big_gemm_conv: widths / pitches (ci, ld_x, ld_w multiples of 8 elements; co, ld_y of 4)");
+  JEN1_CHECK(reinterpret_cast<uintptr_t>(y) % 8 == 0 && reinterpret_cast<uintptr_t>(residual) % 8 == 0 && reinterpret_cast<uintptr_t>(bias) % 16 == 0,
+             "big_gemm_conv: y and residual must be 8-byte aligned, bias 16-byte aligned (the epilogue moves 4 columns at once)");
   JEN1_CHECK(w_tap_stride >= co * ld_w || taps == 1, "big_gemm_conv: tap matrices overlap");
   const int64_t M = (int64_t)B * T_out, Mx = (int64_t)B * T_in;
   JEN1_CHECK(M < ((int64_t)1 << 22) && Mx * ld_x * 2 < 0x7ffffff0ll && (int64_t)taps * w_tap_stride * 2 < ((int64_t)1 << 31) && M * ld_y * 2 < ((int64_t)1 << 40),

@@ -285,7 +285,8 @@ class Weights:
 
 def _bgemm_parts(groups):
     """column groups (c, bias, n0, N, ldc) of a stacked jen1_big_gemm operand -> launches: all groups in one launch when every
-    n0 and N is a multiple of the kernel's 128-column tile, else one launch per group (a single group may have any width)"""
+    n0 and N is a multiple of the kernel's 128-column tile, else one launch per group (a single group's width must be a multiple of 4, like every ldc: the kernel stores 4 columns at once and
+    refuses other widths)"""
     if all(n0 % 128 == 0 and N % 128 == 0 for _, _, n0, N, _ in groups):
         return [groups]
     return [[gr] for gr in groups]

@@ -436,10 +436,15 @@ def ola_seg_table(segs, device):
 
 
 def bgemm_group_table(groups, device):
-    """device copy of a ``jen1_bgemm_group`` table: ``groups`` = [(c_ptr, bias_ptr or None, n0, N, ldc)]"""
+    """device copy of a ``jen1_bgemm_group`` table: ``groups`` = [(c_ptr, bias_ptr or None, n0, N, ldc)].  The library cannot read a
+    device table on the host, so the width and alignment rules of include/jen1_hip.h are checked here: N and ldc multiples of 4,
+    ldc >= N, c 8-byte aligned (a float32 output needs 16: the caller's), bias 16-byte aligned."""
     import numpy as np
     import torch
     arr = (BGemmGroup * len(groups))()
     for i, (c, bias, n0, N, ldc) in enumerate(groups):
+        if N < 4 or N % 4 or ldc % 4 or ldc < N or n0 < 0 or c % 8 or (bias or 0) % 16:
+            raise Jen1HipError(f"bgemm_group_table: group {i} (n0={n0} N={N} ldc={ldc}): N and ldc must be multiples of 4 with ldc >= N, "
+                               "c 8-byte and bias 16-byte aligned")
         arr[i].c, arr[i].bias, arr[i].n0, arr[i].N, arr[i].ldc = c, bias, n0, N, ldc
     return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
