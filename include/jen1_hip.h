@@ -390,7 +390,8 @@ int jen1_step_tail_ms(const void* net, const float* x, float* hist, const float*
 int jen1_cfg_combine(const void* net, float* out, int B, int C, int T, int ld, float embedding_scale, int scale_cfg,
                      float scale_phi, int dtype, void* stream);
 
-/* zero `bytes` bytes at p on the stream (statistics arena reset; capturable). */
+/* zero `bytes` bytes at p on the stream (statistics arena reset; capturable).  p and bytes are multiples of 4 (refused otherwise);
+ * bytes = 0 launches nothing. */
 int jen1_memset_zero(void* p, int64_t bytes, void* stream);
 
 /*
@@ -400,6 +401,17 @@ int jen1_memset_zero(void* p, int64_t bytes, void* stream);
  *                     then torch.optim.AdamW.step() number `step` (1-based) with decoupled weight decay, in place.
  *                     skip_nonfinite: a non-finite norm leaves p, m, v untouched (GradScaler.step semantics).
  * gnorm_sq is read on the device, so clip + update needs no host synchronisation.
+ * Operands: p, g, m, v (and g of the norm) start on 16-byte boundaries, n > 0 is any length (a tail of n % 4 elements is handled),
+ * step >= 1, 0 <= beta1, beta2 < 1; anything else is refused before a launch.  g and gnorm_sq are only read.
+ * Order of one element: p *= 1 - lr wd (decoupled, before the update); m = beta1 m + (1 - beta1) g'; v = beta2 v + (1 - beta2) g'^2;
+ * p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).
+ * The norm: `out` accumulates, so two calls on two buffers give the sum over both; a call gives the same bits every time, whatever
+ * grids the scratch served before (block partials in fixed slots, summed in a fixed order by the last block, which leaves the ticket
+ * at 0).  A NaN or inf anywhere in g, the tail included, makes `out` non-finite.
+ * skip_nonfinite looks at sqrt(gnorm_sq[0]) only: inf and NaN both drop the step, also with max_norm <= 0 (clipping off); with
+ * gnorm_sq NULL there is nothing to look at and no step is ever dropped.  With skip_nonfinite off a non-finite norm is the caller's
+ * problem: an inf norm gives the coefficient 0, a NaN norm leaves it at 1 (the comparison c < 1 is false), and the non-finite
+ * gradient elements go into m, v and p either way.
  */
 int jen1_grad_sqnorm(const float* g, int64_t n, float* out, void* stream);
 /* the same with caller-owned scratch (jen1_grad_sqnorm_scratch_bytes() bytes, 16-byte aligned, zeroed ONCE by the caller; the kernel

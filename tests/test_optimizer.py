@@ -1,7 +1,9 @@
 """Optimiser step and gradient exchange (e).
 CPU: the oracle restatement against torch.optim.AdamW / clip_grad_norm_ / LinearLR (the reference uses exactly these:
 train.py:56-60, :84, trainer.py:144-149), the flat-buffer host logic, the bucketed mean all-reduce on gloo world-2.
-GPU: jen1_grad_sqnorm + jen1_adamw_step through the C ABI against the oracle and torch."""
+GPU: FusedAdamW.step, i.e. jen1_grad_sqnorm_ws + jen1_adamw_step_counted (caller-owned scratch, device step counter), against the
+oracle and torch over a few steps.  jen1_grad_sqnorm, jen1_adamw_step (host step number), jen1_adamw_ema_step_counted and
+jen1_memset_zero are driven entry by entry in tests/test_gpu_optimizer_forms.py."""
 import os
 import sys
 
