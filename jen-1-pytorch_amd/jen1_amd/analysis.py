@@ -15,11 +15,13 @@ in the batch a row sits.  There is no autograd and no fallback; neither ``torch.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Tuple
 
 import numpy as np
 import torch
 
+from . import audio_host as H
+from . import lib as L
 from . import spectral
 
 KEY_NAMES = ("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B",
@@ -29,7 +31,6 @@ KK_MINOR = (6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.
 TEMPO_TOLERANCE = 0.04                      # MIREX accuracy 1
 OCTAVE_FACTORS = (1.0, 2.0, 3.0, 0.5, 1.0 / 3.0)
 ANALYZE = ("tempo", "key")
-_chromas: Dict[tuple, torch.Tensor] = {}
 
 
 # ------------------------------------------------------------------------------------------------------------- host tables
@@ -38,7 +39,7 @@ def chroma_filterbank(sr: float, n_fft: int, a440: float = 440.0, centre_octave:
     in semitones (``pit[0] = pit[1] - 18``) and the width ``max(pit[k+1] - pit[k], 1)`` (the last: 1); class p gets
     ``exp(-0.5 (2 D / width)^2)`` with D the distance of pit[k] from p folded into [-6, 6); every column has unit L2 norm before the octave
     weight ``exp(-0.5 ((pit / 12 - centre_octave) / octave_width)^2)``; the rows are rolled by -3 (the pitch scale starts at A)."""
-    spectral._check_n_fft(n_fft)
+    H.check_n_fft(n_fft)
     if not float(sr) > 0 or not float(a440) > 0 or not float(octave_width) > 0:
         raise ValueError(f"chroma_filterbank needs positive sr, a440 and octave_width, not {sr}, {a440}, {octave_width}")
     n_fft = int(n_fft)
@@ -73,16 +74,12 @@ def frame_lengths(lengths, n: int, n_fft: int, hop: int, center: bool = True) ->
 
 # ------------------------------------------------------------------------------------------------------------- device side
 def _chroma_w(sr, n_fft: int, dev: torch.device) -> torch.Tensor:
-    key = (float(sr), int(n_fft), str(dev))
-    hit = _chromas.get(key)
-    if hit is None:
-        hit = _chromas[key] = torch.from_numpy(chroma_filterbank(sr, n_fft).astype(np.float32)).to(dev)
-    return hit
+    return H.device_table(dev, ("chroma", float(sr), int(n_fft)), lambda: torch.from_numpy(chroma_filterbank(sr, n_fft).astype(np.float32)).to(dev))
 
 
 def _mono(wav: torch.Tensor, sr: int, dev: torch.device, what: str) -> torch.Tensor:
     """[B, C, n] or [B, n] -> float32 [B, n] on dev; two channels are averaged by ``audio.convert_audio``"""
-    spectral._check_wave(wav, what)
+    spectral.check_wave(wav, what)
     if wav.dim() not in (2, 3):
         raise ValueError(f"{what} takes [B, C, n] or [B, n], not {tuple(wav.shape)}")
     x = wav.to(dev)
@@ -112,25 +109,21 @@ def music_features(wav: torch.Tensor, sr: int, n_fft: int = 2048, hop: int = 512
     """(onset float32 [B, F], chroma float32 [B, 12, F]) of ``wav`` ([B, C, n] or [B, n] at rate ``sr``) on ``device``: periodic Hann window
     of n_fft, center=True framing, the mel matrix of ``spectral.mel_filterbank(sr, n_fft, n_mels)`` in banded form and
     ``chroma_filterbank(sr, n_fft)``; one launch"""
-    from . import lib as L
     if not float(gamma) > 0.0:
         raise ValueError(f"gamma = {gamma} must be positive")
-    spectral._check_wave(wav, "music_features")
-    dev = spectral._device(device, "music_features")
+    spectral.check_wave(wav, "music_features")
+    dev = H.gpu_device(device, "music_features")
     x = _mono(wav, sr, dev, "music_features")
-    n_fft, hop, win_length, frames = spectral._framing(int(x.shape[-1]), n_fft, hop, None, "hann", True)
-    lib = L.load()
-    if int(n_mels) > int(lib.jen1_music_features_max_bands(n_fft)):
-        raise ValueError(f"n_mels = {n_mels}: at most {lib.jen1_music_features_max_bands(n_fft)} bands fit next to a transform of {n_fft}")
-    x, rows, n, stride = spectral._rows(x, dev)
-    lo, hi, off, w, nw = spectral._bank(sr, n_fft, n_mels, 0.0, None, "htk", None, dev)
-    onset = torch.empty((rows, frames), dtype=torch.float32, device=dev)
-    chroma = torch.empty((rows, 12, frames), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_music_features(x.data_ptr(), stride, onset.data_ptr(), chroma.data_ptr(), spectral._window("hann", win_length, dev).data_ptr(),
-                                        spectral._twiddle(n_fft, dev).data_ptr(), lo.data_ptr(), hi.data_ptr(), off.data_ptr(), w.data_ptr(),
-                                        int(n_mels), nw, _chroma_w(sr, n_fft, dev).data_ptr(), float(gamma), rows, n, n_fft, hop, win_length, 1,
-                                        torch.cuda.current_stream(dev).cuda_stream), "jen1_music_features")
+    fr = H.framing(n_fft, hop, None, "hann", True, n=int(x.shape[-1]))
+    most = int(L.load().jen1_music_features_max_bands(fr.n_fft))
+    if int(n_mels) > most:
+        raise ValueError(f"n_mels = {n_mels}: at most {most} bands fit next to a transform of {fr.n_fft}")
+    x, rows, n, stride = H.rows_of(x, dev)
+    bands = spectral.mel_bands(sr, fr.n_fft, n_mels, 0.0, None, "htk", None, dev)
+    onset = torch.empty((rows, fr.frames), dtype=torch.float32, device=dev)
+    chroma = torch.empty((rows, 12, fr.frames), dtype=torch.float32, device=dev)
+    H.launch(dev, "jen1_music_features", x.data_ptr(), stride, onset.data_ptr(), chroma.data_ptr(), *H.frame_tables(fr, "hann", dev), *bands.abi(),
+             _chroma_w(sr, fr.n_fft, dev).data_ptr(), float(gamma), *fr.abi(rows, n))
     return onset, chroma
 
 
@@ -139,10 +132,9 @@ def tempo(onset: torch.Tensor, fps: float, frames=None, bpm_min: float = 40.0, b
     """(tempo float32 [B] in BPM, strength float32 [B]) of onset envelopes float32 [B, F] on a GPU, ``fps`` frames per second; ``frames``:
     the valid frames per row (int32 tensor or a sequence; None: all).  ``return_acf``: also the autocorrelation float64 [B, lags] and
     the lag of its first column."""
-    from . import lib as L
     if not torch.is_tensor(onset) or onset.dtype != torch.float32 or onset.dim() != 2 or int(onset.shape[1]) < 1:
         raise ValueError(f"tempo takes a float32 [B, F] envelope, not {getattr(onset, 'dtype', type(onset))} {tuple(getattr(onset, 'shape', ()))}")
-    dev = spectral._device(onset.device, "tempo")
+    dev = H.gpu_device(onset.device, "tempo")
     lib = L.load()
     lags = int(lib.jen1_tempo_lags(float(fps), float(bpm_min), float(bpm_max)))
     if lags < 1 or not float(prior_bpm) > 0 or not float(prior_octaves) > 0:
@@ -153,11 +145,9 @@ def tempo(onset: torch.Tensor, fps: float, frames=None, bpm_min: float = 40.0, b
     out = torch.empty((2, rows), dtype=torch.float32, device=dev)
     acf = torch.empty((rows, lags), dtype=torch.float64, device=dev) if return_acf else None
     nbytes = int(lib.jen1_tempo_workspace_bytes(rows, float(fps), float(bpm_min), float(bpm_max)))
-    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_tempo(o.data_ptr(), stride, fr.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), None if acf is None else acf.data_ptr(),
-                               rows, float(fps), float(bpm_min), float(bpm_max), float(prior_bpm), float(prior_octaves), work.data_ptr(), nbytes,
-                               torch.cuda.current_stream(dev).cuda_stream), "jen1_tempo")
+    work = H.workspace(nbytes, dev)
+    H.launch(dev, "jen1_tempo", o.data_ptr(), stride, fr.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), None if acf is None else acf.data_ptr(),
+             rows, float(fps), float(bpm_min), float(bpm_max), float(prior_bpm), float(prior_octaves), work.data_ptr(), nbytes)
     if return_acf:
         return out[0], out[1], acf, int(np.ceil(60.0 * float(fps) / float(bpm_max))) - 1
     return out[0], out[1]
@@ -166,11 +156,9 @@ def tempo(onset: torch.Tensor, fps: float, frames=None, bpm_min: float = 40.0, b
 def key(chroma: torch.Tensor, frames=None, return_profile: bool = False):
     """(key int32 [B], strength float32 [B]) of chromagrams float32 [B, 12, F] on a GPU; ``return_profile``: also the time sums float64
     [B, 12] and the 24 correlations float32 [B, 24]"""
-    from . import lib as L
     if not torch.is_tensor(chroma) or chroma.dtype != torch.float32 or chroma.dim() != 3 or int(chroma.shape[1]) != 12 or int(chroma.shape[2]) < 1:
         raise ValueError(f"key takes a float32 [B, 12, F] chromagram, not {getattr(chroma, 'dtype', type(chroma))} {tuple(getattr(chroma, 'shape', ()))}")
-    dev = spectral._device(chroma.device, "key")
-    lib = L.load()
+    dev = H.gpu_device(chroma.device, "key")
     c = chroma.contiguous()
     rows, stride = int(c.shape[0]), int(c.shape[2])
     fr = _frames_arg(frames, rows, stride, dev)
@@ -178,9 +166,7 @@ def key(chroma: torch.Tensor, frames=None, return_profile: bool = False):
     st = torch.empty((rows,), dtype=torch.float32, device=dev)
     prof = torch.empty((rows, 12), dtype=torch.float64, device=dev)
     corr = torch.empty((rows, 24), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_key(c.data_ptr(), stride, fr.data_ptr(), k.data_ptr(), st.data_ptr(), prof.data_ptr(), corr.data_ptr(), rows,
-                             torch.cuda.current_stream(dev).cuda_stream), "jen1_key")
+    H.launch(dev, "jen1_key", c.data_ptr(), stride, fr.data_ptr(), k.data_ptr(), st.data_ptr(), prof.data_ptr(), corr.data_ptr(), rows)
     return (k, st, prof, corr) if return_profile else (k, st)
 
 

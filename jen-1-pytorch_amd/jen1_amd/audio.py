@@ -24,20 +24,19 @@ csrc/loudness.hip; see the second half of this file and DESIGN.md section 10e.
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
-
 import numpy as np
 import torch
+
+from . import audio_host as H
+from . import lib as L
 
 LOWPASS_FILTER_WIDTH = 6
 ROLLOFF = 0.99
 TABLE_MAX_BYTES = 256 * 1024     # cap on taps [n, W] float32: the table is meant to stay in L2; also keeps one frame's window within LDS
-_device_tables: Dict[Tuple[int, int, str], Tuple[int, int, int, int, torch.Tensor, torch.Tensor]] = {}
 
 
 def tile_frames(o: int, n: int) -> int:
     """frames (o inputs -> n outputs each) one workgroup of the kernel owns for this rate pair: the library's own rule"""
-    from . import lib as L
     return int(L.load().jen1_resample_tile_frames(int(o), int(n)))
 
 
@@ -82,37 +81,27 @@ def resample_table(sr: int, target_sr: int):
 
 
 def _tables(sr: int, target_sr: int, device: torch.device):
-    g = math.gcd(int(sr), int(target_sr))
-    key = (int(sr) // g, int(target_sr) // g, str(device))
-    hit = _device_tables.get(key)
-    if hit is None:
+    """(o, n, w, W, taps, first) of ``resample_table`` with the two arrays on ``device``"""
+    def make():
         o, n, w, taps, first = resample_table(sr, target_sr)
-        hit = _device_tables[key] = (o, n, w, taps.shape[1], torch.from_numpy(taps).to(device), torch.from_numpy(first).to(device))
-    return hit
+        return o, n, w, taps.shape[1], torch.from_numpy(taps).to(device), torch.from_numpy(first).to(device)
+    g = math.gcd(int(sr), int(target_sr))
+    return H.device_table(device, ("resample", int(sr) // g, int(target_sr) // g), make)
 
 
 def _run(wav: torch.Tensor, sr: int, target_sr: int, c_out: int, device) -> torch.Tensor:
     """wav [..., C, L] float32 -> [..., c_out, ceil(n L / o)] on the kernel of ``device``, returned on wav's device"""
-    from . import lib as L
     if wav.dtype != torch.float32:
         raise TypeError(f"waveforms are float32, not {wav.dtype}")
-    src = wav.device
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise L.Jen1HipError(f"the resampler runs on a GPU, not on {dev}: there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    lib = L.load()
+    dev = H.gpu_device(device, "the resampler")
     lead, c_in, n_in = tuple(wav.shape[:-2]), int(wav.shape[-2]), int(wav.shape[-1])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
     o, n, w, W, taps, first = _tables(sr, target_sr, dev)
     n_out = -(-n * n_in // o)
     x = wav.to(dev).contiguous()
     y = torch.empty(lead + (c_out, n_out), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_resample(x.data_ptr(), y.data_ptr(), taps.data_ptr(), first.data_ptr(), rows, c_in, c_out, n_in, n_out,
-                                  o, n, w, W, torch.cuda.current_stream(dev).cuda_stream), "jen1_resample")
-    return y.to(src)
+    H.launch(dev, "jen1_resample", x.data_ptr(), y.data_ptr(), taps.data_ptr(), first.data_ptr(), math.prod(lead), c_in, c_out, n_in, n_out,
+             o, n, w, W)
+    return y.to(wav.device)
 
 
 def resample(wav: torch.Tensor, sr: int, target_sr: int, device="cuda") -> torch.Tensor:
@@ -185,7 +174,6 @@ def hop_samples(sr: int) -> int:
 
 def chunk_samples(hop: int) -> int:
     """samples per chunk of the time-parallel K-weighting filter for this hop: the library's own rule"""
-    from . import lib as L
     return int(L.load().jen1_kweight_chunk(int(hop)))
 
 
@@ -200,38 +188,25 @@ def _check_wave(wav: torch.Tensor, what: str) -> None:
         raise ValueError(f"{what}: the time axis is empty")
 
 
-def _device(device, what: str) -> torch.device:
-    from . import lib as L
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise L.Jen1HipError(f"{what} runs on a GPU, not on {dev}: there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def _measure(x: torch.Tensor, sr: int, gate: bool = True):
-    """x [rows, C, L] float32, contiguous, on a GPU (the current device) -> (lufs float64 [rows] or None, stats float64 [rows, 2]):
-    the four launches of jen1_kweight_energy and, with ``gate``, jen1_loudness_gate behind them on the current stream"""
-    from . import lib as L
-    lib = L.load()
+    """x [rows, C, L] float32, contiguous, on a GPU -> (lufs float64 [rows] or None, stats float64 [rows, 2]): the four launches of
+    jen1_kweight_energy and, with ``gate``, jen1_loudness_gate behind them on the current stream of x's device"""
     rows, C, n = (int(s) for s in x.shape)
     hop = hop_samples(sr)
-    H = n // hop
+    blocks = n // hop
     dev = x.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    nbytes = int(lib.jen1_kweight_energy_workspace_bytes(rows, C, n, hop))
-    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
-    e = torch.empty((rows, C, H), dtype=torch.float64, device=dev)
+    nbytes = int(L.load().jen1_kweight_energy_workspace_bytes(rows, C, n, hop))
+    work = H.workspace(nbytes, dev)
+    e = torch.empty((rows, C, blocks), dtype=torch.float64, device=dev)
     stats = torch.empty((rows, 2), dtype=torch.float64, device=dev)
     sos = k_weighting(sr)
     coef = (L.C.c_double * 10)(*sos[0, [0, 1, 2, 4, 5]], *sos[1, [0, 1, 2, 4, 5]])
-    L.check(lib.jen1_kweight_energy(x.data_ptr(), e.data_ptr() if H else None, stats.data_ptr(), coef, rows, C, n, hop, work.data_ptr(), nbytes,
-                                    stream), "jen1_kweight_energy")
+    H.launch(dev, "jen1_kweight_energy", x.data_ptr(), e.data_ptr() if blocks else None, stats.data_ptr(), coef, rows, C, n, hop, work.data_ptr(),
+             nbytes)
     if not gate:
         return None, stats
     lufs = torch.empty((rows,), dtype=torch.float64, device=dev)
-    L.check(lib.jen1_loudness_gate(e.data_ptr() if H else None, lufs.data_ptr(), rows, C, H, hop, stream), "jen1_loudness_gate")
+    H.launch(dev, "jen1_loudness_gate", e.data_ptr() if blocks else None, lufs.data_ptr(), rows, C, blocks, hop)
     return lufs, stats
 
 
@@ -240,13 +215,9 @@ def loudness(wav: torch.Tensor, sr: int, device="cuda") -> torch.Tensor:
     wav's device.  ``-inf`` for a row shorter than one 400 ms block or with nothing above the gates."""
     _check_wave(wav, "loudness")
     hop_samples(sr)
-    src = wav.device
-    dev = _device(device, "the loudness meter")
-    lead = tuple(wav.shape[:-2])
-    x = wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:]))
-    with torch.cuda.device(dev):
-        lufs, _ = _measure(x, sr)
-    return lufs.reshape(lead).to(src)
+    dev = H.gpu_device(device, "the loudness meter")
+    lufs, _ = _measure(wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:])), sr)
+    return lufs.reshape(tuple(wav.shape[:-2])).to(wav.device)
 
 
 def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", target_lufs=-14.0, headroom_db=None, limit: str = "clip",
@@ -262,7 +233,6 @@ def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", targ
 
     ``target_lufs``: a float or a tensor ``[...]``, one target per row.  ``limit``: "none", "clip" (clamp to [-1, 1]) or "tanh".  The result is
     a new tensor on wav's device; ``return_gain=True`` returns ``(result, gain float32 [...])``."""
-    from . import lib as L
     if strategy not in STRATEGIES:
         raise ValueError(f"unknown strategy {strategy!r}: one of {STRATEGIES}")
     if limit not in LIMITS:
@@ -272,23 +242,19 @@ def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", targ
     lead = tuple(wav.shape[:-2])
     if torch.is_tensor(target_lufs) and tuple(target_lufs.shape) != lead:
         raise ValueError(f"target_lufs {tuple(target_lufs.shape)} must have one entry per row {lead}")
-    src = wav.device
-    dev = _device(device, "normalize_audio")
+    dev = H.gpu_device(device, "normalize_audio")
     x = wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:]))
     rows, C, n = (int(s) for s in x.shape)
     if torch.is_tensor(target_lufs):
-        target =target_lufs.to(dev, torch.float64).contiguous().reshape(-1)
+        target = target_lufs.to(dev, torch.float64).contiguous().reshape(-1)
     else:
         target = torch.full((rows,), float(target_lufs), dtype=torch.float64, device=dev)
     headroom = DEFAULT_HEADROOM_DB[strategy] if headroom_db is None else float(headroom_db)
-    lib = L.load()
-    with torch.cuda.device(dev):
-        lufs, stats = (None, None) if strategy == "clip" else _measure(x, sr, gate=strategy == "loudness")
-        y = torch.empty_like(x)
-        gain = torch.empty((rows,), dtype=torch.float32, device=dev)
-        L.check(lib.jen1_gain_apply(x.data_ptr(), y.data_ptr(), gain.data_ptr(), None if lufs is None else lufs.data_ptr(),
-                                    None if stats is None else stats.data_ptr(), target.data_ptr(), rows, C, n, STRATEGIES.index(strategy),
-                                    LIMITS.index(limit), headroom, float(energy_floor), torch.cuda.current_stream(dev).cuda_stream),
-                "jen1_gain_apply")
-    y = y.reshape(tuple(wav.shape)).to(src)
-    return (y, gain.reshape(lead).to(src)) if return_gain else y
+    lufs, stats = (None, None) if strategy == "clip" else _measure(x, sr, gate=strategy == "loudness")
+    y = torch.empty_like(x)
+    gain = torch.empty((rows,), dtype=torch.float32, device=dev)
+    H.launch(dev, "jen1_gain_apply", x.data_ptr(), y.data_ptr(), gain.data_ptr(), None if lufs is None else lufs.data_ptr(),
+             None if stats is None else stats.data_ptr(), target.data_ptr(), rows, C, n, STRATEGIES.index(strategy), LIMITS.index(limit), headroom,
+             float(energy_floor))
+    y = y.reshape(tuple(wav.shape)).to(wav.device)
+    return (y, gain.reshape(lead).to(wav.device)) if return_gain else y

@@ -25,6 +25,8 @@ from typing import Sequence, Tuple
 
 import torch
 
+from . import audio_host as H
+
 MAX_DENOMINATOR = 128
 
 
@@ -35,10 +37,10 @@ def semitone_ratio(semitones: float) -> Fraction:
 
 def _check(wav: torch.Tensor, rate: float, n_fft: int, what: str) -> None:
     from . import spectral
-    spectral._check_wave(wav, what)
+    spectral.check_wave(wav, what)
     if not (float(rate) > 0.0 and math.isfinite(float(rate))):
         raise ValueError(f"{what}: rate = {rate} must be positive and finite")
-    spectral._check_n_fft(n_fft)
+    H.check_n_fft(n_fft)
 
 
 def _fit(y: torch.Tensor, n: int) -> torch.Tensor:
@@ -64,7 +66,7 @@ def stretch_and_shift(wav: torch.Tensor, sr: int, rate: float = 1.0, semitones: 
     f = semitone_ratio(semitones)
     if float(rate) == 1.0 and f == 1:
         return wav
-    dev = spectral._device(device, "stretch_and_shift")
+    dev = H.gpu_device(device, "stretch_and_shift")
     n = int(wav.shape[-1])
     n_out = max(1, int(round(n / float(rate))))
     step = float(rate) * f.denominator / f.numerator            # frames of the input per frame of the output

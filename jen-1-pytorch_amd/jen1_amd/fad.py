@@ -23,8 +23,10 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import audio_host as H
+from . import lib as L
 from . import spectral
-from .normalizer import state_words
+from .normalizer import latent_moments, state_words
 
 SR = 16000
 N_FFT, HOP, WIN = 512, 160, 400
@@ -38,7 +40,6 @@ LINEAR_KEYS = ("embeddings.0", "embeddings.2", "embeddings.4")
 GRID = ((96, 64), (48, 32), (24, 16), (24, 16), (12, 8), (12, 8))       # H x W at the input of every convolution
 FLAT_HW = 6 * 4
 CHUNK = 256                         # examples per pass of the network (bounds the activations; results do not depend on it)
-_banks = {}
 
 
 # ------------------------------------------------------------------------------------------------------------- front end
@@ -61,13 +62,6 @@ def example_count(n_samples_16k: int) -> int:
     return 0 if n < WIN else (1 + (n - WIN) // HOP) // FRAMES
 
 
-def _device(t: torch.Tensor, what: str) -> torch.device:
-    from . import lib as L
-    if t.device.type != "cuda":
-        raise L.Jen1HipError(f"{what} runs on a GPU, not on {t.device}: there is no CPU fallback")
-    return t.device
-
-
 def _check_float(t, what: str) -> None:
     if not torch.is_tensor(t) or t.dtype != torch.float32:
         raise TypeError(f"{what}: float32 tensors, not {getattr(t, 'dtype', type(t))}")
@@ -75,23 +69,17 @@ def _check_float(t, what: str) -> None:
         raise ValueError(f"{what}: a metric, not a loss -- there is no autograd; detach the input")
 
 
-def _bank(dev: torch.device):
-    hit = _banks.get(str(dev))
-    if hit is None:
-        lo, hi, off, w = spectral.banded(vggish_mel_matrix())
-        hit = _banks[str(dev)] = (torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev), torch.from_numpy(off).to(dev),
-                                  torch.from_numpy(w.astype(np.float32)).to(dev), int(w.size))
-    return hit
+def vggish_bands(dev: torch.device) -> H.Bands:
+    return H.device_table(dev, ("vggish",), lambda: H.Bands.on(dev, *spectral.banded(vggish_mel_matrix())))
 
 
 def _mel(wav: torch.Tensor, sr: int, lengths, what: str):
     """wav [..., C, L] at ``sr`` -> (linear mel [rows, 64, frames] or None when no row holds a frame, counts per row, frames)"""
     from . import audio
-    from . import lib as L
     _check_float(wav, what)
     if wav.dim() < 2 or int(wav.shape[-1]) < 1:
         raise ValueError(f"{what}: audio is [..., C, L], not {tuple(wav.shape)}")
-    dev = _device(wav, what)
+    dev = H.gpu_device(wav.device, what)
     x = audio.convert_audio(wav, int(sr), SR, 1, device=dev)
     n16 = int(x.shape[-1])
     x = x.reshape(-1, n16)
@@ -99,9 +87,7 @@ def _mel(wav: torch.Tensor, sr: int, lengths, what: str):
     if lengths is None:
         counts = [example_count(n16)] * rows
     else:
-        vals = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(vals) != rows:
-            raise ValueError(f"{what}: lengths has {len(vals)} entries, the batch has {rows} rows")
+        vals = H.host_ints(lengths, rows, f"{what}: lengths")
         if any(v < 0 or v > int(wav.shape[-1]) for v in vals):
             raise ValueError(f"{what}: lengths must lie in 0..{int(wav.shape[-1])}")
         # samples beyond a row's length are taken as padding: a resampled row is as long as convert_audio would make the cut row
@@ -110,30 +96,22 @@ def _mel(wav: torch.Tensor, sr: int, lengths, what: str):
         return None, counts, 0
     xp = torch.nn.functional.pad(x, (PAD, PAD))
     n = n16 + 2 * PAD
-    frames = 1 + (n - N_FFT) // HOP
-    lo, hi, off, w, nw = _bank(dev)
-    lib = L.load()
-    mel = torch.empty((rows, BANDS, frames), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_mel(xp.data_ptr(), n, mel.data_ptr(), spectral._window("hann", WIN, dev).data_ptr(),
-                             spectral._twiddle(N_FFT, dev).data_ptr(), lo.data_ptr(), hi.data_ptr(), off.data_ptr(), w.data_ptr(), BANDS, nw,
-                             rows, n, N_FFT, HOP, WIN, 0, L.SPEC_MAGNITUDE, L.SPEC_LOG_NONE, 0.0, torch.cuda.current_stream(dev).cuda_stream),
-                "jen1_mel")
-    return mel, counts, frames
+    fr = H.framing(N_FFT, HOP, WIN, "hann", False, n=n)
+    mel = torch.empty((rows, BANDS, fr.frames), dtype=torch.float32, device=dev)
+    H.launch(dev, "jen1_mel", xp.data_ptr(), n, mel.data_ptr(), *H.frame_tables(fr, "hann", dev), *vggish_bands(dev).abi(), *fr.abi(rows, n),
+             L.SPEC_MAGNITUDE, L.SPEC_LOG_NONE, 0.0)
+    return mel, counts, fr.frames
 
 
 def vggish_examples(wav: torch.Tensor, sr: int, device="cuda", lengths=None) -> Tuple[torch.Tensor, List[int]]:
     """wav float32 [..., C, L] (C in {1, 2}) on a GPU at rate ``sr`` -> (log-mel examples float32 [N_total, 96, 64], examples per row).
     ``lengths`` (host integers, one per row, in samples at ``sr``): rows padded to a common L count only up to their own length.  A
     row shorter than one example gives none."""
-    from . import lib as L
     mel, counts, frames = _mel(wav, sr, lengths, "vggish_examples")
     total = sum(counts)
     out = torch.empty((total, FRAMES, BANDS), dtype=torch.float32, device=wav.device)
     if total:
-        with torch.cuda.device(wav.device):
-            L.check(L.load().jen1_vggish_examples(mel.data_ptr(), (L.c_int * len(counts))(*counts), len(counts), frames, out.data_ptr(),
-                                                  torch.cuda.current_stream(wav.device).cuda_stream), "jen1_vggish_examples")
+        H.launch(wav.device, "jen1_vggish_examples", mel.data_ptr(), H.c_ints(counts), len(counts), frames, out.data_ptr())
     return out, counts
 
 
@@ -218,10 +196,8 @@ class VGGishHIP:
 
     # ------------------------------------------------------------------ the network
     def _runtime(self):
-        from . import lib as L
         from .gemm_host import GemmRuntime
-        if self.device.type != "cuda":
-            raise L.Jen1HipError(f"VGGishHIP runs on a GPU, not on {self.device}: there is no CPU fallback")
+        H.gpu_device(self.device, "VGGishHIP")
         if self._rt is None:
             self._rt = GemmRuntime("f32", self.device)
         return self._rt
@@ -229,24 +205,21 @@ class VGGishHIP:
     def _convs(self, first_layer, n: int) -> torch.Tensor:
         """the six convolutions on ``n`` examples whose first layer ``first_layer(y)`` writes [n, 48, 32, C1]: [n, 6 * 4 * C4], the
         (h, w, c) order the first linear expects (NHWC needs no permutation)"""
-        from . import lib as L
-        rt = self._runtime()
-        lib, dev, stream = rt.lib, self.device, rt.stream()
+        dev = self.device
         x = torch.empty((n, 48, 32, self.channels[0]), dtype=torch.float32, device=dev)
         first_layer(x)
         for i in range(1, 6):
-            H, W = GRID[i]
+            h, w = GRID[i]
             pool = POOL_AFTER[i]
             cin, cout = self.channels[i - 1], self.channels[i]
-            y = torch.empty((n, H // 2 if pool else H, W // 2 if pool else W, cout), dtype=torch.float32, device=dev)
-            L.check(lib.jen1_conv3x3(x.data_ptr(), self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr(), y.data_ptr(), n, H, W, cin, cout,
-                                     int(pool), stream), "jen1_conv3x3")
+            y = torch.empty((n, h // 2 if pool else h, w // 2 if pool else w, cout), dtype=torch.float32, device=dev)
+            H.launch(dev, "jen1_conv3x3", x.data_ptr(), self.conv_w[i].data_ptr(), self.conv_b[i].data_ptr(), y.data_ptr(), n, h, w, cin, cout,
+                     int(pool))
             x = y
         return x.reshape(n, -1)
 
     def _linears(self, x: torch.Tensor, out_t: torch.Tensor, col0: int) -> None:
         """the three linears on x [n, K]; the embeddings go to ``out_t[:, col0 : col0 + n]`` (out_t: [dim, N_total])"""
-        from . import lib as L
         from .gemm_host import operand
         rt = self._runtime()
         n = int(x.shape[0])
@@ -261,38 +234,37 @@ class VGGishHIP:
                 y = torch.empty((n, nout), dtype=torch.float32, device=self.device)
                 rt.gemm(operand(x.data_ptr(), K, 1), operand(w.data_ptr(), K, 1, tap_stride=nout * K), y.data_ptr(), n, nout, K, dtype=L.F32,
                         ldc_m=nout, bias=b)
-                L.check(rt.lib.jen1_vggish_relu(y.data_ptr(), y.numel(), rt.stream()), "jen1_vggish_relu")
+                H.launch(self.device, "jen1_vggish_relu", y.data_ptr(), y.numel())
                 x = y
 
-    def _stack(self, first_layer, n: int, out_t: torch.Tensor, col0: int) -> None:
-        self._linears(self._convs(first_layer, n), out_t, col0)
+    def _embed(self, src: torch.Tensor, counts: List[int], frames: int, is_log: int, out_t: torch.Tensor) -> None:
+        """the network over the ``sum(counts)`` examples of ``src`` (rows of ``frames`` frames holding ``counts[r]`` examples each; ``is_log``:
+        log-mel examples, not ``jen1_mel``'s linear output), CHUNK at a time, into ``out_t``"""
+        host = H.c_ints(counts)
+        for n0 in range(0, int(out_t.shape[1]), CHUNK):
+            n = min(CHUNK, int(out_t.shape[1]) - n0)
+            first = lambda y, n0=n0, n=n: H.launch(self.device, "jen1_vggish_conv1", src.data_ptr(), host, len(counts), frames, is_log, n0, n,
+                                                   self.conv_w[0].data_ptr(), self.conv_b[0].data_ptr(), y.data_ptr(), self.channels[0])
+            self._linears(self._convs(first, n), out_t, n0)
 
     def _finish(self, out_t: torch.Tensor) -> torch.Tensor:
-        from . import lib as L
         if self.final_relu and out_t.numel():
-            L.check(self._runtime().lib.jen1_vggish_relu(out_t.data_ptr(), out_t.numel(), self._runtime().stream()), "jen1_vggish_relu")
+            H.launch(self.device, "jen1_vggish_relu", out_t.data_ptr(), out_t.numel())
         return out_t.t()                           # [N, dim], a view: the memory stays [dim][N], what the statistics read
 
     @torch.no_grad()
     def forward(self, examples: torch.Tensor) -> torch.Tensor:
         """log-mel examples float32 [N, 96, 64] on the GPU -> embeddings float32 [N, dim] (a transposed view of [dim, N])"""
-        from . import lib as L
         _check_float(examples, "VGGishHIP.forward")
-        _device(examples, "VGGishHIP.forward")
+        H.gpu_device(examples.device, "VGGishHIP.forward")
         if examples.dim() != 3 or tuple(examples.shape[1:]) != (FRAMES, BANDS) or int(examples.shape[0]) < 1:
             raise ValueError(f"VGGishHIP.forward: examples are [N, {FRAMES}, {BANDS}] with N >= 1, not {tuple(examples.shape)}")
-        rt = self._runtime()
+        self._runtime()
         ex = examples.to(self.device).contiguous()
         N = int(ex.shape[0])
         out_t = torch.empty((self.dim, N), dtype=torch.float32, device=self.device)
-        ones = (L.c_int * N)(*([1] * N))
         with torch.cuda.device(self.device):
-            for n0 in range(0, N, CHUNK):
-                n = min(CHUNK, N - n0)
-                first = lambda y, n0=n0, n=n: L.check(rt.lib.jen1_vggish_conv1(ex.data_ptr(), ones, N, FRAMES, 1, n0, n, self.conv_w[0].data_ptr(),
-                                                                                self.conv_b[0].data_ptr(), y.data_ptr(), self.channels[0],
-                                                                                rt.stream()), "jen1_vggish_conv1")
-                self._stack(first, n, out_t, n0)
+            self._embed(ex, [1] * N, FRAMES, 1, out_t)
             return self._finish(out_t)
 
     __call__ = forward
@@ -301,21 +273,14 @@ class VGGishHIP:
     def embed(self, wav: torch.Tensor, sr: int, lengths=None) -> Tuple[torch.Tensor, List[int]]:
         """wav float32 [..., C, L] on the GPU at rate ``sr`` -> (embeddings [N_total, dim], examples per row).  The first layer reads the
         mel spectrogram where ``jen1_mel`` left it: the examples are never written."""
-        from . import lib as L
-        rt = self._runtime()
+        self._runtime()
         mel, counts, frames = _mel(wav, sr, lengths, "VGGishHIP.embed")
         N = sum(counts)
         out_t = torch.empty((self.dim, N), dtype=torch.float32, device=self.device)
         if N == 0:
             return out_t.t(), counts
-        host = (L.c_int * len(counts))(*counts)
         with torch.cuda.device(self.device):
-            for n0 in range(0, N, CHUNK):
-                n = min(CHUNK, N - n0)
-                first = lambda y, n0=n0, n=n: L.check(rt.lib.jen1_vggish_conv1(mel.data_ptr(), host, len(counts), frames, 0, n0, n,
-                                                                                self.conv_w[0].data_ptr(), self.conv_b[0].data_ptr(), y.data_ptr(),
-                                                                                self.channels[0], rt.stream()), "jen1_vggish_conv1")
-                self._stack(first, n, out_t, n0)
+            self._embed(mel, counts, frames, 0, out_t)
             return self._finish(out_t), counts
 
 
@@ -344,9 +309,8 @@ class FrechetStats:
     def update(self, emb: torch.Tensor) -> "FrechetStats":
         """add the rows of ``emb`` float32 [N, dim] on a GPU (N = 0 adds nothing).  A transposed view of a [dim, N] tensor -- what
         ``VGGishHIP`` returns -- is read in place; anything else is copied into that layout first."""
-        from . import lib as L
         _check_float(emb, "FrechetStats.update")
-        dev = _device(emb, "FrechetStats.update")
+        H.gpu_device(emb.device, "FrechetStats.update")
         if emb.dim() != 2 or int(emb.shape[1]) != self.dim:
             raise ValueError(f"FrechetStats.update: embeddings are [N, {self.dim}], not {tuple(emb.shape)}")
         N = int(emb.shape[0])
@@ -355,14 +319,7 @@ class FrechetStats:
         z = emb.t()
         if not z.is_contiguous():
             z = z.contiguous()                     # the transpose copy: embeddings that did not come from VGGishHIP
-        if self.state.device != dev:
-            self.state = self.state.to(dev)
-        lib = L.load()
-        nbytes = int(lib.jen1_latent_moments_workspace(1, self.dim, N))
-        work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            L.check(lib.jen1_latent_moments(z.data_ptr(), None, self.state.data_ptr(), work.data_ptr(), nbytes, 1, self.dim, N,
-                                            torch.cuda.current_stream(dev).cuda_stream), "jen1_latent_moments")
+        self.state = latent_moments(z[None], None, self.state)
         return self
 
     @torch.no_grad()

@@ -358,10 +358,7 @@ def build(verbose: bool = False) -> str:
     under <package>/build/ (compiled in parallel, only when the source or a header is newer than its object), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "jen1_hip.h"), os.path.join(INCLUDE, "jen1_train.h"),
-            os.path.join(INCLUDE, "jen1_deep.h"), os.path.join(INCLUDE, "jen1_long.h"), os.path.join(INCLUDE, "jen1_t5.h"), os.path.join(INCLUDE, "jen1_spectral.h"),
-            os.path.join(INCLUDE, "jen1_fad.h"), os.path.join(INCLUDE, "jen1_analysis.h"), os.path.join(INCLUDE, "jen1_vocoder.h")]
-    hdrs += [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h") and h != "common.h"]
+    hdrs = [os.path.join(d, h) for d in (INCLUDE, CSRC) for h in sorted(os.listdir(d)) if h.endswith(".h")]
     deps = srcs + hdrs
     if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH

@@ -19,11 +19,26 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
+from . import audio_host as H
+from . import lib as L
+
 KINDS = ("zca", "pca", "diag")
 
 
 def state_words(dim: int) -> int:
     return 1 + dim + dim * dim
+
+
+def latent_moments(z: torch.Tensor, host_lengths, state: torch.Tensor) -> torch.Tensor:
+    """add the frame count, ``sum z_c`` and ``sum z_c z_d`` of ``z [B, C, T]`` (float32, contiguous, on a GPU) to ``state`` (float64
+    ``[state_words(C)]``, moved to z's device first) and return it; ``host_lengths``: a ``c_int`` array of the valid frames per row, or None"""
+    B, C, T = z.shape
+    if state.device != z.device:
+        state = state.to(z.device)
+    nbytes = int(L.load().jen1_latent_moments_workspace(B, C, T))
+    work = H.workspace(nbytes, z.device)
+    H.launch(z.device, "jen1_latent_moments", z.data_ptr(), host_lengths, state.data_ptr(), work.data_ptr(), nbytes, B, C, T)
+    return state
 
 
 def whitening(state: torch.Tensor, kind: str = "zca", eps: float = 1e-6) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -94,36 +109,20 @@ class Normalizer(nn.Module):
 
     # ------------------------------------------------------------------ statistics
     def _check(self, z: torch.Tensor, what: str) -> torch.Tensor:
-        from . import lib as L
         if z.dim() != 3 or z.shape[1] != self.dim or z.shape[0] < 1 or z.shape[2] < 1:
             raise ValueError(f"{what}: latents must be [B, {self.dim}, T] with B, T >= 1, not {tuple(z.shape)}")
         if z.dtype != torch.float32:
             raise TypeError(f"{what}: latents must be float32, not {z.dtype}")
-        if z.device.type != "cuda":
-            raise L.Jen1HipError(f"{what} runs on a GPU, not on {z.device}: there is no CPU fallback")
+        H.gpu_device(z.device, what)
         return z.contiguous()
 
     @torch.no_grad()
     def update(self, z: torch.Tensor, lengths=None) -> "Normalizer":
         """add the frames of ``z [B, C, T]`` (float32, on a GPU) to the state; ``lengths`` (host integers, one per row, each in 0..T):
         the valid frames of every row -- frames at or beyond ``lengths[b]`` do not count.  No host synchronisation."""
-        from . import lib as L
         z = self._check(z, "Normalizer.update")
-        B, C, T = z.shape
-        host = None
-        if lengths is not None:
-            vals = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-            if len(vals) != B:
-                raise ValueError(f"lengths has {len(vals)} entries, the batch has {B} rows")
-            host = (L.c_int * B)(*vals)
-        lib = L.load()
-        if self.state.device != z.device:
-            self.state = self.state.to(z.device)
-        nbytes = int(lib.jen1_latent_moments_workspace(B, C, T))
-        work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=z.device)
-        with torch.cuda.device(z.device):
-            L.check(lib.jen1_latent_moments(z.data_ptr(), host, self.state.data_ptr(), work.data_ptr(), nbytes, B, C, T,
-                                            torch.cuda.current_stream(z.device).cuda_stream), "jen1_latent_moments")
+        host = None if lengths is None else H.c_ints(H.host_ints(lengths, int(z.shape[0]), "lengths"))
+        self.state = latent_moments(z, host, self.state)
         return self
 
     @torch.no_grad()
@@ -164,20 +163,16 @@ class Normalizer(nn.Module):
 
     # ------------------------------------------------------------------ the map
     def _affine(self, z: torch.Tensor, inverse: bool, what: str) -> torch.Tensor:
-        from . import lib as L
         if not self.fitted:
             raise RuntimeError(f"{what}: the normalizer has not been fitted (update + finalize, fit, load_state_dict or Normalizer.identity)")
         z = self._check(z, what)
         B, C, T = z.shape
-        lib = L.load()
         if self.weight.device != z.device:
             self.to(z.device)
         mean = None if self.kind == "identity" else self.mean.data_ptr()
         A, pre, post = (self.inverse, None, mean) if inverse else (self.weight, mean, None)
         y = torch.empty_like(z)
-        with torch.cuda.device(z.device):
-            L.check(lib.jen1_latent_affine(z.data_ptr(), y.data_ptr(), A.data_ptr(), pre, post, B, C, T,
-                                           torch.cuda.current_stream(z.device).cuda_stream), "jen1_latent_affine")
+        H.launch(z.device, "jen1_latent_affine", z.data_ptr(), y.data_ptr(), A.data_ptr(), pre, post, B, C, T)
         return y
 
     @torch.no_grad()

@@ -29,44 +29,15 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-N_FFTS = (256, 512, 1024, 2048, 4096)
+from . import audio_host as H
+from . import lib as L
+from .audio_host import N_FFTS, frame_count, hann_window, twiddle_table     # the framing primitives: public names of this module too
+
 RESOLUTIONS_48K = ((1024, 100, 480), (2048, 240, 1200), (4096, 480, 2400))        # (n_fft, hop, win_length): Parallel WaveGAN's set, doubled
 LOGS = (None, "log", "db")
-_twiddles: Dict[Tuple[int, str], torch.Tensor] = {}
-_windows: Dict[Tuple[str, int, str], torch.Tensor] = {}
-_banks: Dict[tuple, tuple] = {}
 
 
 # ------------------------------------------------------------------------------------------------------------- host tables
-def twiddle_table(n_fft: int) -> np.ndarray:
-    """float32 [n_fft, 2]: (cos, -sin)(2 pi m / n_fft), formed in float64 and rounded once"""
-    _check_n_fft(n_fft)
-    a = 2.0 * np.pi * np.arange(int(n_fft), dtype=np.float64) / int(n_fft)
-    return np.stack([np.cos(a), -np.sin(a)], axis=1).astype(np.float32)
-
-
-def hann_window(win_length: int) -> np.ndarray:
-    """the periodic Hann window of ``torch.hann_window(win_length)``: float32, from float64"""
-    if int(win_length) < 1:
-        raise ValueError(f"win_length must be positive, not {win_length}")
-    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(int(win_length), dtype=np.float64) / int(win_length))).astype(np.float32)
-
-
-def frame_count(n: int, n_fft: int, hop: int, center: bool = True) -> int:
-    """frames of ``torch.stft`` for n samples; the ValueErrors of ``stft`` for a signal too short to frame"""
-    n, n_fft, hop = int(n), int(n_fft), int(hop)
-    _check_n_fft(n_fft)
-    if not 1 <= hop <= n_fft:
-        raise ValueError(f"hop = {hop} must be in [1, n_fft = {n_fft}]")
-    if center:
-        if n <= n_fft // 2:
-            raise ValueError(f"center=True needs more than n_fft / 2 = {n_fft // 2} samples for the reflect padding, not {n}")
-        return 1 + n // hop
-    if n < n_fft:
-        raise ValueError(f"center=False needs at least n_fft = {n_fft} samples, not {n}")
-    return 1 + (n - n_fft) // hop
-
-
 def hz_to_mel(f, mel_scale: str = "htk"):
     f = np.asarray(f, dtype=np.float64)
     if mel_scale == "htk":
@@ -140,12 +111,7 @@ def unbanded(lo, hi, off, weights, bins: int) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------------------- arguments
-def _check_n_fft(n_fft) -> None:
-    if int(n_fft) not in N_FFTS:
-        raise ValueError(f"n_fft = {n_fft} is not one of {N_FFTS}")
-
-
-def _check_wave(wav: torch.Tensor, what: str) -> None:
+def check_wave(wav: torch.Tensor, what: str) -> None:
     if not torch.is_tensor(wav) or wav.dtype != torch.float32:
         raise TypeError(f"{what}: waveforms are float32 tensors, not {getattr(wav, 'dtype', type(wav))}")
     if wav.requires_grad:
@@ -154,82 +120,17 @@ def _check_wave(wav: torch.Tensor, what: str) -> None:
         raise ValueError(f"{what}: audio needs a time axis that is not empty, not shape {tuple(wav.shape)}")
 
 
-def _device(device, what: str) -> torch.device:
-    from . import lib as L
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise L.Jen1HipError(f"{what} runs on a GPU, not on {dev}: there is no CPU fallback")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
-def _framing(n: int, n_fft: int, hop: Optional[int], win_length: Optional[int], window, center: bool):
-    """(n_fft, hop, win_length, frames) with the defaults of ``torch.stft`` filled in and every refusal raised"""
-    _check_n_fft(n_fft)
-    n_fft = int(n_fft)
-    if win_length is None:
-        win_length = int(window.numel()) if torch.is_tensor(window) else n_fft
-    win_length = int(win_length)
-    if win_length > n_fft or win_length < 1:
-        raise ValueError(f"win_length = {win_length} must be in [1, n_fft = {n_fft}]")
-    hop = n_fft // 4 if hop is None else int(hop)
-    if torch.is_tensor(window):
-        if window.dim() != 1 or int(window.numel()) != win_length:
-            raise ValueError(f"window of shape {tuple(window.shape)} must be 1-D with win_length = {win_length} values")
-    elif window != "hann":
-        raise ValueError(f"unknown window {window!r}: 'hann' or a 1-D tensor")
-    return n_fft, hop, win_length, frame_count(n, n_fft, hop, center)
-
-
-def _rows(wav: torch.Tensor, dev: torch.device):
-    """(x on dev, rows, n, row stride in floats): the leading axes as one row axis, without a copy where the rows are evenly spaced"""
-    x = wav.to(dev)
-    n = int(x.shape[-1])
-    lead = tuple(x.shape[:-1])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
-    even = x.stride(-1) == 1 or n == 1
-    for d in range(x.dim() - 2):
-        even = even and (x.shape[d] == 1 or x.stride(d) == x.stride(d + 1) * x.shape[d + 1])
-    if x.dim() >= 2 and even and (x.stride(-2) >= n or rows == 1):
-        return x, rows, n, int(x.stride(-2)) if rows > 1 else n
-    x = x.contiguous()
-    return x, rows, n, n
-
-
-def _twiddle(n_fft: int, dev: torch.device) -> torch.Tensor:
-    key = (int(n_fft), str(dev))
-    hit = _twiddles.get(key)
-    if hit is None:
-        hit = _twiddles[key] = torch.from_numpy(twiddle_table(n_fft)).to(dev)
-    return hit
-
-
-def _window(window, win_length: int, dev: torch.device) -> torch.Tensor:
-    if torch.is_tensor(window):
-        return window.detach().to(dev, torch.float32).contiguous()
-    key = ("hann", int(win_length), str(dev))
-    hit = _windows.get(key)
-    if hit is None:
-        hit = _windows[key] = torch.from_numpy(hann_window(win_length)).to(dev)
-    return hit
-
-
-def _bank(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm, dev: torch.device):
-    """(lo, hi, off, weights float32, n_weights) of the mel filterbank on ``dev``"""
-    key = (int(sr), int(n_fft), int(n_mels), float(f_min), None if f_max is None else float(f_max), mel_scale, norm, str(dev))
-    hit = _banks.get(key)
-    if hit is None:
+def mel_bands(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm, dev: torch.device) -> H.Bands:
+    """the mel filterbank on ``dev`` in banded form"""
+    def make():
         lo, hi, off, w = banded(mel_filterbank(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm))
         if w.size == 0:
             raise ValueError(f"the mel filterbank (sr {sr}, n_fft {n_fft}, n_mels {n_mels}, f_min {f_min}, f_max {f_max}) has no bin in any band")
-        hit = _banks[key] = (torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev), torch.from_numpy(off).to(dev),
-                             torch.from_numpy(w.astype(np.float32)).to(dev), int(w.size))
-    return hit
+        return H.Bands.on(dev, lo, hi, off, w)
+    return H.device_table(dev, ("mel", int(sr), int(n_fft), int(n_mels), float(f_min), None if f_max is None else float(f_max), mel_scale, norm), make)
 
 
 def _kind(power: float) -> int:
-    from . import lib as L
     if float(power) == 2.0:
         return L.SPEC_POWER
     if float(power) == 1.0:
@@ -239,18 +140,13 @@ def _kind(power: float) -> int:
 
 # ------------------------------------------------------------------------------------------------------------- transforms
 def _stft(wav, n_fft, hop, win_length, window, center, kind, device, what):
-    from . import lib as L
-    _check_wave(wav, what)
-    n_fft, hop, win_length, frames = _framing(int(wav.shape[-1]), n_fft, hop, win_length, window, center)
-    dev = _device(device, what)
-    lib = L.load()
-    x, rows, n, stride = _rows(wav, dev)
-    bins = n_fft // 2 + 1
-    shape = tuple(wav.shape[:-1]) + (bins, frames)
+    check_wave(wav, what)
+    fr = H.framing(n_fft, hop, win_length, window, center, n=int(wav.shape[-1]))
+    dev = H.gpu_device(device, what)
+    x, rows, n, stride = H.rows_of(wav, dev)
+    shape = tuple(wav.shape[:-1]) + (fr.n_fft // 2 + 1, fr.frames)
     out = torch.empty(shape + ((2,) if kind == L.SPEC_COMPLEX else ()), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_stft(x.data_ptr(), stride, out.data_ptr(), _window(window, win_length, dev).data_ptr(), _twiddle(n_fft, dev).data_ptr(),
-                              rows, n, n_fft, hop, win_length, int(bool(center)), kind, torch.cuda.current_stream(dev).cuda_stream), "jen1_stft")
+    H.launch(dev, "jen1_stft", x.data_ptr(), stride, out.data_ptr(), *H.frame_tables(fr, window, dev), *fr.abi(rows, n), kind)
     return torch.view_as_complex(out) if kind == L.SPEC_COMPLEX else out
 
 
@@ -258,7 +154,6 @@ def stft(wav: torch.Tensor, n_fft: int, hop: Optional[int] = None, win_length: O
          device="cuda") -> torch.Tensor:
     """``torch.stft(wav, n_fft, hop, win_length, window, center=center, pad_mode="reflect", return_complex=True)``: complex64
     ``[..., n_fft / 2 + 1, frames]`` on ``device``.  ``hop`` defaults to n_fft / 4 and ``win_length`` to n_fft, as there."""
-    from . import lib as L
     return _stft(wav, n_fft, hop, win_length, window, center, L.SPEC_COMPLEX, device, "stft")
 
 
@@ -273,23 +168,19 @@ def mel_spectrogram(wav: torch.Tensor, sr: int, n_fft: int = 2048, hop: int = 51
                     log: Optional[str] = None, floor: float = 1e-10, window="hann", center: bool = True, device="cuda") -> torch.Tensor:
     """``mel_filterbank(...) @ spectrogram(wav, ..., power)``: float32 ``[..., n_mels, frames]``, the filterbank applied while the spectrum
     is in LDS.  ``log``: None, ``"log"`` = log(max(v, floor)) or ``"db"`` = 10 log10(max(v, floor))."""
-    from . import lib as L
     if log not in LOGS:
         raise ValueError(f"unknown log {log!r}: one of {LOGS}")
     if log is not None and not float(floor) > 0.0:
         raise ValueError(f"floor = {floor} must be positive under a logarithm")
-    _check_wave(wav, "mel_spectrogram")
+    check_wave(wav, "mel_spectrogram")
     kind = _kind(power)
-    n_fft, hop, win_length, frames = _framing(int(wav.shape[-1]), n_fft, hop, win_length, window, center)
-    dev = _device(device, "mel_spectrogram")
-    lib = L.load()
-    x, rows, n, stride = _rows(wav, dev)
-    lo, hi, off, w, nw = _bank(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm, dev)
-    out = torch.empty(tuple(wav.shape[:-1]) + (int(n_mels), frames), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_mel(x.data_ptr(), stride, out.data_ptr(), _window(window, win_length, dev).data_ptr(), _twiddle(n_fft, dev).data_ptr(),
-                             lo.data_ptr(), hi.data_ptr(), off.data_ptr(), w.data_ptr(), int(n_mels), nw, rows, n, n_fft, hop, win_length,
-                             int(bool(center)), kind, LOGS.index(log), float(floor), torch.cuda.current_stream(dev).cuda_stream), "jen1_mel")
+    fr = H.framing(n_fft, hop, win_length, window, center, n=int(wav.shape[-1]))
+    dev = H.gpu_device(device, "mel_spectrogram")
+    x, rows, n, stride = H.rows_of(wav, dev)
+    bands = mel_bands(sr, fr.n_fft, n_mels, f_min, f_max, mel_scale, norm, dev)
+    out = torch.empty(tuple(wav.shape[:-1]) + (int(n_mels), fr.frames), dtype=torch.float32, device=dev)
+    H.launch(dev, "jen1_mel", x.data_ptr(), stride, out.data_ptr(), *H.frame_tables(fr, window, dev), *bands.abi(), *fr.abi(rows, n), kind,
+             LOGS.index(log), float(floor))
     return out
 
 
@@ -309,7 +200,6 @@ def _check_spec(spec: torch.Tensor, what: str) -> int:
 
 def vocoder_frame_count(frames: int, rate: float) -> int:
     """frames of ``phase_vocoder`` for ``frames`` input frames: ``len(numpy.arange(0, frames, rate))``, by the library's own rule"""
-    from . import lib as L
     if not (float(rate) > 0.0 and math.isfinite(float(rate))):
         raise ValueError(f"rate = {rate} must be positive and finite")
     count = int(L.load().jen1_vocoder_frames(int(frames), float(rate)))
@@ -323,42 +213,21 @@ def istft(spec: torch.Tensor, n_fft: int, hop: Optional[int] = None, win_length:
     """``torch.istft(spec, n_fft, hop, win_length, window, center=center, length=length)`` of a one-sided complex64 ``[..., n_fft / 2 + 1,
     frames]``: float32 ``[..., length]`` on ``device``.  ``length`` defaults to ``hop * (frames - 1)`` (plus n_fft with center=False);
     a longer one is filled with zeros past the last frame.  A window whose squared overlap-add vanishes somewhere (NOLA) is refused."""
-    from . import lib as L
     got = _check_spec(spec, "istft")
-    _check_n_fft(n_fft)
-    n_fft = int(n_fft)
-    if got != n_fft:
-        raise ValueError(f"istft: the input has {int(spec.shape[-2])} bins, n_fft = {n_fft} needs {n_fft // 2 + 1}")
-    if win_length is None:
-        win_length = int(window.numel()) if torch.is_tensor(window) else n_fft
-    win_length = int(win_length)
-    if win_length > n_fft or win_length < 1:
-        raise ValueError(f"win_length = {win_length} must be in [1, n_fft = {n_fft}]")
-    hop = n_fft // 4 if hop is None else int(hop)
-    if not 1 <= hop <= n_fft:
-        raise ValueError(f"hop = {hop} must be in [1, n_fft = {n_fft}]")
-    if torch.is_tensor(window):
-        if window.dim() != 1 or int(window.numel()) != win_length:
-            raise ValueError(f"window of shape {tuple(window.shape)} must be 1-D with win_length = {win_length} values")
-        host = window.detach().to("cpu", torch.float32).contiguous().numpy()
-    elif window == "hann":
-        host = hann_window(win_length)
-    else:
-        raise ValueError(f"unknown window {window!r}: 'hann' or a 1-D tensor")
-    frames = int(spec.shape[-1])
-    length = hop * (frames - 1) + (0 if center else n_fft) if length is None else int(length)
+    H.check_n_fft(n_fft)
+    if got != int(n_fft):
+        raise ValueError(f"istft: the input has {int(spec.shape[-2])} bins, n_fft = {n_fft} needs {int(n_fft) // 2 + 1}")
+    fr = H.framing(n_fft, hop, win_length, window, center, frames=int(spec.shape[-1]))
+    host = window.detach().to("cpu", torch.float32).contiguous().numpy() if torch.is_tensor(window) else hann_window(fr.win_length)
+    length = fr.hop * (fr.frames - 1) + (0 if center else fr.n_fft) if length is None else int(length)
     if length < 1:
-        raise ValueError(f"istft: length = {length} must be positive ({frames} frames at hop {hop})")
-    dev = _device(device, "istft")
-    lib = L.load()
+        raise ValueError(f"istft: length = {length} must be positive ({fr.frames} frames at hop {fr.hop})")
+    dev = H.gpu_device(device, "istft")
     lead = tuple(spec.shape[:-2])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
     x = torch.view_as_real(spec.to(dev).contiguous())
     out = torch.empty(lead + (length,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_istft(x.data_ptr(), out.data_ptr(), length, _window(window, win_length, dev).data_ptr(), host.ctypes.data,
-                               _twiddle(n_fft, dev).data_ptr(), rows, frames, length, n_fft, hop, win_length, int(bool(center)),
-                               torch.cuda.current_stream(dev).cuda_stream), "jen1_istft")
+    H.launch(dev, "jen1_istft", x.data_ptr(), out.data_ptr(), length, H.window_on(window, fr.win_length, dev).data_ptr(), host.ctypes.data,
+             H.twiddle_on(fr.n_fft, dev).data_ptr(), math.prod(lead), fr.frames, length, fr.n_fft, fr.hop, fr.win_length, int(fr.center))
     return out
 
 
@@ -366,54 +235,40 @@ def phase_vocoder(spec: torch.Tensor, rate: float, hop: int, device="cuda") -> t
     """``torchaudio.functional.phase_vocoder(spec, rate, 2 pi hop k / n_fft)``: the frame axis of a complex64 ``[..., n_fft / 2 + 1,
     frames]`` resampled at steps of ``rate`` frames (rate > 1: fewer frames, faster), complex64 ``[..., n_fft / 2 + 1, J]`` on ``device``.
     ``hop`` is the hop the spectrogram was taken with."""
-    from . import lib as L
     n_fft = _check_spec(spec, "phase_vocoder")
-    if not 1 <= int(hop) <= n_fft:
-        raise ValueError(f"hop = {hop} must be in [1, n_fft = {n_fft}]")
+    H.check_hop(hop, n_fft)
     frames = int(spec.shape[-1])
     if not (float(rate) > 0.0 and math.isfinite(float(rate))):
         raise ValueError(f"rate = {rate} must be positive and finite")
-    dev = _device(device, "phase_vocoder")
-    lib = L.load()
+    dev = H.gpu_device(device, "phase_vocoder")
     count = vocoder_frame_count(frames, rate)
-    lead = tuple(spec.shape[:-2])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
     x = torch.view_as_real(spec.to(dev).contiguous())
     out = torch.empty(tuple(spec.shape[:-1]) + (count, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_phase_vocoder(x.data_ptr(), out.data_ptr(), rows, frames, n_fft, int(hop), float(rate),
-                                       torch.cuda.current_stream(dev).cuda_stream), "jen1_phase_vocoder")
+    H.launch(dev, "jen1_phase_vocoder", x.data_ptr(), out.data_ptr(), math.prod(spec.shape[:-2]), frames, n_fft, int(hop), float(rate))
     return torch.view_as_complex(out)
 
 
 # ------------------------------------------------------------------------------------------------------------- distances
 def _pair(test: torch.Tensor, reference: torch.Tensor, what: str) -> None:
-    _check_wave(test, what)
-    _check_wave(reference, what)
+    check_wave(test, what)
+    check_wave(reference, what)
     if tuple(test.shape) != tuple(reference.shape):
         raise ValueError(f"{what}: test {tuple(test.shape)} and reference {tuple(reference.shape)} must have the same shape")
 
 
-def _distance_sums(test, reference, n_fft, hop, win_length, window, center, bank, kind, floor, dev):
+def _distance_sums(test, reference, n_fft, hop, win_length, window, center, bands, kind, floor, dev):
     """float64 [..., 3] on ``dev``: the three sums of ``jen1_spectral_distance`` per row, and the frame count"""
-    from . import lib as L
-    n_fft, hop, win_length, frames = _framing(int(test.shape[-1]), n_fft, hop, win_length, window, center)
+    fr = H.framing(n_fft, hop, win_length, window, center, n=int(test.shape[-1]))
     if not float(floor) > 0.0:
         raise ValueError(f"floor = {floor} must be positive")
-    lib = L.load()
-    x, rows, n, xs = _rows(test, dev)
-    y, _, _, ys = _rows(reference, dev)
-    nbytes = int(lib.jen1_spectral_distance_workspace_bytes(rows, n, n_fft, hop, int(bool(center))))
-    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+    x, rows, n, xs = H.rows_of(test, dev)
+    y, _, _, ys = H.rows_of(reference, dev)
+    nbytes = int(L.load().jen1_spectral_distance_workspace_bytes(rows, n, fr.n_fft, fr.hop, int(fr.center)))
+    work = H.workspace(nbytes, dev)
     out = torch.empty(tuple(test.shape[:-1]) + (3,), dtype=torch.float64, device=dev)
-    lo, hi, off, w, nw = bank if bank is not None else (None, None, None, None, 0)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        L.check(lib.jen1_spectral_distance(x.data_ptr(), xs, y.data_ptr(), ys, out.data_ptr(), _window(window, win_length, dev).data_ptr(),
-                                           _twiddle(n_fft, dev).data_ptr(), ptr(lo), ptr(hi), ptr(off), ptr(w), 0 if lo is None else int(lo.numel()),
-                                           nw, rows, n, n_fft, hop, win_length, int(bool(center)), kind, float(floor), work.data_ptr(), nbytes,
-                                           torch.cuda.current_stream(dev).cuda_stream), "jen1_spectral_distance")
-    return out, frames
+    H.launch(dev, "jen1_spectral_distance", x.data_ptr(), xs, y.data_ptr(), ys, out.data_ptr(), *H.frame_tables(fr, window, dev), *bands.abi(),
+             *fr.abi(rows, n), kind, float(floor), work.data_ptr(), nbytes)
+    return out, fr.frames
 
 
 def _bc(t: torch.Tensor) -> torch.Tensor:
@@ -428,19 +283,18 @@ def mrstft_distance(test: torch.Tensor, reference: torch.Tensor, resolutions: Se
     """The multi-resolution STFT distance of ``test`` from ``reference`` (``[n]``, ``[C, n]`` or ``[B, C, n]``, same shape): ``{"sc", "log_mag"}``
     float64 ``[B, C, n_res]`` and ``"total"`` ``[B]``, the mean over channels and resolutions of sc + log_mag.  One launch pair per
     resolution ``(n_fft, hop, win_length)``; a silent reference gives sc = inf or nan, as the definition does."""
-    from . import lib as L
     _pair(test, reference, "mrstft_distance")
     if len(resolutions) < 1:
         raise ValueError("mrstft_distance needs at least one resolution")
     if not float(floor) > 0.0:
         raise ValueError(f"floor = {floor} must be positive")
     for n_fft, hop, win_length in resolutions:                  # every refusal before anything runs
-        _framing(int(test.shape[-1]), n_fft, hop, win_length, window, center)
-    dev = _device(device, "mrstft_distance")
+        H.framing(n_fft, hop, win_length, window, center, n=int(test.shape[-1]))
+    dev = H.gpu_device(device, "mrstft_distance")
     t, r = _bc(test), _bc(reference)
     sc, lm = [], []
     for n_fft, hop, win_length in resolutions:
-        sums, frames = _distance_sums(t, r, n_fft, hop, win_length, window, center, None, L.SPEC_MAGNITUDE, floor, dev)
+        sums, frames = _distance_sums(t, r, n_fft, hop, win_length, window, center, H.NO_BANDS, L.SPEC_MAGNITUDE, floor, dev)
         sc.append(torch.sqrt(sums[..., 0] / sums[..., 1]))
         lm.append(sums[..., 2] / float((int(n_fft) // 2 + 1) * frames))
     sc, lm = torch.stack(sc, dim=-1), torch.stack(lm, dim=-1)
@@ -456,10 +310,10 @@ def mel_distance(test: torch.Tensor, reference: torch.Tensor, sr: int, n_fft: in
     kind = _kind(power)
     if not float(floor) > 0.0:
         raise ValueError(f"floor = {floor} must be positive")
-    _framing(int(test.shape[-1]), n_fft, hop, win_length, window, center)
-    dev = _device(device, "mel_distance")
-    bank = _bank(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm, dev)
-    sums, frames = _distance_sums(_bc(test), _bc(reference), n_fft, hop, win_length, window, center, bank, kind, floor, dev)
+    H.framing(n_fft, hop, win_length, window, center, n=int(test.shape[-1]))
+    dev = H.gpu_device(device, "mel_distance")
+    bands = mel_bands(sr, n_fft, n_mels, f_min, f_max, mel_scale, norm, dev)
+    sums, frames = _distance_sums(_bc(test), _bc(reference), n_fft, hop, win_length, window, center, bands, kind, floor, dev)
     return sums[..., 2] / float(int(n_mels) * frames)
 
 
@@ -469,7 +323,7 @@ def audio_report(test: torch.Tensor, reference: torch.Tensor, sr: int, device="c
     with its defaults) and ``lufs_test`` / ``lufs_reference [B]`` (``audio.loudness``)"""
     from . import audio
     _pair(test, reference, "audio_report")
-    dev = _device(device, "audio_report")
+    dev = H.gpu_device(device, "audio_report")
     t, r = _bc(test).to(dev), _bc(reference).to(dev)
     d = mrstft_distance(t, r, device=dev)
     return {"mrstft_total": d["total"], "sc": d["sc"], "log_mag": d["log_mag"], "log_mel_l1": mel_distance(t, r, sr, device=dev),
