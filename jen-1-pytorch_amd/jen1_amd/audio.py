@@ -19,7 +19,9 @@ There is no fallback: whatever needs arithmetic runs on the HIP kernel of ``devi
 
 Behind the decoder (and in front of the encoder, for training clips) the same file sets the LEVEL of a waveform, which the reference
 never does: ``loudness`` (ITU-R BS.1770-4 integrated loudness) and ``normalize_audio`` (gain to a target + limiter) on
-csrc/loudness.hip; see the second half of this file and DESIGN.md section 10e.
+csrc/loudness.hip; see the second half of this file and DESIGN.md section 10e.  The last part is the other half of BS.1770: ``true_peak``
+(Annex 2: the level between the samples) and ``limit_true_peak`` (a look-ahead limiter under a true-peak ceiling, ``limit="truepeak"`` of
+``normalize_audio``) on csrc/limiter.hip; DESIGN.md section 10k.
 """
 from __future__ import annotations
 
@@ -139,7 +141,7 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: i
 # to a target (csrc/loudness.hip: jen1_kweight_energy, jen1_loudness_gate, jen1_gain_apply).  Not in the reference, whose output
 # has whatever level the decoder gives it (Encodec 48 kHz: unit RMS per segment, peaks far above full scale).
 STRATEGIES = ("loudness", "peak", "rms", "clip")
-LIMITS = ("none", "clip", "tanh")
+LIMITS = ("none", "clip", "tanh", "truepeak")     # the first three are JEN1_LIMIT_* of jen1_gain_apply; "truepeak" is jen1_limit_true_peak behind it
 DEFAULT_HEADROOM_DB = {"loudness": 0.0, "peak": 1.0, "rms": 18.0, "clip": 0.0}
 
 
@@ -221,7 +223,8 @@ def loudness(wav: torch.Tensor, sr: int, device="cuda") -> torch.Tensor:
 
 
 def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", target_lufs=-14.0, headroom_db=None, limit: str = "clip",
-                    energy_floor: float = 2e-3, device="cuda", return_gain: bool = False):
+                    energy_floor: float = 2e-3, device="cuda", return_gain: bool = False, ceiling_dbtp: float = -1.0,
+                    lookahead_ms: float = 1.5, release_ms: float = 100.0):
     """``limit(g * wav)`` over ``wav [..., C, L]`` (float32, C in {1, 2}) with one gain per row ``[...]``, formed on the device (nothing is
     read back on the way) and rounded to float32 once:
 
@@ -231,14 +234,16 @@ def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", targ
         "rms"       10^(-headroom_db / 20) / rms (headroom_db: 18 by default); 1 for an all-zero row
         "clip"      1
 
-    ``target_lufs``: a float or a tensor ``[...]``, one target per row.  ``limit``: "none", "clip" (clamp to [-1, 1]) or "tanh".  The result is
-    a new tensor on wav's device; ``return_gain=True`` returns ``(result, gain float32 [...])``."""
+    ``target_lufs``: a float or a tensor ``[...]``, one target per row.  ``limit``: "none", "clip" (clamp to [-1, 1]), "tanh", or "truepeak":
+    the gain with no limit, then ``limit_true_peak`` with ``ceiling_dbtp`` / ``lookahead_ms`` / ``release_ms`` (read by this limit alone).
+    The result is a new tensor on wav's device; ``return_gain=True`` returns ``(result, gain float32 [...])``."""
     if strategy not in STRATEGIES:
         raise ValueError(f"unknown strategy {strategy!r}: one of {STRATEGIES}")
     if limit not in LIMITS:
         raise ValueError(f"unknown limit {limit!r}: one of {LIMITS}")
     _check_wave(wav, "normalize_audio")
     hop_samples(sr)
+    plan = limiter_plan(sr, ceiling_dbtp, lookahead_ms, release_ms) if limit == "truepeak" else None
     lead = tuple(wav.shape[:-2])
     if torch.is_tensor(target_lufs) and tuple(target_lufs.shape) != lead:
         raise ValueError(f"target_lufs {tuple(target_lufs.shape)} must have one entry per row {lead}")
@@ -254,7 +259,146 @@ def normalize_audio(wav: torch.Tensor, sr: int, strategy: str = "loudness", targ
     y = torch.empty_like(x)
     gain = torch.empty((rows,), dtype=torch.float32, device=dev)
     H.launch(dev, "jen1_gain_apply", x.data_ptr(), y.data_ptr(), gain.data_ptr(), None if lufs is None else lufs.data_ptr(),
-             None if stats is None else stats.data_ptr(), target.data_ptr(), rows, C, n, STRATEGIES.index(strategy), LIMITS.index(limit), headroom,
-             float(energy_floor))
+             None if stats is None else stats.data_ptr(), target.data_ptr(), rows, C, n, STRATEGIES.index(strategy),
+             L.LIMIT_NONE if plan is not None else LIMITS.index(limit), headroom, float(energy_floor))
+    if plan is not None:
+        _limit_rows(y, y, sr, plan)
     y = y.reshape(tuple(wav.shape)).to(wav.device)
     return (y, gain.reshape(lead).to(wav.device)) if return_gain else y
+
+
+# -------------------------------------------------------------------------------------------------------------- true peak
+#
+# ITU-R BS.1770-4 Annex 2: the peak of a waveform BETWEEN its samples, read from an oversampled copy, and a look-ahead limiter that
+# holds a waveform under a true-peak ceiling (csrc/limiter.hip: jen1_true_peak, jen1_limit_true_peak).  Not in the reference.  The
+# limiter is offline: the whole row is there, so it looks ahead without delay.
+TRUE_PEAK_TAPS = 16              # taps per phase of the interpolator
+
+
+def true_peak_factor(sr: int) -> int:
+    """the oversampling factor: 4 below 80 kHz, 2 below 160 kHz, else 1 -- at least about 192 kHz after oversampling, as in Annex 2"""
+    sr = int(sr)
+    if sr <= 0:
+        raise ValueError(f"sample rate must be positive, not {sr}")
+    return 4 if sr < 80000 else 2 if sr < 160000 else 1
+
+
+def true_peak_prototype(F: int) -> np.ndarray:
+    """``h[i] = sinc((i - F T / 2) / F) kaiser(F T + 1, beta = 8)[i]``, i = 0 .. F T: the interpolator before it is cut into phases.
+    float64; symmetric, 1 at its centre and 0 (to rounding) at every other multiple of F."""
+    n = int(F) * TRUE_PEAK_TAPS
+    i = np.arange(n + 1, dtype=np.float64)
+    return np.sinc((i - n / 2) / F) * np.kaiser(n + 1, 8.0)
+
+
+def true_peak_filter(sr: int):
+    """(F, taps float64 [F - 1, T]) at sample rate ``sr``, T = 16: phase p = 1 .. F - 1 of the prototype, ``taps[p - 1][k] = h[p + k F]``.
+    Phase 0 is the identity by construction (``o[n F] = x[n]``), so it is neither stored nor filtered and a reading never falls below
+    the sample peak.  The oversampled signal is ``o[n F + p] = sum_{k < T} taps[p - 1][k] x[n + T / 2 - k]`` with zeros outside the row."""
+    F = true_peak_factor(sr)
+    h = true_peak_prototype(F)
+    taps = np.stack([h[p:p + F * TRUE_PEAK_TAPS:F] for p in range(1, F)]) if F > 1 else np.zeros((0, TRUE_PEAK_TAPS))
+    return F, np.ascontiguousarray(taps, dtype=np.float64)
+
+
+def true_peak_tile() -> int:
+    """samples of a row one workgroup of the meter and of the limiter owns: the library's own figure"""
+    return int(L.load().jen1_true_peak_tile())
+
+
+def max_lookahead() -> int:
+    """the longest look-ahead of ``limit_true_peak`` in samples: what a tile of the limiter keeps of its neighbour in LDS"""
+    return int(L.load().jen1_limiter_max_lookahead())
+
+
+def attack_window(A: int) -> np.ndarray:
+    """float64 [A + 1]: ``w[j] ~ sin^2(pi (j + 1) / (A + 2))``, normalised to sum 1 -- the weights that spread a step of the held
+    reduction over the look-ahead"""
+    j = np.arange(int(A) + 1, dtype=np.float64)
+    w = np.sin(np.pi * (j + 1.0) / (int(A) + 2.0)) ** 2
+    return w / w.sum()
+
+
+def _envelope(x: torch.Tensor, sr: int, want_env: bool):
+    """x [rows, C, L] float32, contiguous, on a GPU -> (env float64 [rows, L] or None, peak float64 [rows], linear): the two launches of
+    jen1_true_peak on the current stream of x's device"""
+    rows, C, n = (int(s) for s in x.shape)
+    dev = x.device
+    F, taps = true_peak_filter(sr)
+    nbytes = int(L.load().jen1_true_peak_workspace_bytes(rows, C, n))
+    work = H.workspace(nbytes, dev)
+    env = torch.empty((rows, n), dtype=torch.float64, device=dev) if want_env else None
+    peak = torch.empty((rows,), dtype=torch.float64, device=dev)
+    H.launch(dev, "jen1_true_peak", x.data_ptr(), None if env is None else env.data_ptr(), n, peak.data_ptr(),
+             taps.ctypes.data_as(L.C.POINTER(L.C.c_double)) if F > 1 else None, F, rows, C, n, work.data_ptr(), nbytes)
+    return env, peak
+
+
+def true_peak(wav: torch.Tensor, sr: int, device="cuda") -> torch.Tensor:
+    """BS.1770-4 Annex 2 true peak in dBTP of ``wav [..., C, L]`` (float32, C in {1, 2}), the larger of the channels: float64 ``[...]`` on
+    wav's device, ``-inf`` for silence.  Any positive ``sr`` (there is no hop rule).  Nothing is read back on the way."""
+    _check_wave(wav, "true_peak")
+    true_peak_factor(sr)
+    dev = H.gpu_device(device, "the true-peak meter")
+    _, peak = _envelope(wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:])), sr, False)
+    return (20.0 * torch.log10(peak)).reshape(tuple(wav.shape[:-2])).to(wav.device)
+
+
+def limiter_plan(sr: int, ceiling_dbtp, lookahead_ms, release_ms):
+    """(c, A, rho) of ``limit_true_peak`` from its keywords, or the ValueError; nothing touches a device"""
+    true_peak_factor(sr)
+    ceiling_dbtp, lookahead_ms, release_ms = float(ceiling_dbtp), float(lookahead_ms), float(release_ms)
+    if not math.isfinite(ceiling_dbtp):
+        raise ValueError(f"ceiling_dbtp must be finite, not {ceiling_dbtp}")
+    if not (math.isfinite(lookahead_ms) and lookahead_ms >= 0.0):
+        raise ValueError(f"lookahead_ms must be finite and not negative, not {lookahead_ms}")
+    if not (math.isfinite(release_ms) and release_ms >= 0.0):
+        raise ValueError(f"release_ms must be finite and not negative, not {release_ms}")
+    A = int(round(lookahead_ms * int(sr) / 1000.0))
+    if A > max_lookahead():
+        raise ValueError(f"lookahead_ms = {lookahead_ms} is {A} samples at {int(sr)} Hz: the limiter looks ahead {max_lookahead()} samples at most")
+    c = 10.0 ** (ceiling_dbtp / 20.0)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"ceiling_dbtp = {ceiling_dbtp} is not a level a float64 holds")
+    tau = release_ms * int(sr) / 1000.0
+    return c, A, (math.exp(-1.0 / tau) if tau > 0.0 else 0.0)
+
+
+def _limit_rows(x: torch.Tensor, y: torch.Tensor, sr: int, plan, want_reduction: bool = False):
+    """x [rows, C, L] -> y (the same shape; may be x itself), both float32, contiguous, on one GPU: the meter's two launches and the
+    limiter's four on the current stream.  Returns ``1 - s`` float64 [rows, L], or None"""
+    c, A, rho = plan
+    rows, C, n = (int(s) for s in x.shape)
+    dev = x.device
+    env, _ = _envelope(x, sr, True)
+    window = H.device_table(dev, ("attack", A), lambda: torch.from_numpy(attack_window(A)).to(dev))
+    nbytes = int(L.load().jen1_limiter_workspace_bytes(rows, n, A))
+    work = H.workspace(nbytes, dev)
+    red = torch.empty((rows, n), dtype=torch.float64, device=dev) if want_reduction else None
+    H.launch(dev, "jen1_limit_true_peak", x.data_ptr(), y.data_ptr(), C * n, None if red is None else red.data_ptr(), n, env.data_ptr(), n,
+             window.data_ptr(), rows, C, n, A, c, rho, work.data_ptr(), nbytes)
+    return red
+
+
+def limit_true_peak(wav: torch.Tensor, sr: int, ceiling_dbtp: float = -1.0, lookahead_ms: float = 1.5, release_ms: float = 100.0,
+                    device="cuda", return_reduction: bool = False):
+    """``s * wav`` over ``wav [..., C, L]`` (float32, C in {1, 2}) with one gain ``s [..., L] <= 1`` for every channel of a row, such that the
+    true peak of the result stays at ``ceiling_dbtp``.  With ``env`` the linked envelope of the oversampled row (``true_peak_filter``),
+    ``c = 10^(ceiling_dbtp / 20)``, ``A = round(lookahead_ms sr / 1000)`` and ``rho = exp(-1 / (release_ms sr / 1000))`` (0 for 0 ms):
+
+        q[n] = 1 - min(1, c / env[n])                                     the reduction wanted
+        Q[i] = max q[max(i, 0) .. min(i + A, L - 1)],  i = -A .. L - 1       held over the look-ahead (A samples of silence in front)
+        d[i] = max(Q[i], rho d[i - 1]),  d[-A - 1] = 0                      released
+        s[n] = 1 - sum_{j <= A} w[j] d[n - j],  w = attack_window(A)         attacked: every step of d is spread over A + 1 samples
+
+    in float64, and ``float32(s[n] * float64(wav[n]))`` at the store.  By construction ``s[n] <= min(1, c / env[n])`` (to the rounding of
+    ``sum w``), and a row whose true peak is at or under the ceiling comes back bit for bit.  ``A`` may be 0; above ``max_lookahead()``
+    samples the call is refused.  A new tensor on wav's device; ``return_reduction=True`` returns ``(result, 1 - s float64 [..., L])``."""
+    _check_wave(wav, "limit_true_peak")
+    plan = limiter_plan(sr, ceiling_dbtp, lookahead_ms, release_ms)
+    dev = H.gpu_device(device, "the true-peak limiter")
+    x = wav.to(dev).contiguous().reshape((-1,) + tuple(wav.shape[-2:]))
+    y = torch.empty_like(x)
+    red = _limit_rows(x, y, sr, plan, return_reduction)
+    y = y.reshape(tuple(wav.shape)).to(wav.device)
+    return (y, red.reshape(tuple(wav.shape[:-2]) + (int(wav.shape[-1]),)).to(wav.device)) if return_reduction else y

@@ -2,7 +2,7 @@
 
 Host-side mirror of /root/reference/generation.py:16-192 -- same constructor arguments, ``get_model_and_diffusion``,
 ``generate(prompt, seed, steps, batch_size, seconds, use_gdm, task, init_audio, init_audio_sr, inpainting_scope)`` (plus the keyword
-additions ``sampler``, ``preserve_known``, ``output_sr`` and ``normalize`` / ``target_lufs`` / ``limit``),``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
+additions ``sampler``, ``preserve_known``, ``output_sr`` and ``normalize`` / ``target_lufs`` / ``limit`` with ``ceiling_dbtp`` / ``lookahead_ms`` / ``release_ms``),``get_mask``, ``get_emb``, ``get_conditioning`` -- with the two third-party models the reference constructs itself
 passed in instead (their weights are outside this build):
 
   * ``audio_encoder``: the object the reference gets from ``EncodecModel.encodec_model_48khz()``; used exactly as
@@ -195,7 +195,8 @@ class Jen1:
                  task: str = "text_guided", init_audio: Optional[torch.Tensor] = None, init_audio_sr: Optional[int] = None,
                  inpainting_scope=None, sampler: Optional[str] = None, output_sr: Optional[int] = None,
                  decode: str = "whole", segment_scales: str = "unit", conditions=None,
-                 window_seconds: Optional[float] = None, window_overlap: float = 0.5, normalize: Optional[str] = None,
+                 window_seconds: Optional[float] = None, window_overlap: float = 0.5, ceiling_dbtp: float = -1.0,
+                 lookahead_ms: float = 1.5, release_ms: float = 100.0, normalize: Optional[str] = None,
                  target_lufs=-14.0, limit: str = "clip", preserve_known: bool = False) -> torch.Tensor:
         """``normalize`` / ``target_lufs`` / ``limit`` (not in the reference): set the level of the decoder's output, which otherwise comes
         back as the codec leaves it (Encodec 48 kHz decodes every segment at unit RMS: peaks far above full scale, hard-clipped by a
@@ -204,6 +205,9 @@ class Jen1:
         decoder left its output on, at the model's rate, BEFORE the ``output_sr`` resample.  ``target_lufs="input"`` (music_inpaint /
         music_cont with ``init_audio``): each row's target is the measured loudness of its own given audio after conversion.  None
         keeps the call as it was, bit for bit.
+        ``limit="truepeak"`` with ``ceiling_dbtp`` / ``lookahead_ms`` / ``release_ms`` (read by this limit alone, and like every limit only
+        with ``normalize``): the gain is applied with no limit at the model's rate, and ``jen1_amd.audio.limit_true_peak`` runs LAST, behind
+        the ``output_sr`` resample, on the audio at the rate the caller receives -- a ceiling promised in front of a resampler is not kept by it.
         ``window_seconds`` / ``window_overlap`` (not in the reference): long-form generation.  With ``seconds > window_seconds`` the
         piece is not handed to the denoiser as one sample of a length it was never trained on: its latents live on one canvas of L
         frames and are denoised as W overlapping windows of T frames -- T the frame count the encoder gives ``window_seconds``,
@@ -258,6 +262,8 @@ class Jen1:
             if limit not in audio.LIMITS:
                 raise ValueError(f"unknown limit {limit!r}: one of {audio.LIMITS}")
             audio.hop_samples(self.sample_rate)
+            if limit == "truepeak":
+                audio.limiter_plan(self.sample_rate if output_sr is None else int(output_sr), ceiling_dbtp, lookahead_ms, release_ms)
             if isinstance(target_lufs, str):
                 if target_lufs != "input":
                     raise ValueError(f"target_lufs must be a number, a tensor or 'input', not {target_lufs!r}")
@@ -280,11 +286,16 @@ class Jen1:
             on = out.device if out.device.type == "cuda" else self.device
             if isinstance(target_lufs, str):                   # "input": the level of each row's given audio, measured where the output is
                 target_lufs = audio.loudness(wav[:, :, :prefix].to(on), self.sample_rate, device=on)
-            out = audio.normalize_audio(out, self.sample_rate, strategy=normalize, target_lufs=target_lufs, limit=limit, device=on)
+            out = audio.normalize_audio(out, self.sample_rate, strategy=normalize, target_lufs=target_lufs,
+                                        limit="none" if limit == "truepeak" else limit, device=on)
         if output_sr is not None and int(output_sr) != self.sample_rate:
             from . import audio
             # on the device the decoder left its output on; a CPU decoder's output goes through the model's device and comes back
             out = audio.resample(out, self.sample_rate, int(output_sr), device=out.device if out.device.type == "cuda" else self.device)
+        if normalize is not None and limit == "truepeak":
+            out = audio.limit_true_peak(out, self.sample_rate if output_sr is None else int(output_sr), ceiling_dbtp=ceiling_dbtp,
+                                        lookahead_ms=lookahead_ms, release_ms=release_ms,
+                                        device=out.device if out.device.type == "cuda" else self.device)
         return out
 
     @staticmethod
@@ -470,10 +481,12 @@ class Jen1:
 
 # generation.py:194-213
 def save_audio_tensor(audio_tensor: torch.Tensor, file_path: str, sample_rate: int = 48000, normalize: Optional[str] = None,
-                      target_lufs=-14.0, limit: str = "clip") -> None:
+                      target_lufs=-14.0, limit: str = "clip", ceiling_dbtp: float = -1.0, lookahead_ms: float = 1.5,
+                      release_ms: float = 100.0) -> None:
     """saves audio ``[C, N]`` (or ``[1, C, N]``: the batch axis is dropped) as a 16-bit PCM ``.wav`` file (``jen1_amd.wav.save`` in the place
     of ``torchaudio.save``).  ``normalize`` / ``target_lufs`` / ``limit`` (not in the reference): ``jen1_amd.audio.normalize_audio`` at
-    ``sample_rate`` in front of the writer, on the tensor's GPU or the current one; None writes the samples as they are."""
+    ``sample_rate`` in front of the writer, on the tensor's GPU or the current one; None writes the samples as they are.  ``ceiling_dbtp`` /
+    ``lookahead_ms`` / ``release_ms``: the keywords of ``limit="truepeak"``."""
     from . import wav
     audio_tensor = audio_tensor.detach()
     if audio_tensor.ndim == 3:
@@ -481,5 +494,6 @@ def save_audio_tensor(audio_tensor: torch.Tensor, file_path: str, sample_rate: i
     if normalize is not None:
         from . import audio
         audio_tensor = audio.normalize_audio(audio_tensor.to(torch.float32), sample_rate, strategy=normalize, target_lufs=target_lufs, limit=limit,
-                                             device=audio_tensor.device if audio_tensor.device.type == "cuda" else "cuda")
+                                             device=audio_tensor.device if audio_tensor.device.type == "cuda" else "cuda",
+                                             ceiling_dbtp=ceiling_dbtp, lookahead_ms=lookahead_ms, release_ms=release_ms)
     wav.save(file_path, audio_tensor.to("cpu", torch.float32), sample_rate)

@@ -19,7 +19,8 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 SOURCES = ["conv_gemm.hip", "stream_gemm.hip", "tile_gemm.hip", "norm_apply.hip", "attention.hip", "deep_kernel.hip", "elementwise.hip",
            "optimizer.hip", "train_gemm.hip", "train_ops.hip", "train_attn.hip", "encodec.hip", "big_gemm.hip", "train_glue.hip", "train_kvbank.hip",
-           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip", "latent_norm.hip", "vggish.hip", "analysis.hip", "vocoder.hip"]
+           "long_kernel.hip", "audio.hip", "t5.hip", "global_cond.hip", "windows.hip", "loudness.hip", "spectral.hip", "latent_norm.hip", "vggish.hip", "analysis.hip", "vocoder.hip",
+           "limiter.hip"]
 
 F32, BF16, FP8 = 0, 1, 2
 PRO_NONE, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_SILU = 0, 1, 2, 3, 4
@@ -346,6 +347,19 @@ VOCODER_SYMBOLS = {
     "jen1_phase_vocoder": (c_int, [_P, _P, c_int, c_int64, c_int, c_int, C.c_double, _P]),
 }
 
+# every symbol include/jen1_limiter.h declares (BS.1770 true-peak meter, look-ahead true-peak limiter: csrc/limiter.hip; taps of
+# jen1_true_peak: a HOST pointer)
+LIMITER_SYMBOLS = {
+    "jen1_true_peak_tile": (c_int, []),
+    "jen1_limiter_chunk": (c_int, []),
+    "jen1_limiter_max_lookahead": (c_int, []),
+    "jen1_true_peak_workspace_bytes": (c_int64, [c_int, c_int, c_int64]),
+    "jen1_true_peak": (c_int, [_P, _P, c_int64, _P, C.POINTER(C.c_double), c_int, c_int, c_int, c_int64, _P, c_int64, _P]),
+    "jen1_limiter_workspace_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "jen1_limit_true_peak": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int64, c_int, C.c_double, C.c_double, _P, c_int64,
+                                     _P]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -406,7 +420,8 @@ def load() -> C.CDLL:
     # pulls in the system runtime instead, and two runtimes in one process fail with "no ROCm-capable device".
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS, **SPECTRAL_SYMBOLS, **FAD_SYMBOLS, **ANALYSIS_SYMBOLS, **VOCODER_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **T5_SYMBOLS, **SPECTRAL_SYMBOLS, **FAD_SYMBOLS, **ANALYSIS_SYMBOLS, **VOCODER_SYMBOLS,
+                                     **LIMITER_SYMBOLS}.items():
         fn = getattr(lib, name)          # raises AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
